@@ -22,14 +22,24 @@ per GPU, integer-only generator, seeds 1234 + rank) -- inputs are resident when 
 
 Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant kernel (K2 welch_kernel<4096>
 + its finalize): algorithmic bytes = 2 B x samples per launch, duration from HIP events
-recorded on the launch stream around every K2 launch of the timed steps; ``roofline_valu``
-prices the same launch against the measured VALU issue ceiling (what actually bounds it);
-``secondary`` holds the scan and the K5 solve.  ``self_check`` validates the gathered results
-against what the synthetic captures were built to contain (known delays, known burst span), so a
-wrong multi-GPU exchange cannot print a plausible number.  ``cpu_baseline`` times the
-numpy/scipy oracle (oracle/gpsjam_oracle.py, kind "port") on a bounded prefix of the same
-capture on the host's cores (rank 0 at N = 1; with --cpu-baseline-all-ranks one process per rank at N > 1).  ``end_to_end`` (N = 1) is the
-file / host buffer -> result rate with PCIe included; it is never ``value``.
+recorded on the launch stream around every K2 launch of the timed steps.  ``self_check``
+validates the gathered results against what the synthetic captures were built to contain (known
+delays, known burst span), so a wrong multi-GPU exchange cannot print a plausible number.
+
+A plain run sets up, warms up, times the steps and prints the line; everything that takes runs of
+its own is measured only with ``--full``: ``roofline.solo``, ``roofline_valu`` (the same launch
+against the measured VALU issue ceiling, what actually bounds it), ``roofline_flops``,
+``secondary`` (the scan, the K5 solve, the acquisition search, the reference's operating point),
+``cpu_baseline`` (the numpy/scipy oracle, oracle/gpsjam_oracle.py, kind "port", on a bounded prefix
+of the same capture on the host's cores: rank 0 at N = 1; with --cpu-baseline-all-ranks one process
+per rank at N > 1), ``end_to_end`` (N = 1: the file / host buffer -> result rate with PCIe
+included; it is never ``value``), per_rank ``scan_ms`` and the --split ``second_stream_chain``.
+
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0's view) as .npy files:
+``results`` (float64 [streams, result vector], the vectors StepResults carries), ``tdoa`` (float64
+[pairs, 5]: i, j, lag, peak, margin) and, one capture per GPU, ``psd`` (float32 [rows, nperseg], rank
+0's Welch PSD).  The inputs are generated from fixed seeds, so runs with the same arguments compare
+output for output.
 """
 import argparse
 import hashlib
@@ -95,6 +105,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--capture-bytes", type=int, default=CAPTURE_BYTES)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the secondary figures (solo kernels, roofline views, "
+                         "acquisition search, reference operating point, CPU baseline, end to end); off: headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--no-reference-point", action="store_true",
@@ -280,6 +295,9 @@ def main():
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, gathered, stream.psd[:stream.rows])
+    full = args.full
 
     # solo figures (nothing else in flight), after the timed region: K2 next to its as-run figure,
     # which includes whatever the concurrently running scan/TDOA kernels cost it; the scan and the K5 solve
@@ -298,12 +316,13 @@ def main():
         return sum(out) / len(out)
 
     side = stream._side
-    solo_ms = timed(stream.welch, work_stream)
-    scan_ms = timed(stream.stream_scan, side)
-    d_on1 = torch.zeros(4, dtype=torch.int64, device="cuda")
-    onset_alone_ms = timed(lambda: stream.dev_side.onset_dev(cap, nbytes, 200000, 1000, 50.0, d_on1), side)
-    k5_ms = None
-    if rank == 0 and stream.pairs:
+    solo_ms = scan_ms = onset_alone_ms = k5_ms = acq_ms = None
+    if full:
+        solo_ms = timed(stream.welch, work_stream)
+        scan_ms = timed(stream.stream_scan, side)
+        d_on1 = torch.zeros(4, dtype=torch.int64, device="cuda")
+        onset_alone_ms = timed(lambda: stream.dev_side.onset_dev(cap, nbytes, 200000, 1000, 50.0, d_on1), side)
+    if full and rank == 0 and stream.pairs:
         scratch = [torch.empty_like(t) for t in (stream.lags, stream.peaks, stream.margins)]
 
         def k5():                       # the same launch as in the step, into scratch outputs
@@ -312,8 +331,7 @@ def main():
 
     # one cold acquisition search (32 PRNs x 71 Doppler bins x 10 ms) on the quiet start of the
     # capture -- nothing acquires there, so every PRN runs all ten integration steps (the worst case)
-    acq_ms = None
-    if rank == 0:
+    if full and rank == 0:
         try:
             from gpsjam import gnss
             srch = gnss.AcqSearch(dev)
@@ -333,7 +351,7 @@ def main():
     # the group's watchdog thread, polling the end event of a collective it has not yet seen complete (it looks every
     # 100 ms), asks about an event whose stream is being captured: hipErrorCapturedEvent, and torch ends the process
     # (seen once in ~15 runs of the short --force-exchange rehearsal, round 6).  gpsjam/local.py says the same to its users.
-    if rank == 0 and world == 1 and not grouped and not args.no_reference_point:
+    if full and rank == 0 and world == 1 and not grouped and not args.no_reference_point:
         try:
             psd_ref = torch.empty((dev.welch_rows(nbytes, CHUNK_SAMPLES, REF_NPERSEG), REF_NPERSEG), dtype=torch.float32, device="cuda")
             dev.reserve(max(dev.welch_workspace(nbytes, CHUNK_SAMPLES, REF_NPERSEG), dev.welch_workspace(nbytes, CHUNK_SAMPLES, NPERSEG)))
@@ -358,7 +376,7 @@ def main():
     per_rank = None
     if grouped:
         exchange_ms = sum(a.elapsed_time(b) for a, b in ex) / max(len(ex), 1)
-        per_rank = G.per_rank(torch, world, {"k2_ms": welch_ms, "scan_ms": scan_ms, "exchange_ms": exchange_ms,
+        per_rank = G.per_rank(torch, world, {"k2_ms": welch_ms, "scan_ms": scan_ms if full else float("nan"), "exchange_ms": exchange_ms,
                                              "step_ms": local_elapsed / max(args.steps, 1) * 1e3})
     proof = exchange_proof(args, torch, G, dev, stream.comm, world, rank)
 
@@ -366,7 +384,7 @@ def main():
     cpu = None
     # the contract asks for the CPU baseline on rank 0 at N = 1 only; --cpu-baseline-all-ranks times one oracle process
     # per rank at N > 1 as well
-    if not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_all_ranks or args.cpu_sample_chunks):
+    if full and not args.no_cpu_baseline and (world == 1 or args.cpu_baseline_all_ranks or args.cpu_sample_chunks):
         chunks = args.cpu_sample_chunks or (24 if world == 1 else 8)
         barrier()
         cpu = cpu_baseline(np, cap, chunks, stream, gathered if rank == 0 else None, world, ref_point if rank == 0 else None)
@@ -410,21 +428,10 @@ def main():
                          "launch_ms_spread": (lambda v: {"min": v[0], "median": v[len(v) // 2], "max": v[-1], "launches": len(v)})(
                              sorted(a.elapsed_time(b) for a, b in ev)) if ev else None,
                          "overlap": bool(stream.overlap),
-                         "solo": {"avg_launch_ms": solo_ms, "achieved": (nbytes / 1e9) / (solo_ms / 1e3),
-                                  "frac": (nbytes / 1e9) / (solo_ms / 1e3) / HBM_PEAK_GBS},
                          "note": "K2 is FP32-VALU/LDS bound, not HBM bound (DESIGN.md section 5); "
                                  "'achieved' is K2 as run in the timed steps, i.e. with the HBM-bound "
                                  "scan + TDOA kernels executing concurrently on a second stream when "
-                                 "overlap is true; 'solo' is K2 with nothing else in flight"},
-            "roofline_valu": valu_roofline(pmc, welch_ms, solo_ms),
-            "roofline_flops": flops_roofline(nbytes, welch_ms, solo_ms),
-            "secondary": {
-                "stream_scan_kernel (K1+K3+K4 fused) + threshold + tail kernels, solo": {
-                    "bound": "hbm", "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": scan_ms,
-                    "achieved": (nbytes / 1e9) / (scan_ms / 1e3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": (nbytes / 1e9) / (scan_ms / 1e3) / HBM_PEAK_GBS,
-                    **family_traffic("profiles/r06_pmc_scan/summary.json", nbytes)},
-            },
+                                 "overlap is true; 'solo' (--full) is K2 with nothing else in flight"},
             "results": {"pairs": [list(p) for p in tdoa.pairs], "lags": tdoa.lags,
                         "lag_margins": [round(m, 4) for m in tdoa.margins], "onsets": onsets,
                         "jamming_ranges_rank0": results[0].jamming_byte_ranges()[:4],
@@ -433,11 +440,23 @@ def main():
                                      proof=proof, world=world, share_gpu=args.share_gpu),
             "host": host_info(),
         }
-        line["secondary"]["gj_onset_dev alone (K4 through the fused pass + tail since round 6; its own kernel chain took 0.62 ms), solo"] = {
-            "bound": "hbm", "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": onset_alone_ms,
-            "achieved": (nbytes / 1e9) / (onset_alone_ms / 1e3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": (nbytes / 1e9) / (onset_alone_ms / 1e3) / HBM_PEAK_GBS,
-            "onset_equals_the_step's": bool(int(d_on1[0].item()) == results[0].onset)}
+        if full:
+            line["roofline"]["solo"] = {"avg_launch_ms": solo_ms, "achieved": (nbytes / 1e9) / (solo_ms / 1e3),
+                                        "frac": (nbytes / 1e9) / (solo_ms / 1e3) / HBM_PEAK_GBS}
+            line["roofline_valu"] = valu_roofline(pmc, welch_ms, solo_ms)
+            line["roofline_flops"] = flops_roofline(nbytes, welch_ms, solo_ms)
+            line["secondary"] = {
+                "stream_scan_kernel (K1+K3+K4 fused) + threshold + tail kernels, solo": {
+                    "bound": "hbm", "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": scan_ms,
+                    "achieved": (nbytes / 1e9) / (scan_ms / 1e3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": (nbytes / 1e9) / (scan_ms / 1e3) / HBM_PEAK_GBS,
+                    **family_traffic("profiles/r06_pmc_scan/summary.json", nbytes)},
+                "gj_onset_dev alone (K4 through the fused pass + tail since round 6; its own kernel chain took 0.62 ms), solo": {
+                    "bound": "hbm", "algorithmic_bytes_per_launch": nbytes, "avg_launch_ms": onset_alone_ms,
+                    "achieved": (nbytes / 1e9) / (onset_alone_ms / 1e3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": (nbytes / 1e9) / (onset_alone_ms / 1e3) / HBM_PEAK_GBS,
+                    "onset_equals_the_step's": bool(int(d_on1[0].item()) == results[0].onset)},
+            }
         if k5_ms is not None:
             # ingest 2N B per antenna + 32 L B per transform (four-step floor), A + P transforms
             L, P = 2 * SLICE, len(stream.pairs)
@@ -500,7 +519,7 @@ def main():
             line["cpu_baseline"] = cpu
         if per_rank is not None:
             line["per_rank"] = per_rank
-        if world == 1 and not args.no_end_to_end:
+        if full and world == 1 and not args.no_end_to_end:
             try:                        # a secondary figure must never cost the primary line
                 line["end_to_end"] = end_to_end(np, dev, cap, nbytes)
             except Exception as e:      # e.g. no room for the scratch copy of the capture
@@ -584,6 +603,8 @@ def run_split(args, np, torch, gpsjam, G, dev, work_stream, world, rank):
     barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and got is not None:
+        dump_outputs(args.dump_outputs, np, got)
     elapsed = G.reduce(torch, elapsed, "max") if world > 1 else elapsed
     welch_ms = sum(a.elapsed_time(b) for a, b in ev) / max(args.steps, 1)
     per_rank = None
@@ -597,7 +618,7 @@ def run_split(args, np, torch, gpsjam, G, dev, work_stream, world, rank):
     # the second stream's chain (scan, slots, [all-gather], K5, [gather], combine) against K2, one step in isolation:
     # does the chain end inside K2 or does it stick out?
     chain = None
-    if rank == 0 and st.overlap and world == 1 and st.is_root:
+    if args.full and rank == 0 and st.overlap and world == 1 and st.is_root:
         torch.cuda.synchronize()
         e0, e1, e2, e3 = (torch.cuda.Event(enable_timing=True) for _ in range(4))
         reps, k2_ms, front_ms, tail_ms = 5, 0.0, 0.0, 0.0
@@ -776,7 +797,7 @@ class Groups:
             good = [v for v in col if v == v]
             out[k] = {"min": min(good) if good else None, "max": max(good) if good else None, "by_rank": [v if v == v else None for v in col]}
         out["what"] = ("k2_ms: average K2 launch as run (HIP events on its stream); scan_ms: the fused scan + tail alone, after the "
-                       "timed region; exchange_ms: second-stream events around slot -> slot all-gather -> K5 -> pack -> result "
+                       "timed region (--full); exchange_ms: second-stream events around slot -> slot all-gather -> K5 -> pack -> result "
                        "gather of every step; step_ms: the rank's own wall time per step before it waits for the others")
         return out
 
@@ -1062,6 +1083,39 @@ def self_check(results, tdoa, onsets, nsamp, n_ant, n_pairs=None, proof=None, wo
             "streams_checked": len(results), "devices_ok": devices_ok,
             "passed": bool(ok_pairs) and all(ok_pairs) and len(ok_pairs) == n_pairs and all(ok_ranges) and all(ok_rank)
                       and devices_ok}
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SEED = 0
+
+
+def dump_outputs(path, np, got, psd=None):
+    """--dump-outputs: what the last timed step computed, as rank 0 receives it, to path/<name>.npy -- ``results``
+    (float64 [streams, result vector]: header, power map, mean spectrum and pair table of every stream), ``tdoa``
+    (float64 [pairs, 5]: i, j, lag, peak, margin of every solved pair) and ``psd`` (float32 [rows, nperseg]).  At most
+    DUMP_LIMIT_BYTES in all: an array that does not fit keeps a sample of its rows drawn with DUMP_SEED (the same rows
+    for the same arguments), and their indices go to <name>_rows.npy."""
+    _, tdoa = got.unpack()
+    table = [[i, j, lag, peak, margin] for (i, j), lag, peak, margin in zip(tdoa.pairs, tdoa.lags, tdoa.peaks, tdoa.margins)]
+    arrays = {"results": got.vectors.cpu().numpy().astype(np.float64),
+              "tdoa": np.array(table, dtype=np.float64).reshape(-1, 5)}
+    if psd is not None:
+        arrays["psd"] = psd.cpu().numpy().astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    room = DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        room -= 4096                                        # .npy header, generously
+        if a.nbytes > room:
+            row_bytes = a.nbytes // max(a.shape[0], 1) + 8  # + its index in <name>_rows.npy
+            keep = min(a.shape[0], max(room - 4096, 0) // row_bytes)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+            room -= 4096 + rows.size * 8
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        room -= a.nbytes
+    print(f"[bench] outputs of the last timed step: {', '.join(f'{k}{list(v.shape)}' for k, v in arrays.items())} -> {path}",
+          file=sys.stderr)
 
 
 def host_info():

@@ -122,7 +122,7 @@ def test_self_launch_two_ranks_share_gpu():
     """`python bench.py --gpus 2 --backend gloo --share-gpu --steps 3`: the real step on two ranks that share
     cuda:0, started by bench.py itself; one line, n_gpus 2, self_check passed."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "3",
-                        "--warmup", "1", "--precondition", "2", "--cpu-sample-chunks", "1"],
+                        "--warmup", "1", "--precondition", "2", "--cpu-sample-chunks", "1", "--full"],
                        capture_output=True, text=True, env=_env(), timeout=850)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -293,7 +293,7 @@ def test_split_rank0_load_of_eight_gpus_on_one():
     share of the pairs, both collectives over the one-rank RCCL group, and the three-launch combine over ALL eight ranks'
     part vectors (the other seven's prepared before the timed region).  Known delays and burst spans come back."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--split", "--emulate-world", "8", "--force-exchange", "--steps", "3",
-                        "--warmup", "1", "--precondition", "2", "--capture-bytes", str(1 << 28)],
+                        "--warmup", "1", "--precondition", "2", "--capture-bytes", str(1 << 28), "--full"],
                        capture_output=True, text=True, env=_env(), timeout=850)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -303,3 +303,70 @@ def test_split_rank0_load_of_eight_gpus_on_one():
     assert line["self_check"]["passed"] is True and line["self_check"]["pairs_checked"] == 3, line["self_check"]
     ch = line["second_stream_chain"]
     assert ch["combine_launches"] == 3 and ch["k2_ms"] > 0 and ch["pack_gather_combine_ms"] > 0
+
+
+def test_dump_outputs_stays_under_its_limit_with_a_seeded_sample():
+    """--dump-outputs writes the step's arrays as float64 / float32 .npy files; an array too large for the 64-MB budget
+    keeps a sample of its rows, the same rows every time, with their indices beside it."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "gps-jamming_amd"))
+    import bench
+    from gpsjam import sharded
+    pm = np.linspace(1.0, 2.0, 64, dtype=np.float32)
+    pairs = [(0, 1), (0, 2), (1, 2)]
+    vec = sharded.pack_results(
+        pm.size, 16, torch.from_numpy(pm), torch.tensor([1.0, 2.0, 3.0]), torch.tensor(0), torch.tensor(100),
+        torch.tensor(4.5), torch.tensor(7), torch.tensor(0), torch.tensor(0.0), torch.tensor(1.0),
+        torch.arange(16, dtype=torch.float32), 2, 0, pairs=pairs, pair_lags=torch.tensor([3, -5, -8], dtype=torch.int32),
+        pair_peaks=torch.tensor([9.0, 8.0, 7.0]), pair_margins=torch.tensor([0.5, 0.25, 0.125]), capacity=3)
+    got = sharded.StepResults(vec.unsqueeze(0), None, 3)
+    psd = torch.from_numpy(np.random.default_rng(1).random((5200, 4096), dtype=np.float32))   # 85 MB: over the limit
+    import tempfile
+    dumps = []
+    for _ in range(2):
+        d = tempfile.mkdtemp()
+        bench.dump_outputs(d, np, got, psd)
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64_000_000
+    a, b = dumps
+    assert sorted(a) == ["psd", "psd_rows", "results", "tdoa"]
+    assert a["results"].dtype == np.float64 and np.array_equal(a["results"], vec.numpy()[None])
+    assert a["tdoa"].dtype == np.float64 and a["tdoa"][:, :3].tolist() == [[0, 1, 3], [0, 2, -5], [1, 2, -8]]
+    rows = a["psd_rows"].astype(np.int64)
+    assert a["psd"].dtype == np.float32 and 0 < rows.size < 5200 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(a["psd"], psd.numpy()[rows])
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_run_times_the_steps_and_dumps_what_they_computed(tmp_path):
+    """`--steps K --dump-outputs DIR`: a plain run carries the headline fields and none of the --full figures, and writes
+    the last step's arrays; a --full run with the same arguments measures the secondary figures and dumps the same
+    outputs (the inputs come from fixed seeds)."""
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "4", "--warmup", "1", "--precondition", "2", "--capture-bytes", str(1 << 27)]
+    lines, dumps = [], []
+    for extra in ([], ["--full", "--no-cpu-baseline", "--no-end-to-end", "--no-reference-point"]):
+        d = tmp_path / ("full" if extra else "plain")
+        r = subprocess.run([sys.executable, BENCH] + common + ["--dump-outputs", str(d)] + extra,
+                           capture_output=True, text=True, env=_env(), timeout=850)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_json_line(r.stdout))
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    plain, full = lines
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["steps"] == 4 and plain["ms_per_step"] > 0 and plain["self_check"]["passed"] is True
+    assert not {"secondary", "roofline_valu", "roofline_flops", "cpu_baseline", "end_to_end"} & set(plain)
+    assert "solo" not in plain["roofline"]
+    assert "secondary" in full and "solo" in full["roofline"] and "roofline_valu" in full
+    a, b = dumps
+    assert sorted(a) == ["psd", "results", "tdoa"]
+    assert a["results"].dtype == np.float64 and a["results"].shape[0] == 1
+    assert a["psd"].dtype == np.float32 and a["psd"].shape[1] == 4096
+    assert a["tdoa"][:, 2].astype(int).tolist() == plain["results"]["lags"]
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-6, atol=0)
