@@ -28,6 +28,7 @@ import torch
 
 import logging
 
+from ._ffi import GJ_MAX_ANTENNAS
 from .sharded import LAG_INVALID, StepResults, all_pairs, result_len
 from .streams import stream_beside_checked
 
@@ -43,6 +44,10 @@ class LocalAntennas:
                  window: int = 1000, factor: float = 50.0, rssi_threshold: float = 0.0, side_streams: int = 3,
                  graph: bool = True, scan_first: bool = False):
         assert len(captures) >= 1 and all(c.dtype == torch.uint8 and c.is_contiguous() and c.is_cuda for c in captures)
+        if len(captures) > GJ_MAX_ANTENNAS:      # refused here, not at the first step (which may be inside a graph capture)
+            raise ValueError(f"LocalAntennas takes at most GJ_MAX_ANTENNAS = {GJ_MAX_ANTENNAS} captures, got {len(captures)}: "
+                             "K5's pairs may touch at most that many slots per call and one packing launch covers at most "
+                             "that many captures")
         self.dev, self.caps = dev, list(captures)
         self.n_ant = len(self.caps)
         d = self.caps[0].device

@@ -149,3 +149,45 @@ def test_round5_entry_points_check_their_arguments(dev):
     assert int(d_on.download(np.int64, 1)[0]) > 0 and np.isfinite(d_pow.download(np.float32, nch)).all()
     for b in (cap, d_pow, d_st, d_amp, d_on, d_slot, psd):
         b.free()
+
+
+def test_k5_range_ends_are_refused_and_context_survives(dev):
+    """The edges of what K5 accepts (include/gpsjam.h): a slice of 2^23 samples runs (test_gpu_parity.py,
+    test_k5_every_fft_length[L1=4096-n=8388608]) and 2^23 + 1 is GJ_ERR_UNSUPPORTED; 136 pairs (kMaxPairs) run and 137
+    are GJ_ERR_INVALID; the pairs of one gj_xcorr_slots_dev call may touch 16 slots and not 17 (GJ_ERR_UNSUPPORTED).
+    The refusals come after the slices were staged, and the context works afterwards."""
+    big = np.full(2 * ((1 << 23) + 1), 127, np.uint8)
+    with pytest.raises(gpsjam.GpsJamError) as e:
+        dev.xcorr_lags([big, big], [(0, 1)])
+    assert e.value.status == GJ_ERR_UNSUPPORTED and "2^23" in str(e.value)
+    del big
+    n = 1000
+    raws = [generate(StreamSpec(seed=9, antenna=a, delay=a, jam_start=-(1 << 40), jam_end=1 << 40, jam_sigma=50.0), n)
+            for a in range(17)]
+    pairs = [(i, j) for i in range(3) for j in range(3)] * 15 + [(0, 2)]
+    assert len(pairs) == 136
+    lags, _ = dev.xcorr_lags(raws[:3], pairs)
+    assert lags.tolist() == [j - i for i, j in pairs]
+    with pytest.raises(gpsjam.GpsJamError) as e:
+        dev.xcorr_lags(raws[:3], pairs + [(2, 1)])
+    assert e.value.status == GJ_ERR_INVALID and "n_pairs" in str(e.value)
+    # TDOA slots: [int64 flag 0 = valid][int64 start][2 n bytes of I/Q]
+    from gpsjam import _ffi
+    sb = dev.tdoa_slot_bytes(n)
+    host = np.zeros((17, sb), np.uint8)
+    for a, r in enumerate(raws):
+        host[a, _ffi.GJ_SLOT_HEADER:_ffi.GJ_SLOT_HEADER + 2 * n] = r
+    slots = dev.alloc(17 * sb).upload(host.reshape(-1))
+    chain = [(a, a + 1) for a in range(16)]                          # slots 0 .. 16: seventeen touched
+    d_l, d_p, d_m = dev.alloc(4 * 16), dev.alloc(4 * 16), dev.alloc(4 * 16)
+    with pytest.raises(gpsjam.GpsJamError) as e:
+        dev.xcorr_slots_dev(slots, sb, 17, n, chain, d_l, d_p, d_m)
+    assert e.value.status == GJ_ERR_UNSUPPORTED and "16 slots" in str(e.value)
+    dev.xcorr_slots_dev(slots, sb, 17, n, chain[1:], d_l, d_p, d_m)  # slots 1 .. 16: sixteen touched
+    dev.synchronize()
+    assert d_l.download(np.int32, 15).tolist() == [1] * 15
+    # and the context still works
+    lags, _ = dev.xcorr_lags(raws[:2], [(0, 1), (1, 0)])
+    assert lags.tolist() == [1, -1]
+    for b in (slots, d_l, d_p, d_m):
+        b.free()

@@ -57,3 +57,52 @@ def test_restatements_agree_with_the_oracle_on_synthetic_streams(seed, jam, nois
         if k is not None:
             np.testing.assert_allclose(got["mean"], avg, rtol=1e-6)
     np.testing.assert_allclose(ex.chunk_power(raw, 65536), orc.chunk_power(raw), rtol=1e-6)
+
+
+def test_xcorr_f64_is_the_references_lag_and_peak(golden_meta, g4_raws):
+    """The float64 restatement of K5 against the reference's own lags and peaks (G4, both slice sizes, own and common
+    starts) and against the oracle's complex64 arithmetic; its margin precondition holds on all of them."""
+    g4 = golden_meta["g4"]
+    on = g4["onset"]
+    for n in gi.G4_SLICES:
+        for a, b in ((0, 1), (0, 2), (1, 2)):
+            zi = orc.tdoa_unpack(g4_raws[a][2 * on[a]:2 * (on[a] + n)])
+            for kind, s in (("own", on[b]), ("common", on[a])):
+                zj = orc.tdoa_unpack(g4_raws[b][2 * s:2 * (s + n)])
+                lag, peak, run = ex.xcorr_f64(zj, zi)
+                assert lag == g4[f"lags_{kind}_start"][f"{n}_{a}{b}"] == orc.xcorr_lag(zj, zi)[0]
+                np.testing.assert_allclose(peak, g4["peaks"][f"{kind}_{n}_{a}{b}"], rtol=1e-6)
+                assert 0.0 < run < 0.05 * peak
+
+
+@pytest.mark.parametrize("n1,n0", [(1, 1), (2, 2), (1, 7), (7, 5), (100, 100), (1000, 999), (4097, 4097)])
+def test_xcorr_f64_is_a_direct_correlation(n1, n0):
+    """Every 'full' lag of the FFT restatement equals the direct sum (numpy.correlate conjugates its second argument:
+    c[m] = sum_n sig1[n + m - (len(sig0)-1)] conj(sig0[n])), and lag / peak / runner-up are read off it as documented:
+    first maximum, |c| there, largest |c| anywhere else.  Peaks planted at both ends of the lag range are found."""
+    rng = np.random.default_rng(n1 * 7919 + n0)
+    s1 = rng.normal(size=n1) + 1j * rng.normal(size=n1)
+    s0 = rng.normal(size=n0) + 1j * rng.normal(size=n0)
+    direct = np.correlate(s1, s0, "full")
+    got = ex.xcorr_full_f64(s1, s0)
+    assert got.shape == direct.shape
+    np.testing.assert_allclose(got, direct, rtol=0, atol=1e-9 * np.abs(direct).max())
+    for plant in (0, direct.size - 1, direct.size // 2):   # lag -(n0-1), lag n1-1, the middle
+        a, b = s1.copy(), s0.copy()
+        if plant == 0:
+            b[-1], a[0] = 40.0, 40.0j
+        elif plant == direct.size - 1:
+            b[0], a[-1] = 40.0, -40.0
+        else:
+            a, b = np.zeros_like(a), np.zeros_like(b)
+            a[:min(n0, n1)] = b[:min(n0, n1)] = s0[:min(n0, n1)]
+        c = np.abs(np.correlate(a, b, "full"))
+        k = int(np.argmax(c))
+        lag, peak, run = ex.xcorr_f64(a, b)
+        assert lag == k - (n0 - 1)
+        if plant != direct.size // 2:
+            assert k == plant
+        np.testing.assert_allclose(peak, c[k], rtol=1e-12)
+        rest = np.delete(c, k)
+        np.testing.assert_allclose(run, rest.max() if rest.size else 0.0, rtol=1e-9, atol=1e-9 * c[k])
+        assert lag == orc.xcorr_lag(a.astype(np.complex64), b.astype(np.complex64))[0]

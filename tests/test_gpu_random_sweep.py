@@ -4,6 +4,7 @@ Same tolerances as there: power map 1e-6 rel, PSD 1e-4 rel on the linear PSD, am
 import numpy as np
 import pytest
 
+import k5_check as k5
 from gpsjam.synth import StreamSpec, generate
 from oracle import gpsjam_oracle as orc
 
@@ -187,3 +188,88 @@ def test_sweep_unpack_convention(dev, case):
             assert st.first_index == -1
     finally:
         dev.set_unpack()
+
+
+# ----------------------------------------------------------------------------- K5: the many-pair path
+# With more pairs than twice the slices K5 transforms every slice's rows once and keeps them (xc_rows_kernel<0>), then
+# forms each pair's product and inverse rows (xc_rows_kernel<1>); with fewer, one kernel does both per pair
+# (xc_rows_pair_kernel).  LocalAntennas reaches the first path from six antennas on (all_pairs(6) = 15 > 12).  Each case
+# is held to the references (tests/k5_check.py) and solved again in calls of at most 2 x slices pairs, which take the
+# pair kernel: the lags are equal and peaks and margins bit-identical (both paths form conj(Z_j) Z_i with the same
+# expression from the same float32 row spectra).
+def _many_pairs(n_slices, extra):
+    return [(i, j) for i in range(n_slices) for j in range(i + 1, n_slices)] + extra     # sharded.all_pairs + extra
+
+
+K5_MANY = [   # (n, slices, pairs): both orders, self-pairs and duplicates
+    (50_000, 3, [(0, 1), (1, 0), (0, 2), (2, 0), (1, 2), (1, 1), (0, 1), (2, 2)]),                      # L1 = 32
+    (1_100_001, 3, [(0, 1), (1, 0), (0, 2), (2, 1), (1, 2), (0, 0), (1, 0), (0, 1), (2, 2)]),           # L1 = 1024
+    (50_000, 6, _many_pairs(6, [(5, 0), (3, 3), (0, 1)])),
+    (50_000, 9, _many_pairs(9, [(8, 7), (4, 4), (2, 3)])),
+    (50_000, 16, _many_pairs(16, [(a, a) for a in range(16)])),                                         # 136 = kMaxPairs
+]
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.uint32)
+
+
+@pytest.mark.parametrize("n,n_slices,pairs", K5_MANY, ids=[f"{s}x{len(p)}-n={n}" for n, s, p in K5_MANY])
+def test_k5_many_pair_path(dev, n, n_slices, pairs):
+    assert len(pairs) > 2 * n_slices
+    delays = [0] + [int(d) for d in np.random.RandomState(n_slices).randint(-300, 301, n_slices - 1)]
+    raws = [generate(StreamSpec(seed=1700 + n_slices, antenna=a, delay=d, jam_start=-(1 << 40), jam_end=1 << 40,
+                                jam_sigma=50.0), n) for a, d in enumerate(delays)]
+    lags, peaks, margins = dev.xcorr_lags(raws, pairs, want_margins=True)
+    ref = {}
+    for (i, j), lag, pk, m in zip(pairs, lags, peaks, margins):
+        if (i, j) not in ref:
+            ref[(i, j)] = k5.mirror(ref[(j, i)]) if (j, i) in ref else k5.expect(raws[i], raws[j])
+        k5.check(lag, pk, m, ref[(i, j)], f"pair {(i, j)}")
+        assert lag == delays[j] - delays[i]
+    # the same pairs in calls small enough for the pair kernel
+    step = 2 * n_slices
+    few = [dev.xcorr_lags(raws, pairs[k:k + step], want_margins=True) for k in range(0, len(pairs), step)]
+    f_lags, f_peaks, f_margins = (np.concatenate(x) for x in zip(*few))
+    np.testing.assert_array_equal(f_lags, lags)
+    np.testing.assert_array_equal(_bits(f_peaks), _bits(peaks))
+    np.testing.assert_array_equal(_bits(f_margins), _bits(margins))
+    # and through the device-pointer entry point (resident captures, starts on the device)
+    bufs = [dev.alloc(r.size).upload(r) for r in raws]
+    d_starts = dev.alloc(8 * n_slices).upload(np.zeros(n_slices, np.int64))
+    d_l, d_p, d_m = (dev.alloc(4 * len(pairs)) for _ in range(3))
+    dev.xcorr_lags_dev(bufs, [r.size for r in raws], d_starts, n, pairs, d_l, d_p, d_m)
+    dev.synchronize()
+    np.testing.assert_array_equal(d_l.download(np.int32, len(pairs)), lags)
+    np.testing.assert_array_equal(d_p.download(np.uint32, len(pairs)), _bits(peaks))
+    np.testing.assert_array_equal(d_m.download(np.uint32, len(pairs)), _bits(margins))
+
+
+def test_k5_many_pair_path_invalid_starts(dev):
+    """Six captures, every pair plus a self-pair and a reversed one (17 > 12: the many-pair path), through
+    xcorr_lags_dev with one start of -1 and one slice that runs off its capture: exactly their pairs are
+    GJ_LAG_INVALID, the others equal the oracle at the given starts."""
+    import gpsjam
+    from gpsjam import sharded
+    n, total = 50_000, 180_000
+    delays = [0, 7, -11, 25, -3, 14]
+    raws = [generate(StreamSpec(seed=1801, antenna=a, delay=d, jam_start=-(1 << 40), jam_end=1 << 40, jam_sigma=55.0),
+                     total - 1000 * a) for a, d in enumerate(delays)]
+    starts = np.array([40_000, 41_000, -1, 39_000, total - 4000 - n + 1, 60_000], np.int64)
+    assert starts[4] + n == raws[4].size // 2 + 1                                # one sample past the end
+    pairs = sharded.all_pairs(6) + [(3, 3), (5, 1)]
+    assert len(pairs) > 12
+    bufs = [dev.alloc(r.size).upload(r) for r in raws]
+    d_starts = dev.alloc(8 * 6).upload(starts)
+    d_l, d_p, d_m = (dev.alloc(4 * len(pairs)) for _ in range(3))
+    dev.xcorr_lags_dev(bufs, [r.size for r in raws], d_starts, n, pairs, d_l, d_p, d_m)
+    dev.synchronize()
+    lags, peaks, margins = (d_l.download(np.int32, len(pairs)), d_p.download(np.float32, len(pairs)),
+                            d_m.download(np.float32, len(pairs)))
+    for (i, j), lag, pk, m in zip(pairs, lags, peaks, margins):
+        if {i, j} & {2, 4}:
+            assert lag == gpsjam.GJ_LAG_INVALID and pk == 0 and m == 0, (i, j)
+            continue
+        sl = [r[2 * s:2 * (s + n)] for r, s in ((raws[i], starts[i]), (raws[j], starts[j]))]
+        k5.check(lag, pk, m, k5.expect(*sl), f"pair {(i, j)}")
+        assert lag == delays[j] - delays[i] - (starts[j] - starts[i])

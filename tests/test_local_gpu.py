@@ -118,3 +118,64 @@ def test_local_antennas_edge_shapes(dev):
     finally:
         torch.cuda.set_stream(torch.cuda.default_stream())
         dev.set_stream(None, external=False)
+
+
+_MANY_REFS = {}
+
+
+@pytest.mark.parametrize("graph", [False, True])
+@pytest.mark.parametrize("n_ant", [6, 9, 16])
+def test_local_antennas_six_to_sixteen(dev, n_ant, graph):
+    """6 to 16 captures at the reference's slice size: all_pairs(n) > 2 n from six antennas on, so K5 takes its
+    many-pair path (xc_rows_kernel<0> / <1>) inside the step; at 16 with graph=True the captured step runs 120 pairs in
+    the workspace __init__ reserved.  Over three steps (eager, capture, replay) every pair's lag is the known delay
+    between the onsets, the oracle's lag on the onset-aligned slices, and its peak and margin are the float64
+    restatement's (tests/k5_check.py)."""
+    import torch
+    import k5_check as k5
+    from gpsjam import local
+    from gpsjam.synth import StreamSpec, generate
+    from oracle import gpsjam_oracle as orc
+    n, sl = 600_000, 50_000
+    delays = [0] + [int(d) for d in np.random.RandomState(n_ant).randint(-40, 41, n_ant - 1)]
+    raws = [generate(StreamSpec(seed=72, antenna=a, delay=d, jam_start=300_000, jam_end=1 << 40, jam_sigma=55.0), n)
+            for a, d in enumerate(delays)]
+    kw = dict(chunk_samples=131072, nperseg=1024, slice_samples=sl)
+    work = torch.cuda.Stream()
+    torch.cuda.set_stream(work)
+    dev.set_stream(work.cuda_stream)
+    try:
+        with local.LocalAntennas(dev, [torch.from_numpy(r).cuda() for r in raws], graph=graph, **kw) as st:
+            assert len(st.pairs) == n_ant * (n_ant - 1) // 2 > 2 * n_ant
+            steps = [st.step().unpack() for _ in range(3)]
+            if graph:
+                assert st._graphs is not None and all(g is not None for g in st._graphs), "the capture was refused"
+        if n_ant not in _MANY_REFS:
+            onsets = [orc.tdoa_onset(orc.tdoa_unpack(r)) for r in raws]
+            cut = [r[2 * o:2 * (o + sl)] for r, o in zip(raws, onsets)]
+            _MANY_REFS[n_ant] = (onsets, {(i, j): (k5.expect(cut[i], cut[j]), orc.xcorr_lag(orc.tdoa_unpack(cut[j]),
+                                                                                                 orc.tdoa_unpack(cut[i]))[0])
+                                          for i, j in st.pairs})
+        onsets, ref = _MANY_REFS[n_ant]
+        for k, (res, td) in enumerate(steps):
+            assert [r.onset for r in res] == onsets and td.pairs == st.pairs
+            for (i, j), lag, pk, m in zip(td.pairs, td.lags, td.peaks, td.margins):
+                assert lag + onsets[j] - onsets[i] == delays[j] - delays[i], (k, i, j, lag)
+                assert lag == ref[(i, j)][1]
+                k5.check(lag, pk, m, ref[(i, j)][0], f"step {k} pair {(i, j)}")
+    finally:
+        torch.cuda.set_stream(torch.cuda.default_stream())
+        dev.set_stream(None, external=False)
+
+
+def test_local_antennas_refuse_seventeen_captures(dev):
+    """17 captures are more than GJ_MAX_ANTENNAS: K5 would refuse all_pairs(17) (17 slots touched) at the first step,
+    possibly inside a graph capture, and one packing launch covers at most 16 captures.  LocalAntennas refuses at
+    construction, naming the limit, before it makes a stream or a buffer (16, the limit, run in the test above)."""
+    import torch
+    from gpsjam import local
+    caps = [torch.full((2 * 300_000,), 127, dtype=torch.uint8, device="cuda") for _ in range(17)]
+    with pytest.raises(ValueError, match="at most GJ_MAX_ANTENNAS = 16 captures, got 17"):
+        local.LocalAntennas(dev, caps, slice_samples=50_000, graph=True)
+    raw = np.full(2 * 1000, 127, np.uint8)
+    assert dev.xcorr_lags([raw, raw], [(0, 1)])[0][0] == 0             # the context is untouched (constant slices: lag 0)
