@@ -29,8 +29,8 @@ import torch
 import logging
 
 from ._ffi import GJ_MAX_ANTENNAS
-from .sharded import LAG_INVALID, StepResults, all_pairs, result_len
-from .streams import stream_beside_checked
+from .sharded import StepResults, all_pairs, result_len
+from .streams import pair_outputs, scan_workspace, side_context
 
 _log = logging.getLogger("gpsjam.local")
 
@@ -42,7 +42,7 @@ class LocalAntennas:
     def __init__(self, dev, captures: Sequence[torch.Tensor], *, chunk_bytes: int = 65536, chunk_samples: int = 2048000,
                  nperseg: int = 1024, fs: float = 2.048e6, slice_samples: int = 50000, noise_samples: int = 200000,
                  window: int = 1000, factor: float = 50.0, rssi_threshold: float = 0.0, side_streams: int = 3,
-                 graph: bool = True, scan_first: bool = False):
+                 graph: bool = True):
         assert len(captures) >= 1 and all(c.dtype == torch.uint8 and c.is_contiguous() and c.is_cuda for c in captures)
         if len(captures) > GJ_MAX_ANTENNAS:      # refused here, not at the first step (which may be inside a graph capture)
             raise ValueError(f"LocalAntennas takes at most GJ_MAX_ANTENNAS = {GJ_MAX_ANTENNAS} captures, got {len(captures)}: "
@@ -54,19 +54,17 @@ class LocalAntennas:
         self.chunk_bytes, self.chunk_samples, self.nperseg, self.fs = chunk_bytes, chunk_samples, nperseg, fs
         self.slice_samples, self.noise_samples, self.window, self.factor = slice_samples, noise_samples, window, factor
         self.rssi_threshold = rssi_threshold
-        self.scan_first = bool(scan_first)
         self._main = torch.cuda.current_stream(d)
         dev.set_stream(self._main.cuda_stream)
-        # side streams, each on a hardware queue of its own (tested), each with a context (= workspace) bound to it
+        # side streams, each tested to run beside the main stream and the others, each with a context (= workspace) bound to
+        # it (gpsjam.streams.side_context)
         self._sides: List[tuple] = []
         #: True when every side stream was TESTED to run beside the main stream and the other side streams; False: the
         #: step is still correct (cross-stream order is by events) but its chains run one after the other (a warning is logged)
         self.streams_overlap = True
         for _ in range(max(1, min(self.n_ant, int(side_streams)))):
-            sdev = type(dev)(dev.index)
-            s, ok = stream_beside_checked([(dev, self._main)] + self._sides, device=d)
+            sdev, s, ok = side_context(dev, [(dev, self._main)] + self._sides, d)
             self.streams_overlap = self.streams_overlap and ok
-            sdev.set_stream(s.cuda_stream)
             self._sides.append((sdev, s))
         self.nbytes = [int(c.numel()) for c in self.caps]
         self.n_chunks = [dev.chunk_count(n, chunk_bytes) for n in self.nbytes]
@@ -80,11 +78,7 @@ class LocalAntennas:
         self.slot_bytes = dev.tdoa_slot_bytes(slice_samples)
         self.slots = torch.zeros((self.n_ant, self.slot_bytes), dtype=torch.uint8, device=d)
         self.pairs = all_pairs(self.n_ant)
-        npairs = max(len(self.pairs), 1)
-        self.d_pairs = torch.tensor([x for p in self.pairs for x in p] or [0, 0], dtype=torch.int32, device=d)
-        self.lags = torch.full((npairs,), LAG_INVALID, dtype=torch.int32, device=d)
-        self.peaks = torch.zeros(npairs, dtype=f32, device=d)
-        self.margins = torch.zeros(npairs, dtype=f32, device=d)
+        self.d_pairs, self.lags, self.peaks, self.margins = pair_outputs(self.pairs, d)
         self.final_len = max(result_len(n, nperseg, len(self.pairs)) for n in self.n_chunks)
         self._final = [torch.zeros((self.n_ant, self.final_len), dtype=torch.float64, device=d) for _ in range(2)]
         self._done = [torch.cuda.Event() for _ in range(2)]
@@ -102,7 +96,7 @@ class LocalAntennas:
         # workspaces: nothing is allocated inside a step
         dev.reserve(max(dev.welch_workspace(n, chunk_samples, nperseg) for n in self.nbytes) * (self.n_ant if self._k2_batched else 1))
         for k, (sdev, _) in enumerate(self._sides):
-            ws = max(self.nbytes) // 48 + (1 << 20)
+            ws = scan_workspace(max(self.nbytes))
             if k == 0 and self.pairs:
                 ws = max(ws, dev.xcorr_workspace(self.n_ant, slice_samples, len(self.pairs)))
             sdev.reserve(ws)
@@ -113,21 +107,14 @@ class LocalAntennas:
         self._ev_go.record(main)                     # the previous step's packing has read what the chains overwrite
         for _, s in self._sides:
             s.wait_event(self._ev_go)
-        def k2():
-            if self._k2_batched:     # captures of one length: one transform launch + one finalize for all of them
-                self.dev.welch_batch_dev(self.caps, self.nbytes[0], self.chunk_samples, self.nperseg, self.fs, self.psd)
-                return
+        # K2 is issued first: the main stream's K2 launches are the longer chain, and delaying them behind the side chains'
+        # scans was measured to cost more than the scans gain (graph 0.300 against 0.262 ms per step).
+        if self._k2_batched:         # captures of one length: one transform launch + one finalize for all of them
+            self.dev.welch_batch_dev(self.caps, self.nbytes[0], self.chunk_samples, self.nperseg, self.fs, self.psd)
+        else:
             for a, cap in enumerate(self.caps):
                 if self.rows[a]:
                     self.dev.welch_dev(cap, self.nbytes[a], self.chunk_samples, self.nperseg, self.fs, self.psd[a])
-
-        # Which chain is issued first: K2 (default).  With the side chains down to two launches per capture the other
-        # order was tried -- the fused scan takes 9 us on a 10-s capture when it has the chip, ~40 us beside a K2 launch --
-        # and measured slower, graph 0.300 against 0.262 ms per step, eager 0.273 against 0.270 (two rounds on one box,
-        # tools/deployment_probe.py [--k2-first]): the main stream's three K2 launches are still the longer chain, and
-        # delaying them costs more than the scans gain.  ``scan_first`` keeps the experiment reachable.
-        if not self.scan_first:
-            k2()
         for a, cap in enumerate(self.caps):
             sdev, _ = self._sides[a % len(self._sides)]
             # two launches per capture: the fused pass, then the tail (threshold, amplitude totals, onset, slot)
@@ -135,8 +122,6 @@ class LocalAntennas:
                                   self.noise_samples, self.window, self.factor, self.onset[a],
                                   d_stats=self.stats[a] if self.n_chunks[a] else None, slice_samples=self.slice_samples,
                                   d_slot=self.slots[a])
-        if self.scan_first:
-            k2()
         sdev0, s0 = self._sides[0]
         for k in range(1, len(self._sides)):         # every slot is in place before the pairs are solved
             self._ev_side[k].record(self._sides[k][1])

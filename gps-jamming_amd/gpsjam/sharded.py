@@ -23,7 +23,6 @@ backend (tests) and on HIP tensors with the nccl (= RCCL) backend (bench.py).
 """
 from __future__ import annotations
 
-import contextlib
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple  # noqa: F401
 
@@ -31,6 +30,8 @@ import logging
 
 import numpy as np
 import torch
+
+from .streams import StepStreams, pair_outputs, scan_workspace
 
 _log = logging.getLogger("gpsjam.sharded")
 
@@ -346,10 +347,10 @@ class StepResults:
         return self.unpack()[1]
 
 
-class AntennaStream:
+class AntennaStream(StepStreams):
     """Device-resident pipeline of one capture on one GPU (uses torch only for device
     memory, streams and -- with ``transport="torch"`` -- the collectives; every kernel is a
-    gpsjam C-ABI call).
+    gpsjam C-ABI call).  Its streams and their events are ``gpsjam.streams.StepStreams``.
 
     ``exchange_always``: with ``world_size == 1`` and an initialised process group of one, still issue the slot
     all-gather and the result gather (what N > 1 ranks do), so that the collective path can be run on one GPU.
@@ -373,38 +374,18 @@ class AntennaStream:
                  transport="torch", side_device=None, exchange_always: bool = False, pairs=None,
                  side_priority: int = 0, pack_on_side: bool = False, group=None):
         assert capture.dtype == torch.uint8 and capture.is_contiguous()
-        self.dev, self.cap = dev, capture
+        self.cap = capture
         self.group = group                 # torch.distributed group of the exchange (None: the default group)
-        # K2 is bound by VALU issue and leaves ~90 % of the HBM bandwidth idle, the fused scan is HBM
-        # bound: with ``overlap`` the scan, threshold and TDOA kernels run on a second HIP
-        # stream (own gpsjam context = own workspace) concurrently with K2 and join in pack().
-        if overlap is None:
-            overlap = capture.is_cuda and hasattr(dev, "_ctx")
-        self.overlap = bool(overlap)
-        self.streams_overlap = None        # one stream: nothing to overlap
-        self.dev_side = dev
-        self._main = None
-        if capture.is_cuda and hasattr(dev, "_ctx"):
-            # the pipeline's torch ops, its events and the gpsjam kernels must share one stream
-            self._main = torch.cuda.current_stream(capture.device)
-            dev.set_stream(self._main.cuda_stream)
-        self._own_side = False
-        if self.overlap:
-            self.dev_side = side_device if side_device is not None else type(dev)(dev.index)
-            self._own_side = side_device is None
-            # side_priority < 0: a high-priority HIP stream -- its (short) kernels are dispatched ahead of K2's waiting
-            # workgroups, which shortens the scan -> slot -> exchange -> K5 chain without changing the total work
-            # ... on a hardware queue of its own: two streams the runtime has mapped to one queue run one after the other
-            from .streams import stream_beside_checked
-            #: False: no stream could be found that runs beside the main one (results unaffected, chains serialised)
-            self._side, self.streams_overlap = stream_beside_checked([(dev, self._main)], device=capture.device, priority=int(side_priority))
-            self.dev_side.set_stream(self._side.cuda_stream)
-            self._ev_free = torch.cuda.Event()      # main: previous results consumed, buffers may be rewritten
-            self._ev_side = torch.cuda.Event()      # side: scan / TDOA results ready
-            self._ev_packed = torch.cuda.Event()    # main: this step's result vector is packed
-            self._ev_free.record(self._main)
-        else:
-            self._side = self._main
+        # with ``overlap`` the scan, threshold and TDOA kernels run on the side stream, concurrently with K2, and join in
+        # pack().  side_priority < 0: a high-priority HIP stream -- its (short) kernels are dispatched ahead of K2's waiting
+        # workgroups, which shortens the scan -> slot -> exchange -> K5 chain without changing the total work.
+        # ``pack_on_side``: the result vector is packed on the side stream (behind K5, where its inputs come from), so the
+        # main stream carries K2 + finalize and nothing else; needs two PSD buffers, written alternately (gpsjam/split.py
+        # does the same, where it pays: NOTES_r05 section 5).  Off by default: on the 1-GiB step it is measured neutral.
+        on_gpu = capture.is_cuda and hasattr(dev, "_ctx")
+        super().__init__(dev, torch.cuda.current_stream(capture.device) if on_gpu else None,
+                         on_gpu if overlap is None else overlap, device=capture.device, priority=int(side_priority),
+                         side_device=side_device, pack_on_side=pack_on_side)
         self.nbytes = capture.numel()
         self.rank, self.world = rank, world_size
         self.chunk_bytes, self.chunk_samples, self.nperseg, self.fs = chunk_bytes, chunk_samples, nperseg, fs
@@ -416,16 +397,8 @@ class AntennaStream:
         self.power = torch.empty(self.n_chunks, dtype=torch.float32, device=d)
         self.stats = torch.empty(3, dtype=torch.float32, device=d)
         self.mask = torch.empty(self.n_chunks, dtype=torch.uint8, device=d)
-        # ``pack_on_side``: the result vector is packed on the second stream (behind K5, where its inputs come from), so the
-        # main stream carries K2 + finalize and nothing else; needs two PSD buffers, written alternately (gpsjam/split.py
-        # does the same, where it pays: NOTES_r05 section 5).  Off by default: on the 1-GiB step it is measured neutral.
-        self._pack_on_side = bool(pack_on_side) and self.overlap
         self.psd2 = [torch.empty((max(self.rows, 1), nperseg), dtype=torch.float32, device=d) for _ in range(2 if self._pack_on_side else 1)]
         self.psd = self.psd2[0]
-        self._pidx = 0
-        if self._pack_on_side:
-            self._ev_psd = [torch.cuda.Event(), torch.cuda.Event()]
-            self._ev_psd_read = [None, None]
         self.amp = torch.zeros(4, dtype=torch.int64, device=d)        # gj_amp_stats (32 bytes)
         self.onset = torch.zeros(4, dtype=torch.int64, device=d)      # gj_onset (32 bytes)
         # collectives
@@ -459,11 +432,7 @@ class AntennaStream:
             self.slots[1:].copy_(aux_slots)
         # no exchange: the slot is written in place; otherwise a send buffer of its own
         self.my_slot = self.slots[0] if not self._exchange else torch.zeros(self.slot_bytes, dtype=torch.uint8, device=d)
-        npairs = max(len(self.pairs), 1)
-        self.d_pairs = torch.tensor([x for p in self.pairs for x in p] or [0, 0], dtype=torch.int32, device=d)
-        self.lags = torch.full((npairs,), LAG_INVALID, dtype=torch.int32, device=d)
-        self.peaks = torch.zeros(npairs, dtype=torch.float32, device=d)
-        self.margins = torch.zeros(npairs, dtype=torch.float32, device=d)
+        self.d_pairs, self.lags, self.peaks, self.margins = pair_outputs(self.pairs, d)
         # two sets, used alternately: step k's consumer may still be reading one while step k + 1 fills the other
         rl = result_len(self.n_chunks, nperseg, self.pair_cap)
         self._results = [torch.zeros(rl, dtype=torch.float64, device=d) for _ in range(2)]
@@ -474,23 +443,13 @@ class AntennaStream:
         self.result = self._results[0]
         # workspaces: K5 transforms at most the antennas this rank's pairs name
         ants = len({a for p in self.pairs for a in p}) or 1
-        ws_side = max(dev.xcorr_workspace(ants, slice_samples, npairs), self.nbytes // 48 + (1 << 20))
-        ws_main = dev.welch_workspace(self.nbytes, chunk_samples, nperseg)
-        if self.overlap:
-            dev.reserve(ws_main)
-            self.dev_side.reserve(ws_side)
-        else:
-            dev.reserve(max(ws_main, ws_side))
-
-    def _on_side(self):
-        """Context manager: torch's current stream = the side stream (no-op without overlap)."""
-        return torch.cuda.stream(self._side) if self.overlap else contextlib.nullcontext()
+        self.reserve(dev.welch_workspace(self.nbytes, chunk_samples, nperseg),
+                     max(dev.xcorr_workspace(ants, slice_samples, len(self.lags)), scan_workspace(self.nbytes)))
 
     # ---------------------------------------------------------------- per-capture kernels
     def stream_scan(self):
         """K1 + K3 + K4 in one pass over the capture, then the noise-floor threshold."""
-        if self.overlap:
-            self._side.wait_event(self._ev_free)
+        self.begin_side()
         d = self.dev_side
         # two launches: the fused pass, then the tail -- threshold, amplitude totals, onset record and this capture's
         # TDOA slot (gj_capture_scan_dev; tdoa() finds the slot cut)
@@ -499,29 +458,18 @@ class AntennaStream:
                            d_stats=self.stats if self.n_chunks else None, d_mask=self.mask if self.n_chunks else None,
                            slice_samples=self.slice_samples, d_slot=self.my_slot)
         self._slot_cut = True
-        if self.overlap:
-            self._ev_side.record(self._side)
+        self.end_side()
 
     def welch(self):
-        if self._pack_on_side:
-            self._pidx ^= 1
-            self.psd = self.psd2[self._pidx]
-            if self._ev_psd_read[self._pidx] is not None:           # the packing of two steps ago has read this buffer
-                self._main.wait_event(self._ev_psd_read[self._pidx])
+        self.psd = self.psd2[self._psd_turn.before_k2()]
         self.dev.welch_dev(self.cap, self.nbytes, self.chunk_samples, self.nperseg, self.fs, self.psd)
-        if self._pack_on_side:
-            self._ev_psd[self._pidx].record(self._main)
-
-    def scan(self):
-        """Everything that only needs this rank's capture (no host synchronisation)."""
-        self.stream_scan()
-        self.welch()
+        self._psd_turn.after_k2()
 
     # ---------------------------------------------------------------- the TDOA exchange
     def tdoa(self):
         """Own slice -> TDOA slot; ONE all-gather puts every rank's slot on every rank; this rank solves
         its share of the antenna pairs with one multi-pair K5 launch.  All on the second stream, beside K2."""
-        with self._on_side():
+        with self.on_side():
             dev = self.dev_side
             if not getattr(self, "_slot_cut", False):      # tdoa() without a stream_scan() in front of it
                 dev.tdoa_slot_dev(self.cap, self.nbytes, self.onset, self.slice_samples, self.my_slot)
@@ -534,29 +482,17 @@ class AntennaStream:
             if self.pairs:
                 dev.xcorr_slots_dev(self.slots, self.slot_bytes, self.n_ant, self.slice_samples, self.pairs,
                                     self.lags, self.peaks, self.margins)
-            if self.overlap:
-                self._ev_side.record(self._side)
+            self.end_side()
 
     def pack(self) -> torch.Tensor:
         """Result vector of this stream, built by one kernel (layout = pack_results)."""
-        side = self._pack_on_side
-        stream, dev = (self._side, self.dev_side) if side else (self._main, self.dev)
-        if side:
-            stream.wait_event(self._ev_psd[self._pidx])
-        elif self.overlap:
-            self._main.wait_event(self._ev_side)
+        stream, dev = self.begin_pack()
         self._idx ^= 1
         self.result = self._results[self._idx]
         dev.pack_result_dev(self.n_chunks, self.power, self.stats, self.amp, self.onset, self.psd, self.rows,
                             self.nperseg, self.rank, len(self.pairs), self.pair_cap, self.d_pairs, self.lags,
                             self.peaks, self.margins, self.result)
-        if self.overlap:
-            self._ev_free.record(stream)       # the next step's scan / K5 may overwrite their outputs now
-            self._ev_packed.record(stream)
-            if side:
-                if self._ev_psd_read[self._pidx] is None:
-                    self._ev_psd_read[self._pidx] = torch.cuda.Event()
-                self._ev_psd_read[self._pidx].record(stream)
+        self.end_pack(stream)
         return self.result
 
     def exchange(self, dst: int = 0) -> Optional[StepResults]:
@@ -574,9 +510,8 @@ class AntennaStream:
             if self._done[k] is not None:
                 self._done[k].record(self._side if self._pack_on_side else self._main)
         else:
-            if self.overlap:
-                self._side.wait_event(self._ev_packed)
-            with self._on_side():
+            self.wait_packed(self._side)
+            with self.on_side():
                 if self.comm is not None:
                     rows = self._gathered[k]
                     self.comm.gather(vec, vec.numel() * vec.element_size(), rows if self.is_root else None, 0)
@@ -588,14 +523,7 @@ class AntennaStream:
             return None
         return StepResults(rows, self._done[k], self.n_ant)
 
-    def step(self) -> Optional[StepResults]:
-        """One pass of the hot path over this rank's capture + the exchange."""
-        self.scan()
-        self.tdoa()
-        return self.exchange(0)
-
     def close(self):
         if self.comm is not None and hasattr(self.comm, "close"):
             self.comm.close()
-        if self.overlap and self._own_side and self.dev_side is not self.dev:
-            self.dev_side.close()
+        super().close()

@@ -41,8 +41,9 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _ffi
-from .sharded import (HEADER, LAG_INVALID, PAIR_FIELDS, StepResults, all_pairs, allgather_rows, gather_rows,
-                      result_len, slot_bytes)
+from .sharded import (HEADER, PAIR_FIELDS, StepResults, all_pairs, allgather_rows, gather_rows, result_len,
+                      slot_bytes)
+from .streams import StepStreams, pair_outputs, scan_workspace, side_context
 
 TILE = 65536
 
@@ -183,7 +184,7 @@ def emulated_rank(dev, capture_bytes: Sequence[int], make_buffer, make_noise, wo
               for r in range(world) if r != rank]
     for st in [me] + others:                              # pass 1: what needs no other rank
         st.scan()
-        with st._on_side():
+        with st.on_side():
             st.cut_slots()
     torch.cuda.synchronize()
     for st in others:
@@ -233,8 +234,8 @@ class PartStream:
         self.tiles = torch.zeros(2 * max(self.n_tiles, 1), dtype=torch.float64, device=d)   # (sum, first) records
         self.amp = torch.zeros(4, dtype=torch.int64, device=d)                                 # gj_amp_part
         self.onset = torch.zeros(4, dtype=torch.int64, device=d)                               # gj_onset
-        # two PSD buffers, written alternately: a step's packing (which reads one) may run on the second stream while the
-        # main stream has gone on to the next step's K2 + finalize (which writes the other)
+        # two PSD buffers, written alternately (gpsjam.streams.PsdPingPong): a step's packing (which reads one) may run on
+        # the second stream while the main stream has gone on to the next step's K2 + finalize (which writes the other)
         self.psd2 = [torch.empty((max(self.rows, 1), nperseg), dtype=torch.float32, device=d) for _ in range(2)]
         self.psd = self.psd2[0]
 
@@ -262,8 +263,9 @@ class PartStream:
         self.dev_side.part_slot_dev(self.view, self.onset, self.slice_samples, out)
 
 
-class SplitStreams:
-    """This rank's share of ``capture_bytes`` (one entry per antenna) cut by ``plan_parts``.
+class SplitStreams(StepStreams):
+    """This rank's share of ``capture_bytes`` (one entry per antenna) cut by ``plan_parts``.  Its main and side streams
+    and their events are ``gpsjam.streams.StepStreams``; rank 0 adds a third stream for the gather and combine.
 
     ``make_buffer(part, b0, b1)`` returns the uint8 device tensor holding capture bytes [b0, b1) of the part's
     antenna; ``make_noise(antenna, nbytes)`` the capture's first ``nbytes`` bytes (asked for every part that does
@@ -274,7 +276,7 @@ class SplitStreams:
                  slice_samples: int = 1 << 19, noise_samples: int = 200000, window: int = 1000, factor: float = 50.0,
                  rssi_threshold: float = 0.0, overlap: Optional[bool] = None, device=None, exchange_always: bool = False,
                  emulate: bool = False, pack_on_side: bool = True, group=None):
-        self.dev, self.rank, self.world = dev, rank, world_size
+        self.rank, self.world = rank, world_size
         self.group = group                 # torch.distributed group of the exchange (None: the default group)
         # one rank of a world_size-rank plan alone on its GPU: no collective, local copies into the world-size buffers
         self.emulate = bool(emulate)
@@ -291,43 +293,23 @@ class SplitStreams:
         d = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.device = d
         self.is_root = rank == 0
-        self.overlap = bool(d.type == "cuda" if overlap is None else overlap)
-        self.dev_side = dev
-        self.streams_overlap = None        # one stream: nothing to overlap
-        self._pack_on_side = bool(pack_on_side)
-        self._pidx = 0
-        self._main = torch.cuda.current_stream(d) if d.type == "cuda" else None
-        if self._main is not None:
-            dev.set_stream(self._main.cuda_stream)
-        if self.overlap:
-            from .streams import stream_beside_checked
-            self.dev_side = type(dev)(dev.index)
-            # on a hardware queue of its own (gpsjam/streams.py); streams_overlap False: none found, chains serialised
-            self._side, self.streams_overlap = stream_beside_checked([(dev, self._main)], device=d)
-            self.dev_side.set_stream(self._side.cuda_stream)
-            self._ev_free, self._ev_side, self._ev_packed = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
-            self._ev_free.record(self._main)
-            # Packing on the SECOND stream (behind K5, where its inputs come from): the main stream then carries nothing but
-            # K2 + finalize, step after step, and never waits for the side chain -- at the per-rank load of an eight-way
-            # split the wait, the packing launch and the two cross-stream joins were 45 us of a 0.58-ms step between two K2
-            # launches (profiles/NOTES_r05.md).  Needs the two PSD buffers of PartStream.
-            self._ev_psd = [torch.cuda.Event(), torch.cuda.Event()]         # main: finalize has written psd2[i]
-            self._ev_psd_read = [None, None]                                # side: the packing has read psd2[i]
-        else:
-            self._side = self._main
+        # Packing on the SECOND stream (behind K5, where its inputs come from): the main stream then carries nothing but
+        # K2 + finalize, step after step, and never waits for the side chain -- at the per-rank load of an eight-way split
+        # the wait, the packing launch and the two cross-stream joins were 45 us of a 0.58-ms step between two K2 launches
+        # (profiles/NOTES_r05.md).  Needs the two PSD buffers of PartStream.
+        super().__init__(dev, torch.cuda.current_stream(d) if d.type == "cuda" else None,
+                         d.type == "cuda" if overlap is None else overlap, device=d, pack_on_side=pack_on_side)
         # Rank 0's gather + combine get a THIRD stream (and a context bound to it): on the second stream they would sit
         # between step k's K5 and step k + 1's scan, and under K2 -- where every small launch waits tens of microseconds
         # for a slot -- that serialisation left the next scan starting when K2 was two thirds through
         # (profiles/r04_split_emulated8_timeline.txt).  The combine reads only the packed vectors of its own step.
         self.dev_comb, self._comb = self.dev_side, self._side
         if self.overlap and self.is_root:
-            self.dev_comb = type(dev)(dev.index)
             # The runtime deals streams over a few hardware queues and two streams on one queue run one after the other: a
-            # third stream once landed on the MAIN stream's queue and K2 queued behind the combine.  stream_beside tests
-            # candidates until one runs beside both other streams; more queues (GPU_MAX_HW_QUEUES=8) give it room.
-            self._comb, ok = stream_beside_checked([(dev, self._main), (self.dev_side, self._side)], device=d)
+            # third stream once landed on the MAIN stream's queue and K2 queued behind the combine.  It is tested to run
+            # beside both other streams; more queues (GPU_MAX_HW_QUEUES=8) give the search room.
+            self.dev_comb, self._comb, ok = side_context(dev, [(dev, self._main), (self.dev_side, self._side)], d)
             self.streams_overlap = self.streams_overlap and ok
-            self.dev_comb.set_stream(self._comb.cuda_stream)
         kw = dict(chunk_bytes=chunk_bytes, chunk_samples=chunk_samples, nperseg=nperseg, fs=fs, slice_samples=slice_samples,
                   noise_samples=noise_samples, window=window, factor=factor, rssi_threshold=rssi_threshold)
         self.streams: List[PartStream] = []
@@ -364,11 +346,7 @@ class SplitStreams:
             offsets.append(len(members))
         self.d_members = torch.tensor(members or [0], dtype=torch.int32, device=d)
         self.d_offsets = torch.tensor(offsets, dtype=torch.int32, device=d)
-        npairs = max(len(self.pairs), 1)
-        self.d_pairs = torch.tensor([x for p in self.pairs for x in p] or [0, 0], dtype=torch.int32, device=d)
-        self.lags = torch.full((npairs,), LAG_INVALID, dtype=torch.int32, device=d)
-        self.peaks = torch.zeros(npairs, dtype=torch.float32, device=d)
-        self.margins = torch.zeros(npairs, dtype=torch.float32, device=d)
+        self.d_pairs, self.lags, self.peaks, self.margins = pair_outputs(self.pairs, d)
         # vectors: this rank's parts (two sets, used alternately), everybody's on the root, one per antenna on the root
         self._vecs = [torch.zeros((self.pmax, self.part_len), dtype=torch.float64, device=d) for _ in range(2)]
         self._gathered = ([torch.zeros((world_size, self.pmax * self.part_len), dtype=torch.float64, device=d) for _ in range(2)]
@@ -391,52 +369,30 @@ class SplitStreams:
         self._idx = 0
         self.last_psd = [None] * self.n_ant     # rank 0: each capture's waterfall rows as rebuilt by the last combine
         # workspaces
-        ws_main = max([dev.part_welch_workspace(s.view, chunk_samples, nperseg) for s in self.streams] + [1 << 20])
         ants = len({a for p in self.pairs for a in p}) or 1
-        ws_side = max(dev.xcorr_workspace(ants, slice_samples, npairs),
-                      max([(s.buf.numel()) // 48 + (1 << 20) for s in self.streams] + [1 << 20]))
-        if self.overlap:
-            dev.reserve(ws_main)
-            self.dev_side.reserve(ws_side)
-        else:
-            dev.reserve(max(ws_main, ws_side))
+        self.reserve(max([dev.part_welch_workspace(s.view, chunk_samples, nperseg) for s in self.streams] + [1 << 20]),
+                     max(dev.xcorr_workspace(ants, slice_samples, len(self.lags)),
+                         scan_workspace(max((s.buf.numel() for s in self.streams), default=0))))
 
     @staticmethod
     def _invalidate(slots: torch.Tensor):
         """Slot headers -> (flag -1, start -1): an unused slot must never be picked."""
         slots.view(torch.int64)[:, :2] = -1
 
-    def _on_side(self):
-        return torch.cuda.stream(self._side) if self.overlap else contextlib.nullcontext()
-
-    def _on_comb(self):
-        return torch.cuda.stream(self._comb) if self.overlap else contextlib.nullcontext()
-
     # ---------------------------------------------------------------- the step
     def stream_scan(self):
         """K1 + K3 + K4 of every part of this rank, one fused pass each (side stream)."""
-        if self.overlap:
-            self._side.wait_event(self._ev_free)
+        self.begin_side()
         for j, s in enumerate(self.streams):
             s.scan(slot=self.my_slots[j])
-        if self.overlap:
-            self._ev_side.record(self._side)
+        self.end_side()
 
     def welch(self):
         """K2 of every part of this rank (main stream)."""
-        side_pack = self.overlap and self._pack_on_side
-        if side_pack:
-            self._pidx ^= 1
-            if self._ev_psd_read[self._pidx] is not None:           # the packing of two steps ago has read this buffer
-                self._main.wait_event(self._ev_psd_read[self._pidx])
+        which = self._psd_turn.before_k2()
         for s in self.streams:
-            s.welch(self._pidx)
-        if side_pack:
-            self._ev_psd[self._pidx].record(self._main)
-
-    def scan(self):
-        self.stream_scan()
-        self.welch()
+            s.welch(which)
+        self._psd_turn.after_k2()
 
     def cut_slots(self):
         """Slots of this rank's parts (current stream)."""
@@ -452,7 +408,7 @@ class SplitStreams:
 
     def tdoa(self):
         """Slots of this rank's parts -> ONE all-gather -> one slot per antenna -> this rank's pairs."""
-        with self._on_side():
+        with self.on_side():
             self.cut_slots()
             if self.emulate:
                 # alone on the GPU: this rank's rows of the world-size buffer are filled by a copy (the other ranks'
@@ -469,17 +425,10 @@ class SplitStreams:
             else:
                 slots = self.my_slots
             self.solve(slots)
-            if self.overlap:
-                self._ev_side.record(self._side)
+            self.end_side()
 
     def pack(self) -> torch.Tensor:
-        side_pack = self.overlap and self._pack_on_side
-        stream = self._side if side_pack else self._main
-        dev = self.dev_side if side_pack else self.dev
-        if side_pack:
-            stream.wait_event(self._ev_psd[self._pidx])             # this step's PSD rows (main stream) are written
-        elif self.overlap:
-            self._main.wait_event(self._ev_side)
+        stream, dev = self.begin_pack()
         self._idx ^= 1
         vec = self._vecs[self._idx]
         if self.overlap and self._ev_vec_free[self._idx] is not None:
@@ -494,13 +443,7 @@ class SplitStreams:
                               s.psd.data_ptr(), self.d_pairs.data_ptr(), self.lags.data_ptr(), self.peaks.data_ptr(),
                               self.margins.data_ptr())
             dev.pack_part_dev(a, vec[j])
-        if self.overlap:
-            self._ev_free.record(stream)
-            self._ev_packed.record(stream)
-            if side_pack:
-                if self._ev_psd_read[self._pidx] is None:
-                    self._ev_psd_read[self._pidx] = torch.cuda.Event()
-                self._ev_psd_read[self._pidx].record(stream)
+        self.end_pack(stream)
         return vec
 
     def exchange(self, dst: int = 0) -> Optional[StepResults]:
@@ -512,9 +455,8 @@ class SplitStreams:
         vec = self.pack()
         k = self._idx
         final = None
-        if self.overlap:
-            self._comb.wait_event(self._ev_packed)
-        with self._on_comb():
+        self.wait_packed(self._comb)
+        with torch.cuda.stream(self._comb) if self.overlap else contextlib.nullcontext():
             if self.emulate:
                 src = vec.view(-1)
                 if self._always:
@@ -537,11 +479,6 @@ class SplitStreams:
         if not self.is_root:
             return None
         return StepResults(final, self._done[k], self.n_ant)
-
-    def step(self) -> Optional[StepResults]:
-        self.scan()
-        self.tdoa()
-        return self.exchange(0)
 
     # ---------------------------------------------------------------- rank 0: parts -> captures
     def _build_combine(self, k: int):
@@ -635,5 +572,4 @@ class SplitStreams:
                 self._plans[k] = None
         if self.dev_comb is not self.dev_side and self.dev_comb is not self.dev:
             self.dev_comb.close()
-        if self.overlap and self.dev_side is not self.dev:
-            self.dev_side.close()
+        super().close()
