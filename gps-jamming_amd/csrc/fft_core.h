@@ -403,45 +403,6 @@ GJ_HD void dft16_fma_tw(c2 (&a)[16], const c2* tw, const InnerTw& k) {
     dft16_layer2(a, k);
 }
 
-// Radix-16 butterfly with its input twiddles W^(t k), t = n1 + 4 n2, applied in two steps:
-// W^(4 n2 k) before the first radix-4 stage and W^(n1 k) after it (constant over the sum on
-// n2).  Six twiddle values (12 VGPRs) instead of fifteen (30) per pass for nine more complex
-// multiplies: the registers buy a third resident workgroup per CU.
-// tw6 = { W^(4k), W^(8k), W^(12k), W^(k), W^(2k), W^(3k) }.
-GJ_HD void dft16_twiddled(c2 (&a)[16], const c2* tw6, const InnerTw& k) {
-#pragma unroll
-    for (int n2 = 1; n2 < 4; ++n2)
-#pragma unroll
-        for (int n1 = 0; n1 < 4; ++n1) a[n1 + 4 * n2] = cmul(a[n1 + 4 * n2], tw6[n2 - 1]);
-#pragma unroll
-    for (int n1 = 0; n1 < 4; ++n1) dft4(a[n1], a[n1 + 4], a[n1 + 8], a[n1 + 12]);   // A[n1][k2] in a[n1 + 4 k2]
-#pragma unroll
-    for (int n1 = 1; n1 < 4; ++n1)
-#pragma unroll
-        for (int k2 = 0; k2 < 4; ++k2) a[n1 + 4 * k2] = cmul(a[n1 + 4 * k2], tw6[2 + n1]);
-    a[5] = cmul_k(a[5], k.w16_1);
-    a[9] = cmul_k(a[9], k.w16_2);
-    a[13] = cmul_k(a[13], k.w16_3);
-    a[6] = cmul_k(a[6], k.w16_2);
-    a[10] = mul_mj(a[10]);
-    a[14] = cmul_k(a[14], k.w16_6);
-    a[7] = cmul_k(a[7], k.w16_3);
-    a[11] = cmul_k(a[11], k.w16_6);
-    a[15] = cmul_k(a[15], k.w16_9);
-    c2 r[16];
-#pragma unroll
-    for (int k2 = 0; k2 < 4; ++k2) {
-        c2 y0 = a[4 * k2], y1 = a[4 * k2 + 1], y2 = a[4 * k2 + 2], y3 = a[4 * k2 + 3];
-        dft4(y0, y1, y2, y3);
-        r[k2] = y0;
-        r[4 + k2] = y1;
-        r[8 + k2] = y2;
-        r[12 + k2] = y3;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) a[i] = r[i];
-}
-
 // LDS element index (8-byte elements) of logical point i of a transform whose region
 // starts at `base`.
 // Additive padding (one spare slot per 16) rather than an XOR swizzle: every address a thread
@@ -458,17 +419,12 @@ constexpr int lds_span(int n) { return n + n / 16; }   // slots one N-point tran
 // leg t sits in v[u + t*(16/R)] and belongs at index out_index<N,PASS>(jl, u, t) of the
 // next pass' input (or IS X[jl + (N/16)(u + t*(16/R))] after the last pass).
 // tw[u*(R-1) + t-1] = W_(Ns R)^(t * ((jl + (N/16) u) mod Ns)), unused when PASS == 0.
-// TWO_STEP (radix-16 passes after the first only): tw holds the six values of dft16_twiddled.
 // FMA_FORM (radix-16 passes): the FMA-form butterflies above (same twiddle registers as the
 // default form).
-template <int N, int PASS, bool TWO_STEP = false, bool FMA_FORM = false>
+template <int N, int PASS, bool FMA_FORM = false>
 GJ_HD void fft_pass(c2 (&v)[16], const c2* tw, const InnerTw& k) {
     constexpr int R = fft_radix(N, PASS);
     constexpr int G = 16 / R;   // butterflies per thread
-    if constexpr (TWO_STEP && PASS > 0 && R == 16) {
-        dft16_twiddled(v, tw, k);
-        return;
-    }
     if constexpr (FMA_FORM && R == 16) {
         if constexpr (PASS > 0) dft16_fma_tw(v, tw, k);
         else dft16_fma(v, k);
@@ -505,17 +461,6 @@ GJ_HD int twiddle_index(int jl, int u, int t) {
     constexpr int NS = fft_ns(N, PASS);
     const int k = (jl + (N / 16) * u) & (NS - 1);
     return (t * k * (kTwiddleTable / (NS * R))) & (kTwiddleTable - 1);
-}
-
-// the six twiddles of dft16_twiddled for thread jl (radix-16 pass, one butterfly per thread)
-template <int N, int PASS>
-GJ_HD void load_twiddles6(c2* tw6, const cf* table, int jl) {
-    constexpr int NS = fft_ns(N, PASS);
-    const int k = jl & (NS - 1);
-    constexpr int step = kTwiddleTable / (NS * 16);
-    const int e[6] = {4, 8, 12, 1, 2, 3};
-#pragma unroll
-    for (int i = 0; i < 6; ++i) tw6[i] = to_c2(table[(e[i] * k * step) & (kTwiddleTable - 1)]);
 }
 
 template <int N, int PASS>

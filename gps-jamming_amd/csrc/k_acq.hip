@@ -31,7 +31,7 @@ __device__ __forceinline__ void acq_passes(c2 (&v)[16], cf* lds, int base, int j
     constexpr int NP = fft_npass(N);
     c2 tw[15];
     if constexpr (PASS > 0) load_twiddles<N, PASS>(tw, twtab, jl);
-    fft_pass<N, PASS, false, true>(v, tw, inner_twiddles());
+    fft_pass<N, PASS, true>(v, tw, inner_twiddles());
     if constexpr (PASS + 1 < NP) {
         lds_scatter<N, PASS>(v, lds, base, jl);
         __syncthreads();
@@ -45,7 +45,7 @@ __device__ __forceinline__ void acq_passes(c2 (&v)[16], cf* lds, int base, int j
 template <int N, int PASS>
 __device__ __forceinline__ void acq_passes_tw(c2 (&v)[16], cf* lds, int base, int jl, const c2 (&tw)[3][15]) {
     constexpr int NP = fft_npass(N);
-    fft_pass<N, PASS, false, true>(v, tw[PASS], inner_twiddles());
+    fft_pass<N, PASS, true>(v, tw[PASS], inner_twiddles());
     if constexpr (PASS + 1 < NP) {
         lds_scatter<N, PASS>(v, lds, base, jl);
         __syncthreads();
@@ -329,16 +329,16 @@ template <int N>
 __device__ __forceinline__ void acq_transform(c2 (&v)[16], cf* lds, int tid, int base, int jl, const c2 (&tw)[3][15]) {
     if constexpr (N == 4096) {
         const InnerTw k = inner_twiddles();
-        fft_pass<4096, 0, false, true>(v, tw[0], k);
+        fft_pass<4096, 0, true>(v, tw[0], k);
         x4096_scatter<0>(v, lds, tid);
         __syncthreads();
         x4096_gather<0>(v, lds, tid);
         __syncthreads();
-        fft_pass<4096, 1, false, true>(v, tw[1], k);
+        fft_pass<4096, 1, true>(v, tw[1], k);
         x4096_scatter<1>(v, lds, tid);
         __syncthreads();
         x4096_gather<1>(v, lds, tid);
-        fft_pass<4096, 2, false, true>(v, tw[2], k);
+        fft_pass<4096, 2, true>(v, tw[2], k);
     } else {
         acq_passes_tw<N, 0>(v, lds, base, jl, tw);
     }
@@ -435,10 +435,6 @@ __global__ __launch_bounds__(kBlockThreads, N == 2048 ? 2 : 3) void acq_inv_all_
             acc[s] += (double)(v[s].x * v[s].x + v[s].y * v[s].y);   // 1/m^2 rides on the code spectrum (acq_code_body)
             mine.v = __builtin_fmax(mine.v, acc[s]);
         }
-#ifdef GJ_ACQ_ABLATE_CHECK   // timing only (tools/ab_build.sh): no peak bookkeeping at all
-        if (step + 1 == P.intg && live && jl == 0) rows[((size_t)p * P.intg + step) * P.n_freq + f].maxv = mine.v;
-        continue;
-#endif
         // The row's maximum (value only) AND what the transform's first thread read of the running maximum when the step
         // began, both known to every thread of the transform after ONE exchange.  The early read may be stale, but gmax
         // only grows: a row below even the stale value cannot be the step's winner and goes straight on -- no atomic,

@@ -17,70 +17,11 @@
 // fixed order (deterministic), applies fftshift and writes the optional dB row.
 #include "gj_common.h"
 
-// ---- build-time tuning knobs (defaults = the shipped configuration; tools/ab_build.sh flips them)
-#ifndef GJ_LB
-#define GJ_LB 2          // min waves per SIMD asked of the register allocator
-#endif
-#ifndef GJ_W_TWOSTEP
-#define GJ_W_TWOSTEP 0   // 1: six twiddles per radix-16 pass (dft16_twiddled) instead of fifteen
-#endif
-#ifndef GJ_W_PREFETCH
-#define GJ_W_PREFETCH 1  // 1: next step's raw samples are loaded while the current one is transformed
-#endif
-#ifndef GJ_W_FMA
-#define GJ_W_FMA 1       // 1: FMA-form radix-4 butterflies (fft_core.h dft16_fma*): ~9 % fewer packed ops
-#endif
-#ifndef GJ_W_PKACC
-#define GJ_W_PKACC 1     // 1: |X|^2 accumulated as (re^2, im^2) pairs with one v_pk_fma_f32 per bin
-#endif
-#ifndef GJ_W_DBUF
-#define GJ_W_DBUF 1      // 1: two LDS exchange buffers, one barrier per exchange; 0: one buffer, two barriers
-#endif
-#ifndef GJ_W_OCC3_MASK
-// Bit k set: transform size 2^k runs in the "three workgroups per CU" shape (<= 168 VGPRs, one
-// LDS buffer with two barriers per exchange, window kept as 16 floats, scalar |X|^2 accumulators:
-// +32 VALU instructions per step, but a third wave per SIMD to fill the issue slots -- a wave
-// issues at most one instruction every ~5 cycles, whatever its kind).  Measured on MI355X, 1 GiB,
-// same box, two-workgroup shape -> three-workgroup shape:
-//   N = 4096  1.328 -> 1.257 ms   2048  1.348 -> 1.320   1024  1.284 -> 1.211   512  1.242 -> 1.142
-//   N = 256   1.001 -> 0.960      128   1.055 -> 1.042   64    1.278 -> 1.207   32   2.160 -> 2.119
-//   N = 16    1.669 -> 1.707 (stays in the two-workgroup shape)
-// (Figures of rounds 2-5.  Below 4096 they INCLUDED a finalize that added B = 4096 / N partial rows per workgroup -- at 16
-// points 256 of them, a launch longer than the transform.  With one partial row per workgroup (round 6) K2 + finalize
-// per GiB is 0.43 / 0.63 / 0.68 / 0.73 / 0.76 / 0.94 / 0.99 / 1.15 / 1.09 ms at 16 / 32 / ... / 4096 points
-// (profiles/r06_k2_all_sizes.txt); the two-against-three-workgroup comparison itself has not been repeated.)
-// (512..2048 fit 168 VGPRs only since the exchange addresses are written as base + constant,
-// fft_core.h lds_scatter/lds_gather: 236-246 -> 192-206 VGPRs in the two-workgroup shape.)
-#define GJ_W_OCC3_MASK 0x1FE0u
-#endif
-#ifndef GJ_W_HALFSUM
-#define GJ_W_HALFSUM 1   // 1: (one transform per workgroup) half-segment sums carried from step to step
-#endif
-#ifndef GJ_W_CARRY
-// 1: (one transform per workgroup, i.e. N = 4096) the unpacked second half of a segment is CARRIED in registers as
-// the first half of the next one (50 % overlap), and the periodic Hann window's symmetry w[n + N/2] = 1 - w[n]
-// halves the window registers that pays for it: per step 16 conversions, 8 offset FMAs and 8 loads fewer
-// (72 -> 48 front-end instructions per thread), same VGPR count.
-#define GJ_W_CARRY 1
-#endif
-#ifndef GJ_W_CARRY_MASK
-#define GJ_W_CARRY_MASK 0x1400u   // bit k set: transform size 2^k carries.  1024 and 4096; 2048 spills with it (+2 %, measured)
-#endif
 #ifndef GJ_W_WAVEFENCE
 // 1: for N <= 1024 the LDS exchange is ordered by a wavefront fence (a transform lies inside one wave); 0: by the
 // workgroup barrier, as for the larger sizes.  The second form is built as libgpsjam_hip_barrier.so (Makefile) and
 // tests/test_round5_gpu.py compares the two byte for byte: the fence path must never depend on a barrier it removed.
 #define GJ_W_WAVEFENCE 1
-#endif
-#ifndef GJ_W_WIDELOAD
-// 1: transforms of 16 and 32 points fetch their segment with 16-byte loads (2 or 4 of them) and pick the thread's sixteen
-// samples out of the registers, instead of sixteen 2-byte loads at a 2 TF-byte stride.  Measured per GiB, interleaved on
-// one box (profiles/r06_k2_small_sizes.txt): N = 32 0.95 -> 0.64 ms, N = 16 0.449 -> 0.441; the same for 64 points needs a
-// run-time choice between register pairs, spills, and is three times SLOWER (0.70 -> 2.29 ms): 64 keeps the narrow loads.
-#define GJ_W_WIDELOAD 1
-#endif
-#ifndef GJ_W_XPOSE
-#define GJ_W_XPOSE 1     // 1: N = 4096 uses the bank-conflict-free exchange schedule (fft_core.h X4096)
 #endif
 
 namespace gj {
@@ -103,15 +44,42 @@ __device__ __forceinline__ c2 one_minus_hi(c2 a, c2 p) {
     return r;
 }
 
-constexpr int welch_log2(int n) { return n <= 1 ? 0 : 1 + welch_log2(n / 2); }
-constexpr bool welch_occ3(int n) { return ((GJ_W_OCC3_MASK >> welch_log2(n)) & 1u) != 0; }
+// N = 32 .. 4096 run in the "three workgroups per CU" shape (<= 168 VGPRs, one LDS buffer with two barriers per
+// exchange, window kept as 16 floats, scalar |X|^2 accumulators: +32 VALU instructions per step, but a third wave per
+// SIMD to fill the issue slots -- a wave issues at most one instruction every ~5 cycles, whatever its kind).  Measured
+// on MI355X, 1 GiB, same box, two-workgroup shape -> three-workgroup shape:
+//   N = 4096  1.328 -> 1.257 ms   2048  1.348 -> 1.320   1024  1.284 -> 1.211   512  1.242 -> 1.142
+//   N = 256   1.001 -> 0.960      128   1.055 -> 1.042   64    1.278 -> 1.207   32   2.160 -> 2.119
+//   N = 16    1.669 -> 1.707 (stays in the two-workgroup shape)
+// (Figures of rounds 2-5.  Below 4096 they INCLUDED a finalize that added B = 4096 / N partial rows per workgroup -- at 16
+// points 256 of them, a launch longer than the transform.  With one partial row per workgroup (round 6) K2 + finalize
+// per GiB is 0.43 / 0.63 / 0.68 / 0.73 / 0.76 / 0.94 / 0.99 / 1.15 / 1.09 ms at 16 / 32 / ... / 4096 points
+// (profiles/r06_k2_all_sizes.txt); the two-against-three-workgroup comparison itself has not been repeated.)
+// (512..2048 fit 168 VGPRs only since the exchange addresses are written as base + constant,
+// fft_core.h lds_scatter/lds_gather: 236-246 -> 192-206 VGPRs in the two-workgroup shape.)
+constexpr bool welch_occ3(int n) { return n >= 32; }
 template <int N>
 struct WelchCfg {
     static constexpr bool occ3 = welch_occ3(N);
-    static constexpr int min_waves = occ3 ? 3 : GJ_LB;          // per SIMD, asked of the register allocator
-    static constexpr bool pkacc = (GJ_W_PKACC != 0) && !occ3;   // |X|^2 as (re^2, im^2) pairs
-    static constexpr bool dbuf = (GJ_W_DBUF != 0) && !occ3;     // two LDS exchange buffers
-    static constexpr bool win16 = occ3;                         // window as 16 floats instead of 16 pairs
+    static constexpr int min_waves = occ3 ? 3 : 2;   // per SIMD, asked of the register allocator
+    static constexpr bool pkacc = !occ3;             // |X|^2 as (re^2, im^2) pairs with one v_pk_fma_f32 per bin
+    static constexpr bool dbuf = !occ3;              // two LDS exchange buffers, one barrier per exchange
+    static constexpr bool win16 = occ3;              // window as 16 floats instead of 16 pairs
+    // transform groups of one wave or more walk runs of consecutive segments and carry half-segment sums (see RUNS)
+    static constexpr bool runs = N >= 1024;
+    // The unpacked second half of a segment is CARRIED in registers as the first half of the next one (50 % overlap),
+    // and the periodic Hann window's symmetry w[n + N/2] = 1 - w[n] halves the window registers that pays for it: per
+    // step 16 conversions, 8 offset FMAs and 8 loads fewer (72 -> 48 front-end instructions per thread), same VGPR
+    // count.  1024 and 4096 only: 2048 spills with it (+2 %, measured).
+    static constexpr bool carry = N == 1024 || N == 4096;
+    // the bank-conflict-free exchange schedule of fft_core.h (X4096)
+    static constexpr bool xpose = N == 4096;
+    // Transforms of 16 and 32 points fetch their segment with 16-byte loads (2 or 4 of them) and pick the thread's
+    // sixteen samples out of the registers, instead of sixteen 2-byte loads at a 2 TF-byte stride.  Measured per GiB,
+    // interleaved on one box (profiles/r06_k2_small_sizes.txt): N = 32 0.95 -> 0.64 ms, N = 16 0.449 -> 0.441; the same
+    // for 64 points needs a run-time choice between register pairs, spills, and is three times SLOWER (0.70 -> 2.29 ms):
+    // 64 keeps the narrow loads.
+    static constexpr bool wide_load = N <= 32;
 };
 
 struct WelchGeom {
@@ -155,7 +123,7 @@ template <int N, int PASS, typename Mid>
 __device__ __forceinline__ void welch_passes(c2 (&v)[16], cf* lds0, cf* lds1, unsigned it, int base, int jl,
                                              const c2 (&tw)[3][15], const InnerTw& ktw, Mid&& after_scatter0) {
     constexpr int NP = fft_npass(N);
-    fft_pass<N, PASS, GJ_W_TWOSTEP != 0, GJ_W_FMA != 0>(v, tw[PASS], ktw);
+    fft_pass<N, PASS, true>(v, tw[PASS], ktw);
     if constexpr (PASS + 1 < NP) {
         // exchanges per segment: NP-1.  Even count -> parity of PASS; odd count -> parity of (it + PASS)
         const bool second = ((NP - 1) % 2 == 0) ? (PASS & 1) : ((it + PASS) & 1);
@@ -170,25 +138,25 @@ __device__ __forceinline__ void welch_passes(c2 (&v)[16], cf* lds0, cf* lds1, un
 }
 
 // N = 4096 with the conflict-free exchange schedule of fft_core.h (X4096): pass 0 in role
-// jl0 = tid, passes 1 and 2 in role jl1; buffer 0 carries exchange 0, buffer 1 exchange 1.
+// jl0 = tid, passes 1 and 2 in role jl1; one LDS buffer, two barriers per exchange.
 // `after_scatter0()` runs where the fewest registers are live (the points are in LDS, the next pass has not
 // gathered them yet): the caller issues its prefetch loads there.
 template <typename Mid>
-__device__ __forceinline__ void welch_passes_x4096(c2 (&v)[16], cf* lds0, cf* lds1, int tid, const c2 (&tw)[3][15],
+__device__ __forceinline__ void welch_passes_x4096(c2 (&v)[16], cf* lds, int tid, const c2 (&tw)[3][15],
                                                    const InnerTw& ktw, Mid&& after_scatter0) {
-    fft_pass<4096, 0, false, GJ_W_FMA != 0>(v, tw[0], ktw);
-    x4096_scatter<0>(v, lds0, tid);
+    static_assert(!WelchCfg<4096>::dbuf, "4096 points run in the one-buffer shape");
+    fft_pass<4096, 0, true>(v, tw[0], ktw);
+    x4096_scatter<0>(v, lds, tid);
     after_scatter0();
     __syncthreads();
-    x4096_gather<0>(v, lds0, tid);
-    if (!WelchCfg<4096>::dbuf) __syncthreads();
-    fft_pass<4096, 1, GJ_W_TWOSTEP != 0, GJ_W_FMA != 0>(v, tw[1], ktw);
-    cf* ldsx = WelchCfg<4096>::dbuf ? lds1 : lds0;
-    x4096_scatter<1>(v, ldsx, tid);
+    x4096_gather<0>(v, lds, tid);
     __syncthreads();
-    x4096_gather<1>(v, ldsx, tid);
-    if (!WelchCfg<4096>::dbuf) __syncthreads();
-    fft_pass<4096, 2, GJ_W_TWOSTEP != 0, GJ_W_FMA != 0>(v, tw[2], ktw);
+    fft_pass<4096, 1, true>(v, tw[1], ktw);
+    x4096_scatter<1>(v, lds, tid);
+    __syncthreads();
+    x4096_gather<1>(v, lds, tid);
+    __syncthreads();
+    fft_pass<4096, 2, true>(v, tw[2], ktw);
 }
 
 // Several captures of ONE size in one launch (gj_welch_batch_dev: the reference's deployment is three antenna files of one
@@ -207,18 +175,18 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
                                                               WelchBatch batch = WelchBatch()) {
     // wg_base: index of this launch's first workgroup in the whole capture's grid (0 unless the capture is
     // transformed piece by piece while it is still being uploaded, gj_ingest_*)
+    using Cfg = WelchCfg<N>;
     constexpr int TF = N / 16, B = kBlockPoints / N, NP = fft_npass(N);
     constexpr int WPF = (TF >= 64) ? TF / 64 : 1;   // waves per transform
-    constexpr bool XP = (N == 4096) && GJ_W_XPOSE;
+    constexpr bool XP = Cfg::xpose, CARRY = Cfg::carry;
     constexpr int SPAN = XP ? X4096::kSpan : lds_span(kBlockPoints);
     __shared__ cf lds0[SPAN];
-    using Cfg = WelchCfg<N>;
     // RUNS (transform groups of one wave or more, N >= 1024): group b of the workgroup walks a run of CONSECUTIVE
     // segments (b-th slice of the workgroup's segments) instead of taking every B-th one, so that every step's first
     // half segment is the previous step's second half for ALL these sizes, not only for N = 4096 (B = 1): the
     // half-segment sums (HS) and the unpacked half (CARRY) are then carried from step to step.  Smaller transforms keep
     // the interleaved order: their groups are fractions of a wave and consecutive groups read consecutive memory.
-    constexpr bool RUNS = (TF >= 64) && (GJ_W_HALFSUM != 0);
+    constexpr bool RUNS = Cfg::runs;
     constexpr bool HS = RUNS;
     __shared__ cf lds1[Cfg::dbuf ? SPAN : 1];
     // (sum I, sum Q) per wave; three slots when half-segment sums are carried over (see HS below)
@@ -253,18 +221,9 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
     for (int p = 0; p < 3; ++p)
 #pragma unroll
         for (int k = 0; k < 15; ++k) tw[p][k] = make_c2(1.f, 0.f);
-    if constexpr (NP > 1) {
-        if constexpr (GJ_W_TWOSTEP && fft_radix(N, 1) == 16) load_twiddles6<N, 1>(tw[1], twtab, jl);
-        else load_twiddles<N, 1>(tw[1], twtab, jl);
-    }
-    if constexpr (NP > 2) {
-        if constexpr (GJ_W_TWOSTEP && fft_radix(N, 2) == 16) load_twiddles6<N, 2>(tw[2], twtab, jl);
-        else load_twiddles<N, 2>(tw[2], twtab, jl);
-    }
+    if constexpr (NP > 1) load_twiddles<N, 1>(tw[1], twtab, jl);
+    if constexpr (NP > 2) load_twiddles<N, 2>(tw[2], twtab, jl);
 
-    // CARRY (every group walks consecutive segments, N >= 1024): see GJ_W_CARRY above
-    constexpr bool CARRY = HS && Cfg::win16 && (GJ_W_CARRY != 0) && (GJ_W_PREFETCH != 0) &&
-                           (((GJ_W_CARRY_MASK >> welch_log2(N)) & 1u) != 0);
     // window folded into the unpack: w (2u - 255) = u (2w) + (-255 w); (w[2i], w[2i+1]) share a
     // VGPR pair and op_sel picks the half, so 16 points cost 16 register pairs.
     // CARRY: w[n + N/2] = 1 - w[n] (periodic Hann), so the eight values of the first half do for both.
@@ -290,7 +249,7 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
     // one SGPR pair + one VGPR + immediates
     const uint8_t* chunk8 = iq + (size_t)c * g.chunk_samples * 2;
     auto load_step = [&](unsigned (&dst)[16], unsigned seg_idx) {
-        if constexpr (GJ_W_WIDELOAD != 0 && TF <= 2) {
+        if constexpr (Cfg::wide_load) {
             // the whole segment (2 N bytes) in 16-byte loads; sample jl0 + TF s is one half of dword (jl0 + TF s) / 2.
             // The segment is only 2-byte aligned in general: global memory takes unaligned vector loads.
             struct __attribute__((packed, aligned(2))) Vec16 { unsigned x, y, z, w; };
@@ -375,7 +334,6 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
                 v[8 + s] = (s & 1) ? one_minus_hi(u2, w2p[s >> 1]) : one_minus_lo(u2, w2p[s >> 1]);
             }
         } else {
-            if (!GJ_W_PREFETCH && it > 0) load_step(raw, active ? seg : seg_idle);
             if (HS && it == 0) {   // first step of the workgroup: the first half has no predecessor
                 c2 flo = make_c2(0.f, 0.f);
 #pragma unroll
@@ -397,7 +355,7 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
                     v[s] = (s & 1) ? fma_hi(f, w2p[s >> 1], wcp[s >> 1]) : fma_lo(f, w2p[s >> 1], wcp[s >> 1]);
                 if (!HS || s >= 8) fsum = cadd(fsum, f);
             }
-            if (GJ_W_PREFETCH) load_step(raw, seg_next);
+            load_step(raw, seg_next);
         }
         float si, sq;
         if constexpr (TF >= 64) {
@@ -416,7 +374,7 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
         auto prefetch_half = [&] {
             if constexpr (CARRY) load_half(rawh, seg_next, 8);
         };
-        if constexpr (XP) welch_passes_x4096(v, lds0, lds1, tid, tw, ktw, prefetch_half);
+        if constexpr (XP) welch_passes_x4096(v, lds0, tid, tw, ktw, prefetch_half);
         else welch_passes<N, 0>(v, lds0, lds1, it, b * lds_span(N), jl, tw, ktw, prefetch_half);
 
         // detrend in the frequency domain on bins 0, 1, N-1
@@ -653,19 +611,10 @@ int launch_welch_batch(gj_ctx* ctx, const uint8_t* const* d_iq, int n_captures, 
     if (job.rows == 0) return GJ_OK;
     WelchPlan pl;
     memcpy(&pl, job.plan, sizeof(pl));
-    {
-        // Measurement only (tools/k2_batch_sweep.py, profiles/r06_k2_batch_sweep.txt): force the workgroups per chunk of a
-        // batched launch.  Round 6 tried planning the split over ALL the batch's chunks (three 10-s captures: 25 per chunk
-        // = 750 workgroups of 40 steps instead of 76 per chunk = 2 280 of 13): K2 alone 4 % faster (122 against 127 us),
-        // the deployment step it is part of 11 % SLOWER (0.231 against 0.206 ms, interleaved on one box) -- few long
-        // workgroups keep the scan / tail / K5 kernels of the side chains waiting for a slot, many short ones let them in.
-        // The per-capture plan stays, and with it the byte-equality of a PSD across every arrangement.
-        static const long forced = [] { const char* e = getenv("GPSJAM_W_BATCH_SPLITS"); return e ? atol(e) : 0l; }();
-        if (forced > 0 && forced <= 256 && (size_t)forced * 2 * (size_t)pl.batch <= pl.g.nseg_full) {
-            pl.g.splits = (unsigned)forced;
-            job.ws_bytes = pl.rows * (size_t)forced * (size_t)nperseg * sizeof(float);
-        }
-    }
+    // Every capture keeps its own plan's workgroups per chunk, and with it the byte-equality of its PSD across every
+    // arrangement.  A split planned over ALL the batch's chunks made K2 alone 4 % faster but the deployment step it is
+    // part of 11 % slower (profiles/r06_k2_batch_sweep.txt): few long workgroups keep the scan / tail / K5 kernels of
+    // the side chains waiting for a slot, many short ones let them in.
     if ((unsigned long long)n_captures * pl.g.nchunks * pl.g.splits > 0x7fffffffull || (unsigned long long)n_captures * pl.g.nchunks > 65535ull)
         return fail(ctx, GJ_ERR_UNSUPPORTED, "too many chunks for one launch");
     WelchBatch batch;

@@ -14,46 +14,13 @@
 // Tie rule of numpy.argmax (first maximum in 'full' order m = lag + N-1) is kept.
 #include "gj_common.h"
 
-// ---- build-time experiment knobs (defaults = the shipped configuration; tools/ab_build.sh flips them) ----
-#ifndef GJ_XC_NT
-#define GJ_XC_NT 0        // 1: the spectra between the launches are stored / loaded non-temporally (each is used once): -2 % at 2^19-sample slices, +2.5 % at the reference's 50 000 (profiles/r06_k5_variants.txt): off
-#endif
-#ifndef GJ_XC_SWIZZLE
-#define GJ_XC_SWIZZLE 0   // 1: column tiles are dealt so that one XCD walks a contiguous range of columns: no effect (same file): off
-#endif
-
 namespace gj {
 
 constexpr int kRow = 4096;   // L2: contiguous row length
 
 // the spectra that travel between K5's launches (Y after the forward columns, D after the rows)
-__device__ __forceinline__ void xc_store(cf* p, c2 v) {
-#if GJ_XC_NT
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    __builtin_nontemporal_store(f2{v.x, v.y}, reinterpret_cast<f2*>(p));
-#else
-    *p = to_cf(v);
-#endif
-}
-__device__ __forceinline__ c2 xc_load(const cf* p) {
-#if GJ_XC_NT
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 t = __builtin_nontemporal_load(reinterpret_cast<const f2*>(p));
-    return make_c2(t.x, t.y);
-#else
-    return to_c2(*p);
-#endif
-}
-// column tile of workgroup x out of `tiles` (a multiple of 8 for every L >= 2^16): workgroups are dealt round-robin over
-// the eight XCDs, so with the swizzle XCD k walks tiles [k tiles/8, (k+1) tiles/8) in order
-__device__ __forceinline__ unsigned xc_tile(unsigned x, unsigned tiles) {
-#if GJ_XC_SWIZZLE
-    return (tiles & 7u) ? x : (x & 7u) * (tiles >> 3) + (x >> 3);
-#else
-    (void)tiles;
-    return x;
-#endif
-}
+__device__ __forceinline__ void xc_store(cf* p, c2 v) { *p = to_cf(v); }
+__device__ __forceinline__ c2 xc_load(const cf* p) { return to_c2(*p); }
 
 struct XcParams {
     int off2;   // unpack convention: 2 * offset (255)
@@ -149,7 +116,7 @@ __global__ __launch_bounds__(kBlockThreads) void xc_cols_kernel(XcParams P, cons
     const int tid = threadIdx.x;
     const int b = tid % B, jl = tid / B;
     const int t = blockIdx.y;   // antenna (MODE 0) or pair (MODE 1)
-    const unsigned tile = xc_tile(blockIdx.x, gridDim.x);
+    const unsigned tile = blockIdx.x, tiles = gridDim.x;   // column tile of this workgroup, out of `tiles`
     const int n2 = (int)tile * B + b;
     c2 v[16];
     if constexpr (MODE == 0) {
@@ -224,16 +191,16 @@ __global__ __launch_bounds__(kBlockThreads) void xc_cols_kernel(XcParams P, cons
         if (tid == 0) {
             XcCand r = red[0];
             for (int k = 1; k < kBlockThreads / 64; ++k) r = xc_merge(r, red[k]);
-            cand[(size_t)t * gridDim.x + blockIdx.x] = r;
+            cand[(size_t)t * tiles + tile] = r;
             const unsigned ticket = arrive_release(arrive + t);
-            const int last = ticket == gridDim.x - 1;
+            const int last = ticket == tiles - 1;
             if (last) last_arriver_acquire(arrive + t);
             last_s = last;
         }
         __syncthreads();
         if (!last_s) return;
         XcCand r{-1.f, 0x7fffffff, -1.f, 0};
-        for (unsigned k = tid; k < gridDim.x; k += kBlockThreads) r = xc_merge(r, cand[(size_t)t * gridDim.x + k]);
+        for (unsigned k = tid; k < tiles; k += kBlockThreads) r = xc_merge(r, cand[(size_t)t * tiles + k]);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
             XcCand o;

@@ -14,17 +14,15 @@ using namespace gj;
 
 static std::vector<cf> g_table;
 
-template <int N, int PASS, bool TWO = false, bool FMA = false>
+template <int N, int PASS, bool FMA = false>
 static void run_passes(std::vector<cf (*)[16]>& regs, std::vector<cf>& lds) {
     constexpr int TF = N / 16, NP = fft_npass(N);
     for (int j = 0; j < kBlockThreads; ++j) {
         const int b = j / TF, jl = j % TF;
         c2 tw[15];
         for (auto& t : tw) t = make_c2(0.f, 0.f);
-        constexpr bool two = TWO && PASS > 0 && fft_radix(N, PASS) == 16;
-        if constexpr (two) load_twiddles6<N, PASS>(tw, g_table.data(), jl);
-        else if constexpr (PASS > 0) load_twiddles<N, PASS>(tw, g_table.data(), jl);
-        fft_pass<N, PASS, TWO, FMA>(*regs[j], tw, inner_twiddles());
+        if constexpr (PASS > 0) load_twiddles<N, PASS>(tw, g_table.data(), jl);
+        fft_pass<N, PASS, FMA>(*regs[j], tw, inner_twiddles());
         if constexpr (PASS + 1 < NP) lds_scatter<N, PASS>(*regs[j], lds.data(), b * lds_span(N), jl);
     }
     if constexpr (PASS + 1 < NP) {
@@ -32,11 +30,11 @@ static void run_passes(std::vector<cf (*)[16]>& regs, std::vector<cf>& lds) {
             const int b = j / TF, jl = j % TF;
             lds_gather<N>(*regs[j], lds.data(), b * lds_span(N), jl);
         }
-        run_passes<N, PASS + 1, TWO, FMA>(regs, lds);
+        run_passes<N, PASS + 1, FMA>(regs, lds);
     }
 }
 
-template <int N, bool TWO = false, bool FMA = false>
+template <int N, bool FMA = false>
 static double check() {
     constexpr int TF = N / 16, B = kBlockPoints / N;
     std::vector<cf> in(kBlockPoints), lds(kBlockPoints + kBlockPoints / 16 + 64);
@@ -48,7 +46,7 @@ static double check() {
         const int b = j / TF, jl = j % TF;
         for (int s = 0; s < 16; ++s) (*regs[j])[s] = in[b * N + jl + TF * s];
     }
-    run_passes<N, 0, TWO, FMA>(regs, lds);
+    run_passes<N, 0, FMA>(regs, lds);
     double worst = 0.0;
     for (int b = 0; b < B; ++b) {
         double norm = 0.0;
@@ -96,7 +94,7 @@ static double check_x4096() {
     c2 none[15];
     for (int j = 0; j < 256; ++j) {
         for (int s = 0; s < 16; ++s) regs(j)[s] = in[j + 256 * s];
-        fft_pass<N, 0, false, FMA>(regs(j), none, k);
+        fft_pass<N, 0, FMA>(regs(j), none, k);
         // the scatter must put leg t at the layout slot of its logical index
         for (int t = 0; t < 16; ++t)
             if (286 * (j >> 4) + 17 * (j & 15) + X4096::c0(t) != X4096::slot0(out_index<N, 0>(j, 0, t))) return 2.0;
@@ -112,13 +110,13 @@ static double check_x4096() {
             c2 tw[15];
             if (pass == 1) {
                 load_twiddles<N, 1>(tw, g_table.data(), jl);
-                fft_pass<N, 1, false, FMA>(regs(j), tw, k);
+                fft_pass<N, 1, FMA>(regs(j), tw, k);
                 for (int t = 0; t < 16; ++t)
                     if (287 * (j & 15) + (j >> 4) + 18 * t != X4096::slot1(out_index<N, 1>(jl, 0, t))) return 3.0;
                 x4096_scatter<1>(regs(j), lds.data(), j);
             } else {
                 load_twiddles<N, 2>(tw, g_table.data(), jl);
-                fft_pass<N, 2, false, FMA>(regs(j), tw, k);
+                fft_pass<N, 2, FMA>(regs(j), tw, k);
             }
         }
     }
@@ -159,12 +157,7 @@ int main() {
         if (!(e < 2e-6)) ++bad;                                     \
     }
     {
-        const double e1 = check<4096, true>(), e2 = check<1024, true>(), e3 = check<256, true>();
-        printf("two-step twiddles: N=4096 %.3e  N=1024 %.3e  N=256 %.3e\n", e1, e2, e3);
-        if (!(e1 < 2e-6 && e2 < 2e-6 && e3 < 2e-6)) ++bad;
-    }
-    {
-        const double e1 = check<4096, false, true>(), e2 = check<1024, false, true>(), e3 = check<16, false, true>();
+        const double e1 = check<4096, true>(), e2 = check<1024, true>(), e3 = check<16, true>();
         printf("FMA-form butterflies: N=4096 %.3e  N=1024 %.3e  N=16 %.3e\n", e1, e2, e3);
         if (!(e1 < 2e-6 && e2 < 2e-6 && e3 < 2e-6)) ++bad;
     }

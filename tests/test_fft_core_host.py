@@ -9,7 +9,7 @@ import tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_block_fft_schedule_on_host():
+def test_block_fft_shipped_forms_on_host():
     src = os.path.join(REPO, "tests", "host_fft_emul.cpp")
     inc = os.path.join(REPO, "gps-jamming_amd", "csrc")
     with tempfile.TemporaryDirectory() as d:

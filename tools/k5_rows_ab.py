@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """K5 variants (VERDICT r05 "next" 5), interleaved on one box: three antennas, three pairs, slices of --n samples; one child
 process per (variant, round): `default` is the shipped library, `lib:<name>` an alternative build made by
-tools/ab_build.sh (e.g. `tools/ab_build.sh xcnt "-DGJ_XC_NT=1" k_xcorr.hip`).  Each child prints the solve time (events
+tools/ab_build.sh (`tools/ab_build.sh <name> "<hipcc flags>" k_xcorr.hip`).  Each child prints the solve time (events
 around `reps` back-to-back gj_xcorr_lags_dev calls) and a digest of lags / peaks / margins: every variant must give the
 same bytes.  (Round 6 also measured a three-antenna row kernel that transforms every row once -- `pair` / `trio` in
 profiles/r06_k5_rows_ab_v1.txt; it was no faster and is gone.)
-    python tools/k5_rows_ab.py [--n 524288] [--rounds 3] [--variants default,lib:xcnt]"""
+    python tools/k5_rows_ab.py [--n 524288] [--rounds 3] [--variants default,lib:<name>]"""
 import argparse
 import hashlib
 import json

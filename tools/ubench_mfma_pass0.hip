@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256, 3) void step_kernel(float* __restrict__ out, c
                 const c2 t = cadd(f, khalf);
                 v[s] = make_c2(t.x * w16[s], t.y * w16[s]);
             }
-            fft_pass<4096, 0, false, true>(v, tw1, ktw);
+            fft_pass<4096, 0, true>(v, tw1, ktw);
         } else {
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
@@ -101,8 +101,8 @@ __global__ __launch_bounds__(256, 3) void step_kernel(float* __restrict__ out, c
 #pragma unroll
             for (int k = 0; k < W; ++k) v[k & 15] = fma2(v[(k + 1) & 15], tw1[k % 15], v[k & 15]);
         }
-        fft_pass<4096, 1, false, true>(v, tw1, ktw);
-        fft_pass<4096, 2, false, true>(v, tw2, ktw);
+        fft_pass<4096, 1, true>(v, tw1, ktw);
+        fft_pass<4096, 2, true>(v, tw2, ktw);
 #pragma unroll
         for (int s = 0; s < 16; ++s) acc[s] = fmaf(v[s].x, v[s].x, fmaf(v[s].y, v[s].y, acc[s]));
     }
