@@ -774,6 +774,20 @@ size_t gj_acq_workspace(gj_ctx*, int nsamp, int n_freq, int n_prn, int intg, int
     return acq_workspace(nsamp, n_freq, n_prn, intg, with_power == 0);
 }
 
+int gj_acq_series_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t stride_samples, int n_epochs,
+                      int epochs_per_launch, int nsamp, int intg, const int16_t* d_codes, int n_prn, const uint8_t* d_phase,
+                      int n_freq, int nsampchip, double ctime, float threshold, gj_acq_result* d_out) {
+    GJ_ENTER(ctx);
+    if (!d_iq || !d_codes || !d_phase || !d_out) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+    return launch_acq_series(ctx, d_iq, nbytes, first_sample, stride_samples, n_epochs, epochs_per_launch, nsamp, intg, d_codes,
+                             n_prn, d_phase, n_freq, nsampchip, ctime, threshold, d_out);
+}
+
+size_t gj_acq_series_workspace(gj_ctx*, int nsamp, int n_freq, int n_prn, int intg, int n_epochs, int epochs_per_launch) {
+    if (nsamp <= 0 || n_freq <= 0 || n_prn <= 0 || intg <= 0 || n_epochs <= 0 || epochs_per_launch < 0) return 0;
+    return acq_series_workspace(nsamp, n_freq, n_prn, intg, n_epochs, epochs_per_launch);
+}
+
 int gj_synth_u8_dev(gj_ctx* ctx, const gj_synth_params* params, int64_t first_sample, size_t n_samples, uint8_t* d_out) {
     GJ_ENTER(ctx);
     if (!params || (n_samples && !d_out)) return fail(ctx, GJ_ERR_INVALID, "null buffer");

@@ -419,6 +419,9 @@ int launch_split_combine(gj_ctx*, const gj_combine_plan*, const double*);
 int launch_acq_search(gj_ctx*, const uint8_t*, size_t, size_t, int, int, const int16_t*, int, const uint8_t*, int, int, double,
                       float, gj_acq_result*, double*);
 size_t acq_workspace(int, int, int, int, bool);
+int launch_acq_series(gj_ctx*, const uint8_t*, size_t, size_t, size_t, int, int, int, int, const int16_t*, int, const uint8_t*, int,
+                      int, double, float, gj_acq_result*);
+size_t acq_series_workspace(int, int, int, int, int, int);
 size_t xcorr_workspace(gj_ctx*, int, size_t, int);
 int launch_synth(gj_ctx*, const gj_synth_params&, int64_t, size_t, uint8_t*);
 int launch_pack_result(gj_ctx*, size_t, const float*, const float*, const gj_amp_stats*, const gj_onset*, const float*, size_t,

@@ -131,6 +131,25 @@ __global__ __launch_bounds__(kBlockThreads) void acq_prep_kernel(AcqParams P, co
     else acq_fwd_body<N>(P, phase, twtab, xspec, lds, (int)blockIdx.x - code_blocks);
 }
 
+// The series' data transforms for one batch of epochs: grid (ceil(intg n_freq / B), E), epoch e's windows start at
+// P.first_sample + e * stride.  The code spectra are transformed once per call (acq_prep_kernel with code blocks only),
+// so these workgroups clear the batch's running maxima [E][n_prn][intg] instead (acq_inv_all_kernel<N, true> comes next
+// in stream order, after the previous batch's has finished).
+template <int N>
+__global__ __launch_bounds__(kBlockThreads) void acq_series_prep_kernel(AcqParams P, unsigned long long stride,
+                                                                        const uint8_t* __restrict__ phase, const cf* __restrict__ twtab,
+                                                                        cf* __restrict__ xspec /* [E][intg][n_freq][N] */,
+                                                                        unsigned long long* __restrict__ gmax, size_t n_gmax) {
+    constexpr int B = kBlockPoints / N;
+    __shared__ cf lds[B * lds_span(N)];
+    const size_t nblk = (size_t)gridDim.x * gridDim.y, blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    for (size_t i = blk * kBlockThreads + threadIdx.x; i < n_gmax; i += nblk * kBlockThreads) gmax[i] = 0ull;
+    const unsigned e = blockIdx.y;
+    AcqParams Pe = P;
+    Pe.first_sample += (unsigned long long)e * stride;
+    acq_fwd_body<N>(Pe, phase, twtab, xspec + (size_t)e * P.intg * P.n_freq * N, lds, (int)blockIdx.x);
+}
+
 // grid.x = ceil(n_freq / B), grid.y = PRN.  |IFFT(Y)|^2 = |FFT(conj Y)|^2, Y = -X conj(C)  (cpxconv's product).
 template <int N>
 __global__ __launch_bounds__(kBlockThreads) void acq_inv_kernel(AcqParams P, int step, const int* __restrict__ done,
@@ -362,7 +381,14 @@ __device__ __forceinline__ void acq_transform(c2 (&v)[16], cf* lds, int tid, int
 // have been offered before it), so acq_summary_kernel finds the same record with the same bits; with the rows arriving
 // in arbitrary order about ln 71 = 4-5 of the 71 do the full bookkeeping instead of all.  Records of skipped rows
 // carry their maximum and cnt = 0.
-template <int N>
+//
+// SERIES (acq_series_run): grid.y = the epoch of the batch, the slowest grid index, and each epoch has its own data
+// spectra [E][intg][n_freq][N], row records [E][n_prn][intg][n_freq] and running maxima [E][n_prn][intg].  The grid's x
+// extent is a multiple of eight, so the residues of blockIdx.x still deal the Doppler groups over the XCDs inside every
+// epoch.  The epoch's offsets are workgroup-uniform (blockIdx.y and kernel arguments: scalar registers); everything else
+// is the single search's code.  (A flag, not a wrapper kernel around a shared body: inlined into a wrapper, the single
+// search compiled to different float contractions, and its results changed in the last bits.)
+template <int N, bool SERIES = false>
 __global__ __launch_bounds__(kBlockThreads, N == 2048 ? 2 : 3) void acq_inv_all_kernel(AcqParams P, int nsampchip, const cf* __restrict__ twtab,
                                                                     const cf* __restrict__ xspec,
                                                                     const cf* __restrict__ cspec,
@@ -376,6 +402,12 @@ __global__ __launch_bounds__(kBlockThreads, N == 2048 ? 2 : 3) void acq_inv_all_
     __shared__ AcqTail sht[kBlockThreads / 64];
     __shared__ int sh_need[2][B];               // [step parity][transform]: this row may hold the step's peak
     __shared__ unsigned long long sh_seen[2];   // (one transform per workgroup) the running maximum as read when the step began
+    if constexpr (SERIES) {
+        const size_t e = blockIdx.y, per = (size_t)P.n_prn * P.intg;
+        xspec += e * P.intg * P.n_freq * N;
+        rows += e * per * P.n_freq;
+        gmax += e * per;
+    }
     const int slot = blockIdx.x >> 3;
     const int p = slot % P.n_prn, fg = (int)(blockIdx.x & 7) + 8 * (slot / P.n_prn);
     if (fg * B >= P.n_freq) return;            // the whole workgroup: the grid is padded to a multiple of eight groups
@@ -532,10 +564,8 @@ __global__ __launch_bounds__(kBlockThreads, N == 2048 ? 2 : 3) void acq_inv_all_
 // the reference's loop over the integration steps (sdracq.c:15-28), replayed on the row records: wave w finds the
 // winning Doppler row of steps w, w + 16, ... (their loads are in flight together), then one thread walks the steps
 // in order and stops at the first that passes the peak test
-__global__ __launch_bounds__(1024) void acq_summary_kernel(AcqParams P, double ctime, float threshold,
-                                                           const AcqRow* __restrict__ rows, gj_acq_result* __restrict__ out) {
-    __shared__ AcqRow win[64];     // intg <= 64 (launch_acq_search)
-    __shared__ int winf[64];
+__device__ __forceinline__ void acq_summary_body(const AcqParams& P, double ctime, float threshold, const AcqRow* __restrict__ rows,
+                                                 gj_acq_result* __restrict__ out, AcqRow* win, int* winf) {
     const int p = blockIdx.x, lane = threadIdx.x & 63;
     for (int step = threadIdx.x >> 6; step < P.intg; step += blockDim.x >> 6) {
         const AcqRow* rr = rows + ((size_t)p * P.intg + step) * P.n_freq;
@@ -576,6 +606,21 @@ __global__ __launch_bounds__(1024) void acq_summary_kernel(AcqParams P, double c
             return;
         }
     }
+}
+__global__ __launch_bounds__(1024) void acq_summary_kernel(AcqParams P, double ctime, float threshold,
+                                                           const AcqRow* __restrict__ rows, gj_acq_result* __restrict__ out) {
+    __shared__ AcqRow win[64];     // intg <= 64 (launch_acq_search)
+    __shared__ int winf[64];
+    acq_summary_body(P, ctime, threshold, rows, out, win, winf);
+}
+// grid (n_prn, E): the epochs of a batch, rows and results at the epoch's offsets
+__global__ __launch_bounds__(1024) void acq_summary_series_kernel(AcqParams P, double ctime, float threshold,
+                                                                  const AcqRow* __restrict__ rows /* [E][n_prn][intg][n_freq] */,
+                                                                  gj_acq_result* __restrict__ out /* [E][n_prn] */) {
+    __shared__ AcqRow win[64];
+    __shared__ int winf[64];
+    const size_t e = blockIdx.y;
+    acq_summary_body(P, ctime, threshold, rows + e * P.n_prn * P.intg * P.n_freq, out + e * P.n_prn, win, winf);
 }
 
 size_t acq_workspace(int nsamp, int n_freq, int n_prn, int intg, bool own_power) {
@@ -635,20 +680,18 @@ static int acq_run(gj_ctx* ctx, const AcqParams& P, const short* d_codes, const 
     return GJ_OK;
 }
 
-int launch_acq_search(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, int nsamp, int intg,
-                      const int16_t* d_codes, int n_prn, const uint8_t* d_phase, int n_freq, int nsampchip, double ctime,
-                      float threshold, gj_acq_result* d_out, double* d_power) {
+// the shape checks every search form shares
+static int acq_check_shape(gj_ctx* ctx, const uint8_t* d_iq, int nsamp, int intg, int n_prn, int n_freq, int nsampchip,
+                           double ctime) {
     if (nsamp != 2048 && nsamp != 1024 && nsamp != 512) return fail(ctx, GJ_ERR_UNSUPPORTED, "nsamp must be 512, 1024 or 2048");
     if (intg < 1 || intg > 64 || n_prn < 1 || n_prn > 4096 || n_freq < 1 || n_freq > 4096)
         return fail(ctx, GJ_ERR_INVALID, "intg 1..64, n_prn and n_freq 1..4096");
     if (nsampchip < 0 || 4 * nsampchip >= nsamp || !(ctime > 0.0)) return fail(ctx, GJ_ERR_INVALID, "bad nsampchip / ctime");
     if ((reinterpret_cast<uintptr_t>(d_iq) & 1) != 0) return fail(ctx, GJ_ERR_INVALID, "capture must be 2-byte aligned");
-    // step s reads samples [first + s nsamp, first + s nsamp + 2 nsamp)  (rcvgetbuff of 2*nsamp, then += nsamp)
-    if (first_sample > nbytes / 2) return fail(ctx, GJ_ERR_INVALID, "first_sample %zu is past the capture's %zu samples", first_sample, nbytes / 2);
-    const size_t need = first_sample + (size_t)(intg + 1) * nsamp;   // cannot wrap: first_sample <= nbytes / 2
-    if (need > nbytes / 2) return fail(ctx, GJ_ERR_INVALID, "search needs samples up to %zu, capture has %zu", need, nbytes / 2);
-    int rc = ensure_workspace(ctx, acq_workspace(nsamp, n_freq, n_prn, intg, d_power == nullptr));
-    if (rc) return rc;
+    return GJ_OK;
+}
+
+static AcqParams acq_params(const uint8_t* d_iq, size_t first_sample, int nsamp, int intg, int n_prn, int n_freq) {
     AcqParams P;
     P.iq = d_iq;
     P.first_sample = first_sample;
@@ -660,6 +703,103 @@ int launch_acq_search(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t fi
     P.offset = 128;
     P.scale = (float)((1.0 / 32.0) / (double)P.nfft);   // CSCALE / m (sdrcmn.c:7,766)
     P.inv_m2 = 1.0f / ((float)P.nfft * (float)P.nfft);
+    return P;
+}
+
+// ---- acquisition series: n_epochs searches at first_sample + e * stride ------------------------------------------
+// Code spectra once per call; then per batch of at most E epochs three launches: the batch's data transforms (which also
+// clear its running maxima), acq_inv_all with the epoch as grid.y, the summary over (PRN, epoch).  Every epoch runs the
+// single search's arithmetic on its own spectra, row records and running maxima, so its result has the bits of a
+// separate gj_acq_search_dev at that first sample (the same-winner argument above acq_inv_all_kernel holds per epoch).
+constexpr int kAcqSeriesDefaultBatch = 16;   // 16 x 23 MB of data spectra at nsamp 2048, intg 10, 71 bins
+constexpr int kAcqSeriesMaxBatch = 4096;
+
+static int acq_series_batch(int n_epochs, int epochs_per_launch) {
+    const int e = epochs_per_launch > 0 ? epochs_per_launch : kAcqSeriesDefaultBatch;
+    return e < n_epochs ? e : n_epochs;
+}
+
+size_t acq_series_workspace(int nsamp, int n_freq, int n_prn, int intg, int n_epochs, int epochs_per_launch) {
+    const size_t nfft = 2 * (size_t)nsamp, E = (size_t)acq_series_batch(n_epochs, epochs_per_launch);
+    size_t b = align_up((size_t)n_prn * nfft * sizeof(cf), 256);                           // code spectra
+    b += align_up(E * intg * n_freq * nfft * sizeof(cf), 256);                            // data spectra [E]
+    b += align_up(E * n_prn * intg * n_freq * sizeof(AcqRow), 256);                       // row records [E]
+    b += align_up(E * n_prn * intg * sizeof(unsigned long long), 256);                    // running maxima [E]
+    return b;
+}
+
+template <int N>
+static int acq_series_run(gj_ctx* ctx, const AcqParams& P, size_t stride, int n_epochs, int E, const short* d_codes,
+                          const uint8_t* d_phase, int nsampchip, double ctime, float threshold, gj_acq_result* d_out) {
+    constexpr int B = kBlockPoints / N;
+    unsigned char* w = ctx->ws;
+    cf* cspec = reinterpret_cast<cf*>(w);
+    w += align_up((size_t)P.n_prn * N * sizeof(cf), 256);
+    cf* xspec = reinterpret_cast<cf*>(w);
+    w += align_up((size_t)E * P.intg * P.n_freq * N * sizeof(cf), 256);
+    AcqRow* rows = reinterpret_cast<AcqRow*>(w);
+    w += align_up((size_t)E * P.n_prn * P.intg * P.n_freq * sizeof(AcqRow), 256);
+    unsigned long long* gmax = reinterpret_cast<unsigned long long*>(w);
+    const int code_blocks = (P.n_prn + B - 1) / B, fwd_blocks = (P.intg * P.n_freq + B - 1) / B;
+    hipLaunchKernelGGL((acq_prep_kernel<N>), dim3((unsigned)code_blocks), dim3(kBlockThreads), 0, ctx->stream, P, d_codes, d_phase,
+                       ctx->d_twiddle, cspec, xspec, nullptr, 0, code_blocks);   // code blocks only: the code spectra
+    GJ_LAUNCH_CHECK(ctx);
+    const unsigned groups = (unsigned)((P.n_freq + B - 1) / B);
+    const unsigned waves = (unsigned)(P.intg < 16 ? P.intg : 16);
+    for (int e0 = 0; e0 < n_epochs; e0 += E) {
+        const int eb = n_epochs - e0 < E ? n_epochs - e0 : E;
+        AcqParams Pb = P;
+        Pb.first_sample += (unsigned long long)e0 * stride;
+        hipLaunchKernelGGL((acq_series_prep_kernel<N>), dim3((unsigned)fwd_blocks, (unsigned)eb), dim3(kBlockThreads), 0, ctx->stream,
+                           Pb, (unsigned long long)stride, d_phase, ctx->d_twiddle, xspec, gmax, (size_t)eb * P.n_prn * P.intg);
+        GJ_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL((acq_inv_all_kernel<N, true>), dim3(8u * (unsigned)P.n_prn * ((groups + 7u) / 8u), (unsigned)eb),
+                           dim3(kBlockThreads), 0, ctx->stream, Pb, nsampchip, ctx->d_twiddle, xspec, cspec, rows, gmax);
+        GJ_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(acq_summary_series_kernel, dim3((unsigned)P.n_prn, (unsigned)eb), dim3(64u * waves), 0, ctx->stream, Pb,
+                           ctime, threshold, rows, d_out + (size_t)e0 * P.n_prn);   // every (epoch, PRN) record of the batch
+        GJ_LAUNCH_CHECK(ctx);
+    }
+    return GJ_OK;
+}
+
+int launch_acq_series(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t stride_samples, int n_epochs,
+                      int epochs_per_launch, int nsamp, int intg, const int16_t* d_codes, int n_prn, const uint8_t* d_phase,
+                      int n_freq, int nsampchip, double ctime, float threshold, gj_acq_result* d_out) {
+    if (int rc = acq_check_shape(ctx, d_iq, nsamp, intg, n_prn, n_freq, nsampchip, ctime)) return rc;
+    if (n_epochs < 1) return fail(ctx, GJ_ERR_INVALID, "n_epochs must be at least 1");
+    if (epochs_per_launch < 0 || epochs_per_launch > kAcqSeriesMaxBatch)
+        return fail(ctx, GJ_ERR_INVALID, "epochs_per_launch 0 (default) or 1..%d", kAcqSeriesMaxBatch);
+    // epoch e reads samples [first + e stride, first + e stride + (intg + 1) nsamp): bound the last one by subtraction
+    // and division, so that no product or sum can wrap
+    const size_t avail = nbytes / 2, window = (size_t)(intg + 1) * nsamp;
+    if (first_sample > avail || window > avail - first_sample)
+        return fail(ctx, GJ_ERR_INVALID, "the first epoch needs samples from %zu to %zu more, capture has %zu", first_sample, window, avail);
+    if (n_epochs > 1 && stride_samples > (avail - first_sample - window) / (size_t)(n_epochs - 1))
+        return fail(ctx, GJ_ERR_INVALID, "epoch %d at stride %zu runs past the capture's %zu samples", n_epochs - 1, stride_samples, avail);
+    int rc = ensure_workspace(ctx, acq_series_workspace(nsamp, n_freq, n_prn, intg, n_epochs, epochs_per_launch));
+    if (rc) return rc;
+    const AcqParams P = acq_params(d_iq, first_sample, nsamp, intg, n_prn, n_freq);
+    const short* codes = reinterpret_cast<const short*>(d_codes);
+    const int E = acq_series_batch(n_epochs, epochs_per_launch);
+    switch (P.nfft) {
+        case 4096: return acq_series_run<4096>(ctx, P, stride_samples, n_epochs, E, codes, d_phase, nsampchip, ctime, threshold, d_out);
+        case 2048: return acq_series_run<2048>(ctx, P, stride_samples, n_epochs, E, codes, d_phase, nsampchip, ctime, threshold, d_out);
+        default: return acq_series_run<1024>(ctx, P, stride_samples, n_epochs, E, codes, d_phase, nsampchip, ctime, threshold, d_out);
+    }
+}
+
+int launch_acq_search(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, int nsamp, int intg,
+                      const int16_t* d_codes, int n_prn, const uint8_t* d_phase, int n_freq, int nsampchip, double ctime,
+                      float threshold, gj_acq_result* d_out, double* d_power) {
+    if (int rc = acq_check_shape(ctx, d_iq, nsamp, intg, n_prn, n_freq, nsampchip, ctime)) return rc;
+    // step s reads samples [first + s nsamp, first + s nsamp + 2 nsamp)  (rcvgetbuff of 2*nsamp, then += nsamp)
+    if (first_sample > nbytes / 2) return fail(ctx, GJ_ERR_INVALID, "first_sample %zu is past the capture's %zu samples", first_sample, nbytes / 2);
+    const size_t need = first_sample + (size_t)(intg + 1) * nsamp;   // cannot wrap: first_sample <= nbytes / 2
+    if (need > nbytes / 2) return fail(ctx, GJ_ERR_INVALID, "search needs samples up to %zu, capture has %zu", need, nbytes / 2);
+    int rc = ensure_workspace(ctx, acq_workspace(nsamp, n_freq, n_prn, intg, d_power == nullptr));
+    if (rc) return rc;
+    const AcqParams P = acq_params(d_iq, first_sample, nsamp, intg, n_prn, n_freq);
     const short* codes = reinterpret_cast<const short*>(d_codes);
     switch (P.nfft) {
         case 4096: return acq_run<4096>(ctx, P, codes, d_phase, nsampchip, ctime, threshold, d_out, d_power);

@@ -212,6 +212,8 @@ SIGNATURES = {
     "gj_combine_plan_check": (_i, [C.POINTER(CombineCopy), _i, C.POINTER(CombineCapture), _i, _sz, _vp, _sz, _i, _i]),
     "gj_acq_search_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp, _i, _vp, _i, _i, _d, _f, _vp, _vp]),
     "gj_acq_workspace": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "gj_acq_series_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _d, _f, _vp]),
+    "gj_acq_series_workspace": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
     "gj_comm_unique_id": (_i, [_vp]),
     "gj_comm_init_rank": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
     "gj_comm_rank": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),

@@ -11,13 +11,18 @@ at start-up, in a few microseconds per channel (GpsJammerApp/backend/):
 * the mixer's phase index per sample     sdrcmn.c:618-659,676-684 (mixcarr, SSE2 form: 16-entry table,
                                          phases accumulated in doubles in ITS order, truncated toward zero)
 
+``AcqSearch.series`` runs the search epoch after epoch over a whole capture (``gj_acq_series_dev``), and
+``telemetry`` turns the result into gnssdec-shaped records for the drop-in worker's detector.  The C/N0 there is
+the acquisition's 10 log10(maxP / meanP / ctime), not gnssdec's tracking SNR: comparable between the epochs of one
+capture, not with gnssdec's numbers.
+
 Nothing here is a CPU fallback for the kernels: without the HIP library ``AcqSearch`` cannot be built.
 """
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Sequence
+from typing import Iterator, List, Sequence
 
 import numpy as np
 
@@ -137,6 +142,46 @@ class AcqResult:
     mean_power: float
 
 
+@dataclass
+class AcqSeries:
+    """One search per epoch over a capture: arrays [n_epochs][n_prn] (PRNs in ``prns`` order), and per epoch its
+    first sample and that sample's time from the start of the capture."""
+    prns: List[int]
+    first_sample: np.ndarray     # int64 [n_epochs]
+    elapsed_s: np.ndarray        # float64 [n_epochs]
+    acquired: np.ndarray         # bool
+    cn0: np.ndarray              # float64, dB-Hz (acquisition C/N0)
+    peak_ratio: np.ndarray
+    code_index: np.ndarray
+    freq_index: np.ndarray
+    doppler_hz: np.ndarray
+    steps: np.ndarray
+
+    @property
+    def n_epochs(self) -> int:
+        return int(self.first_sample.size)
+
+    def cn0_avg(self) -> np.ndarray:
+        """Per epoch the mean C/N0 of the PRNs acquired at that epoch, 0.0 where none is: the worker's
+        ``current_cn0_avg = mean(snr of the observations)`` (worker.py:303-306), acquired standing for tracked."""
+        n = self.acquired.sum(axis=1)
+        tot = np.where(self.acquired, self.cn0, 0.0).sum(axis=1)
+        return np.where(n > 0, tot / np.maximum(n, 1), 0.0)
+
+
+def telemetry(series: AcqSeries) -> Iterator[dict]:
+    """One gnssdec-shaped telemetry record per epoch (the fields ``process_incoming_data`` reads, sdrout.c:214-325):
+    ``elapsed_time``; ``position`` with ``buffcnt`` = the epoch's first BYTE (the unit of ``jamming_byte_ranges``),
+    no fix (nsat 0, lat / lon / hgt 0, so the altitude flag stays off); ``observations`` = prn and snr of each PRN
+    acquired at the epoch.  Fed to an unmodified ``GPSAnalysisThread`` they drive its own F1 / F2 state machine."""
+    for e in range(series.n_epochs):
+        obs = [{"prn": int(p), "snr": float(series.cn0[e, k])}
+               for k, p in enumerate(series.prns) if series.acquired[e, k]]
+        yield {"elapsed_time": float(series.elapsed_s[e]),
+               "position": {"buffcnt": 2 * int(series.first_sample[e]), "lat": 0.0, "lon": 0.0, "hgt": 0.0, "nsat": 0},
+               "observations": obs}
+
+
 class _AcqStruct(C.Structure):
     _fields_ = [("max_power", C.c_double), ("second_power", C.c_double), ("mean_power", C.c_double),
                 ("peak_ratio", C.c_double), ("cn0", C.c_double), ("code_index", C.c_int32),
@@ -199,6 +244,55 @@ class AcqSearch:
             d_power.free()
             return res, p
         return res
+
+    def series_workspace(self, n_epochs: int, epochs_per_launch: int = 0) -> int:
+        return int(self.dev._lib.gj_acq_series_workspace(self.dev._ctx, self.nsamp, len(self.freqs), len(self.prns),
+                                                         self.intg, int(n_epochs), int(epochs_per_launch)))
+
+    def series_dev(self, d_iq, nbytes: int, first_sample: int, stride_samples: int, n_epochs: int, d_out,
+                   epochs_per_launch: int = 0):
+        """Enqueue a series (no host synchronisation); d_out receives gj_acq_result[n_epochs][n_prn]."""
+        from . import _ptr
+        self.dev._check(self.dev._lib.gj_acq_series_dev(
+            self.dev._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(stride_samples), int(n_epochs),
+            int(epochs_per_launch), self.nsamp, self.intg, self.d_codes.ptr, len(self.prns), self.d_phase.ptr,
+            len(self.freqs), self.nsampchip, self.ctime, self.threshold, _ptr(d_out)))
+
+    def series(self, capture, first_sample: int = 0, stride_samples=None, n_epochs=None,
+               epochs_per_launch: int = 0) -> AcqSeries:
+        """Search a resident capture at first_sample + e * stride_samples, e = 0 .. n_epochs-1.  Default stride: 0.1 s
+        of samples (gnssdec's telemetry cadence); default n_epochs: as many as fit in the capture."""
+        nbytes = getattr(capture, "nbytes", None)
+        if nbytes is None:
+            nbytes = capture.numel() * capture.element_size()
+        if stride_samples is None:
+            stride_samples = int(round(0.1 * self.fs))
+        first_sample, stride_samples = int(first_sample), int(stride_samples)
+        if n_epochs is None:
+            room = nbytes // 2 - first_sample - self.samples_needed()
+            if room < 0:
+                raise ValueError("the capture does not hold one search window after first_sample")
+            n_epochs = 1 if stride_samples == 0 else room // stride_samples + 1
+        n_epochs = int(n_epochs)
+        if n_epochs >= 1:
+            self.dev.reserve(self.series_workspace(n_epochs, epochs_per_launch))
+        rec = C.sizeof(_AcqStruct)
+        d_out = self.dev.alloc(rec * max(n_epochs, 1) * len(self.prns))
+        try:
+            self.dev.timer_start()
+            self.series_dev(capture, nbytes, first_sample, stride_samples, n_epochs, d_out, epochs_per_launch)
+            self.dev.last_kernel_ms = self.dev.timer_stop()
+            raw = d_out.download(np.uint8, rec * n_epochs * len(self.prns))
+        finally:
+            d_out.free()
+        r = np.frombuffer(raw.tobytes(), dtype=np.dtype([(n, np.float64 if t is C.c_double else np.int32)
+                                                         for n, t in _AcqStruct._fields_]))
+        r = r.reshape(n_epochs, len(self.prns))
+        first = first_sample + stride_samples * np.arange(n_epochs, dtype=np.int64)
+        return AcqSeries(prns=list(self.prns), first_sample=first, elapsed_s=first / self.fs,
+                         acquired=r["acquired"] != 0, cn0=r["cn0"].copy(), peak_ratio=r["peak_ratio"].copy(),
+                         code_index=r["code_index"].copy(), freq_index=r["freq_index"].copy(),
+                         doppler_hz=self.freqs[r["freq_index"]], steps=r["steps"].copy())
 
     def close(self):
         for b in (self.d_codes, self.d_phase, self.d_out):

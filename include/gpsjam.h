@@ -591,6 +591,21 @@ int gj_acq_search_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t fi
                       int nsampchip, double ctime, float threshold, gj_acq_result* d_out /* [n_prn] */,
                       double* d_power /* [n_prn*n_freq*nsamp] or NULL */);
 size_t gj_acq_workspace(gj_ctx* ctx, int nsamp, int n_freq, int n_prn, int intg, int with_power);
+/* Acquisition series: n_epochs searches of a resident capture, epoch e at first_sample + e*stride_samples
+ * (overlapping windows and stride 0 are allowed), d_out[e][p] = what gj_acq_search_dev(first_sample +
+ * e*stride_samples) without d_power writes for PRN p, bit for bit.  The code spectra are transformed once per
+ * call; the epochs run in batches of at most epochs_per_launch (0: 16; at most 4096), three launches per batch.
+ * Arguments and limits as in gj_acq_search_dev, and n_epochs >= 1; the last epoch's window must lie in the
+ * capture.  A refused call enqueues nothing.  The cn0 is the acquisition's 10 log10(maxP / meanP / ctime):
+ * comparable between epochs of one capture, not with a tracking loop's C/N0. */
+int gj_acq_series_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t stride_samples,
+                      int n_epochs, int epochs_per_launch, int nsamp, int intg, const int16_t* d_codes, int n_prn,
+                      const uint8_t* d_phase, int n_freq, int nsampchip, double ctime, float threshold,
+                      gj_acq_result* d_out /* [n_epochs][n_prn] */);
+/* The workspace gj_acq_series_dev ensures for these arguments (reserve it first to capture the call in a graph);
+ * 0 for arguments it would refuse by sign. */
+size_t gj_acq_series_workspace(gj_ctx* ctx, int nsamp, int n_freq, int n_prn, int intg, int n_epochs,
+                               int epochs_per_launch);
 
 /* ------------------------------------------------- collectives (RCCL over xGMI) ------- */
 /* One communicator rank per GPU / process, for hosts without torch.distributed.  The path
