@@ -412,6 +412,12 @@ size_t gj_xcorr_workspace(gj_ctx* ctx, int n_ant, size_t n_samples, int n_pairs)
     return xcorr_workspace(ctx, n_ant, n_samples, n_pairs);
 }
 
+size_t gj_xcorr_fft_len(size_t n_samples) { return xcorr_fft_len(n_samples); }
+
+size_t gj_xcorr_caf_workspace(gj_ctx* ctx, int n_ant, size_t n_samples, int n_pairs, int n_bins, int bins_per_launch) {
+    return xcorr_caf_workspace(ctx, n_ant, n_samples, n_pairs, n_bins, bins_per_launch);
+}
+
 // ---------------------------------------------------------------- device entry points
 #define GJ_ENTER(ctx)                 \
     if (!(ctx)) return GJ_ERR_INVALID; \
@@ -566,37 +572,73 @@ int gj_tdoa_slot_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, const int6
     return launch_tdoa_slot(ctx, d_iq, nbytes, d_start, n_samples, d_slot);
 }
 
-int gj_xcorr_slots_dev(gj_ctx* ctx, const uint8_t* d_slots, size_t slot_stride, int n_ant, size_t n_samples,
-                       const int32_t* pairs, int n_pairs, int32_t* d_lags, float* d_peaks, float* d_margins) {
-    GJ_ENTER(ctx);
-    if (!d_slots || !pairs || !d_lags || !d_peaks) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+// the slots the pairs of one call name, as the antennas of launch_xcorr / launch_xcorr_caf: only those are transformed,
+// at most GJ_MAX_ANTENNAS of them
+struct SlotTable {
+    const uint8_t* ptrs[GJ_MAX_ANTENNAS];
+    const int64_t* starts[GJ_MAX_ANTENNAS];
+    size_t sizes[GJ_MAX_ANTENNAS];
+    std::vector<int32_t> local_pairs;
+    int used = 0;
+};
+static int slot_table(gj_ctx* ctx, const uint8_t* d_slots, size_t slot_stride, int n_ant, size_t n_samples, const int32_t* pairs,
+                      int n_pairs, SlotTable& T) {
     if (n_ant < 1 || n_ant > 4096) return fail(ctx, GJ_ERR_INVALID, "n_ant must be 1..4096 slots");
     if (n_pairs < 1) return fail(ctx, GJ_ERR_INVALID, "n_pairs must be >= 1");
     if (slot_stride < GJ_SLOT_HEADER + 2 * n_samples || (slot_stride & 15) || (reinterpret_cast<uintptr_t>(d_slots) & 15))
         return fail(ctx, GJ_ERR_INVALID, "slot stride %zu too small for %zu samples or not 16-byte aligned", slot_stride,
                     n_samples);
-    // only the slots the pairs name are transformed: the pairs of one call may touch at most GJ_MAX_ANTENNAS of them
     int local_of[4096];
     for (int a = 0; a < n_ant; ++a) local_of[a] = -1;
-    const uint8_t* ptrs[GJ_MAX_ANTENNAS];
-    const int64_t* starts[GJ_MAX_ANTENNAS];
-    size_t sizes[GJ_MAX_ANTENNAS];
-    std::vector<int32_t> local_pairs((size_t)2 * n_pairs);
-    int used = 0;
+    T.local_pairs.resize((size_t)2 * n_pairs);
     for (int k = 0; k < 2 * n_pairs; ++k) {
         const int a = pairs[k];
         if (a < 0 || a >= n_ant) return fail(ctx, GJ_ERR_INVALID, "pair %d names slot %d of %d", k / 2, a, n_ant);
         if (local_of[a] < 0) {
-            if (used == GJ_MAX_ANTENNAS) return fail(ctx, GJ_ERR_UNSUPPORTED, "the pairs of one call touch more than %d slots", GJ_MAX_ANTENNAS);
+            if (T.used == GJ_MAX_ANTENNAS) return fail(ctx, GJ_ERR_UNSUPPORTED, "the pairs of one call touch more than %d slots", GJ_MAX_ANTENNAS);
             const uint8_t* slot = d_slots + (size_t)a * slot_stride;
-            ptrs[used] = slot + GJ_SLOT_HEADER;
-            starts[used] = reinterpret_cast<const int64_t*>(slot);   // the flag word: 0 valid / -1 invalid
-            sizes[used] = 2 * n_samples;
-            local_of[a] = used++;
+            T.ptrs[T.used] = slot + GJ_SLOT_HEADER;
+            T.starts[T.used] = reinterpret_cast<const int64_t*>(slot);   // the flag word: 0 valid / -1 invalid
+            T.sizes[T.used] = 2 * n_samples;
+            local_of[a] = T.used++;
         }
-        local_pairs[k] = local_of[a];
+        T.local_pairs[k] = local_of[a];
     }
-    return launch_xcorr(ctx, ptrs, sizes, used, starts, n_samples, local_pairs.data(), n_pairs, d_lags, d_peaks, d_margins);
+    return GJ_OK;
+}
+
+int gj_xcorr_slots_dev(gj_ctx* ctx, const uint8_t* d_slots, size_t slot_stride, int n_ant, size_t n_samples,
+                       const int32_t* pairs, int n_pairs, int32_t* d_lags, float* d_peaks, float* d_margins) {
+    GJ_ENTER(ctx);
+    if (!d_slots || !pairs || !d_lags || !d_peaks) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+    SlotTable T;
+    const int rc = slot_table(ctx, d_slots, slot_stride, n_ant, n_samples, pairs, n_pairs, T);
+    if (rc) return rc;
+    return launch_xcorr(ctx, T.ptrs, T.sizes, T.used, T.starts, n_samples, T.local_pairs.data(), n_pairs, d_lags, d_peaks, d_margins);
+}
+
+int gj_xcorr_caf_dev(gj_ctx* ctx, const uint8_t* const* d_iq, const size_t* nbytes, int n_ant, const int64_t* d_starts,
+                     size_t n_samples, const int32_t* pairs, int n_pairs, int bin_first, int n_bins, int bins_per_launch,
+                     gj_caf_result* d_out, int32_t* d_bin_lags, float* d_bin_peaks) {
+    GJ_ENTER(ctx);
+    if (!d_iq || !nbytes || !d_starts || !pairs || !d_out) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+    if (n_ant < 1 || n_ant > GJ_MAX_ANTENNAS) return fail(ctx, GJ_ERR_INVALID, "n_ant must be 1..%d", GJ_MAX_ANTENNAS);
+    const int64_t* sp[GJ_MAX_ANTENNAS];
+    for (int a = 0; a < n_ant; ++a) sp[a] = d_starts + a;
+    return launch_xcorr_caf(ctx, d_iq, nbytes, n_ant, sp, n_samples, pairs, n_pairs, bin_first, n_bins, bins_per_launch, d_out,
+                            d_bin_lags, d_bin_peaks);
+}
+
+int gj_xcorr_caf_slots_dev(gj_ctx* ctx, const uint8_t* d_slots, size_t slot_stride, int n_ant, size_t n_samples,
+                           const int32_t* pairs, int n_pairs, int bin_first, int n_bins, int bins_per_launch,
+                           gj_caf_result* d_out, int32_t* d_bin_lags, float* d_bin_peaks) {
+    GJ_ENTER(ctx);
+    if (!d_slots || !pairs || !d_out) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+    SlotTable T;
+    const int rc = slot_table(ctx, d_slots, slot_stride, n_ant, n_samples, pairs, n_pairs, T);
+    if (rc) return rc;
+    return launch_xcorr_caf(ctx, T.ptrs, T.sizes, T.used, T.starts, n_samples, T.local_pairs.data(), n_pairs, bin_first, n_bins,
+                            bins_per_launch, d_out, d_bin_lags, d_bin_peaks);
 }
 
 int gj_pack_result_dev(gj_ctx* ctx, size_t n_chunks, const float* d_power, const float* d_stats, const gj_amp_stats* d_amp,

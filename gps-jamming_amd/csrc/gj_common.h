@@ -95,7 +95,7 @@ namespace gj {
 
 constexpr int kSyncWords = 1024;    // 4 KiB
 constexpr int kSyncTail = 0;        // scan_tail_kernel
-constexpr int kSyncXcorr = 64;      // xc_cols_kernel<.., 1>: + pair index
+constexpr int kSyncXcorr = 64;      // xc_cols_kernel<.., 1>: + pair index; behind K5's words: caf_cols_kernel (k_xcorr.hip)
 
 // what the kernels need of the unpack convention: v = 2 u - off2 (exact integer), |sample| = |v| * half_scale
 struct Unpack {
@@ -423,6 +423,10 @@ int launch_acq_series(gj_ctx*, const uint8_t*, size_t, size_t, size_t, int, int,
                       int, double, float, gj_acq_result*);
 size_t acq_series_workspace(int, int, int, int, int, int);
 size_t xcorr_workspace(gj_ctx*, int, size_t, int);
+int launch_xcorr_caf(gj_ctx*, const uint8_t* const*, const size_t*, int, const int64_t* const*, size_t, const int32_t*, int, int, int,
+                     int, gj_caf_result*, int32_t*, float*);
+size_t xcorr_caf_workspace(gj_ctx*, int, size_t, int, int, int);
+size_t xcorr_fft_len(size_t);
 int launch_synth(gj_ctx*, const gj_synth_params&, int64_t, size_t, uint8_t*);
 int launch_pack_result(gj_ctx*, size_t, const float*, const float*, const gj_amp_stats*, const gj_onset*, const float*, size_t,
                        int, int, int, int, const int32_t*, const int32_t*, const float*, const float*, double*);

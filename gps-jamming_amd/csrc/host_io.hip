@@ -1062,4 +1062,65 @@ int gj_xcorr_lags_u8(gj_ctx* ctx, const uint8_t* const* slices, int n_ant, size_
     return GJ_OK;
 }
 
+// gj_xcorr_lags_u8 with the frequency-offset search (gj_xcorr_caf_dev); the ridge arrays are optional
+int gj_xcorr_caf_u8(gj_ctx* ctx, const uint8_t* const* slices, int n_ant, size_t n_samples, const int32_t* pairs, int n_pairs,
+                    int bin_first, int n_bins, gj_caf_result* out, int32_t* bin_lags, float* bin_peaks, float* kernel_ms) {
+    if (!ctx) return GJ_ERR_INVALID;
+    if (!slices || !pairs || !out) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+    if (n_ant < 1 || n_ant > GJ_MAX_ANTENNAS) return fail(ctx, GJ_ERR_INVALID, "n_ant must be 1..%d", GJ_MAX_ANTENNAS);
+    if (n_pairs < 1 || n_pairs > 4096) return fail(ctx, GJ_ERR_INVALID, "bad n_pairs");
+    if (n_bins < 1) return fail(ctx, GJ_ERR_INVALID, "n_bins must be >= 1");
+    if (n_bins > GJ_CAF_MAX_BINS) return fail(ctx, GJ_ERR_UNSUPPORTED, "more than %d bins in one call", GJ_CAF_MAX_BINS);
+    for (int a = 0; a < n_ant; ++a)
+        if (!slices[a]) return fail(ctx, GJ_ERR_INVALID, "null slice %d", a);
+    HostCall call(ctx);
+    gj_lane* L = call.L;
+    if (!L) return GJ_ERR_NOMEM;
+    // lane staging: [slot x n_ant of staged slices][starts: 16 x int64][records | ridge lags | ridge peaks]
+    const size_t slot = align_up(2 * n_samples, 256);
+    const size_t off_starts = slot * (size_t)n_ant + 256;
+    const size_t off_res = off_starts + 128;
+    const size_t cells = (size_t)n_pairs * (size_t)n_bins;
+    const size_t rec_bytes = sizeof(gj_caf_result) * (size_t)n_pairs;
+    const size_t res_bytes = rec_bytes + 8 * cells;
+    int rc = lane_events(ctx, L);
+    if (!rc) rc = lane_stage(ctx, L, off_res + res_bytes + 256);
+    if (!rc) rc = lane_rpin(ctx, L, res_bytes + 256);
+    if (rc) return rc;
+    hipStream_t s = current_stream(ctx);
+    const uint8_t* d_ptrs[GJ_MAX_ANTENNAS];
+    size_t nbytes[GJ_MAX_ANTENNAS];
+    for (int a = 0; a < n_ant; ++a) {
+        nbytes[a] = 2 * n_samples;
+        if (n_samples && is_device_ptr(slices[a])) {
+            d_ptrs[a] = slices[a];
+        } else {
+            if (n_samples) GJ_HIP(ctx, hipMemcpyAsync(L->stage + slot * a, slices[a], 2 * n_samples, hipMemcpyHostToDevice, s));
+            d_ptrs[a] = L->stage + slot * a;
+        }
+    }
+    int64_t* d_starts = reinterpret_cast<int64_t*>(L->stage + off_starts);   // zeros: slices start at their first sample
+    gj_caf_result* d_out = reinterpret_cast<gj_caf_result*>(L->stage + off_res);
+    int32_t* d_bin_lags = reinterpret_cast<int32_t*>(L->stage + off_res + rec_bytes);
+    float* d_bin_peaks = reinterpret_cast<float*>(L->stage + off_res + rec_bytes + 4 * cells);
+    GJ_HIP(ctx, hipMemsetAsync(d_starts, 0, 128, s));
+    GJ_HIP(ctx, hipEventRecord(L->ev_done, s));
+    const int64_t* sp[GJ_MAX_ANTENNAS];
+    for (int a = 0; a < n_ant; ++a) sp[a] = d_starts + a;
+    call.s = s;
+    call.staged = true;
+    call.d_res = L->stage + off_res;
+    call.result_bytes = res_bytes;
+    rc = call.run([&] {
+        return launch_xcorr_caf(ctx, d_ptrs, nbytes, n_ant, sp, n_samples, pairs, n_pairs, bin_first, n_bins, 0, d_out, d_bin_lags,
+                                d_bin_peaks);
+    });
+    if (!rc) rc = call.finish(kernel_ms);
+    if (rc) return rc;
+    memcpy(out, call.host(), rec_bytes);
+    if (bin_lags) memcpy(bin_lags, call.host(rec_bytes), 4 * cells);
+    if (bin_peaks) memcpy(bin_peaks, call.host(rec_bytes + 4 * cells), 4 * cells);
+    return GJ_OK;
+}
+
 }   // extern "C"

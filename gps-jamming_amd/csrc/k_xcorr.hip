@@ -347,15 +347,14 @@ static void xc_cols(gj_ctx* ctx, int mode, const XcParams& P, int count, cf* buf
     }
 }
 
-int launch_xcorr(gj_ctx* ctx, const uint8_t* const* d_iq, const size_t* nbytes, int n_ant,
-                 const int64_t* const* start_ptrs, size_t n_samples, const int32_t* pairs, int n_pairs, int32_t* d_lags,
-                 float* d_peaks, float* d_margins) {
+// argument checks and the kernels' parameter block, shared by K5 and the cross-ambiguity search
+static int xc_params(gj_ctx* ctx, const uint8_t* const* d_iq, const size_t* nbytes, int n_ant, const int64_t* const* start_ptrs,
+                     size_t n_samples, const int32_t* pairs, int n_pairs, XcParams& P) {
     if (n_ant < 1 || n_ant > GJ_MAX_ANTENNAS) return fail(ctx, GJ_ERR_INVALID, "n_ant must be 1..%d", GJ_MAX_ANTENNAS);
     if (n_pairs < 1 || n_pairs > kMaxPairs) return fail(ctx, GJ_ERR_INVALID, "n_pairs must be 1..%d", kMaxPairs);
     static_assert(kSyncXcorr + kMaxPairs <= kSyncWords, "one arrival counter per pair");
     if (n_samples < 1) return fail(ctx, GJ_ERR_INVALID, "n_samples must be >= 1");
     if (n_samples > (1ull << 23)) return fail(ctx, GJ_ERR_UNSUPPORTED, "slice longer than 2^23 samples");
-    XcParams P;
     memset(&P, 0, sizeof(P));
     P.off2 = ctx->off2;
     for (int a = 0; a < n_ant; ++a) {
@@ -375,8 +374,17 @@ int launch_xcorr(gj_ctx* ctx, const uint8_t* const* d_iq, const size_t* nbytes, 
     P.L1 = (int)(P.L / kRow);
     P.n_ant = n_ant;
     P.n_pairs = n_pairs;
+    return GJ_OK;
+}
+
+int launch_xcorr(gj_ctx* ctx, const uint8_t* const* d_iq, const size_t* nbytes, int n_ant,
+                 const int64_t* const* start_ptrs, size_t n_samples, const int32_t* pairs, int n_pairs, int32_t* d_lags,
+                 float* d_peaks, float* d_margins) {
+    XcParams P;
+    int rc = xc_params(ctx, d_iq, nbytes, n_ant, start_ptrs, n_samples, pairs, n_pairs, P);
+    if (rc) return rc;
     const size_t need = xcorr_workspace(ctx, n_ant, n_samples, n_pairs);
-    int rc = ensure_workspace(ctx, need);
+    rc = ensure_workspace(ctx, need);
     if (rc) return rc;
     cf* spec = reinterpret_cast<cf*>(ctx->ws);
     cf* dbuf = spec + (size_t)n_ant * P.L;
@@ -402,6 +410,243 @@ int launch_xcorr(gj_ctx* ctx, const uint8_t* const* d_iq, const size_t* nbytes, 
     GJ_LAUNCH_CHECK(ctx);
     return GJ_OK;
 }
+
+// ---- cross-ambiguity search: K5 over a grid of frequency offsets (gj_xcorr_caf_dev) ----------------------------
+// Bin b rotates antenna j by exp(-2 pi i b t / L).  The slice is zero-padded to L, so the rotation is an exact shift of
+// its spectrum: FFT_L(x_j^(b))[k] = Z_j[(k + b) mod L].  Every antenna is therefore transformed ONCE (K5's forward
+// columns, then xc_rows_kernel<0>, which stores the spectra), and per (pair, bin) only the product, the inverse rows and
+// the inverse columns with |.|^2 + arg-max repeat.  In the layout Z[k1][k2], k = k1 + L1 k2, the shift b = b1 + L1 b2
+// (taken mod L) turns row k1 into row (k1 + b1) mod L1 read from column (k2 + b2 + carry) mod 4096, carry = k1 + b1 >= L1:
+// a rotated contiguous row, no gather.  Bin 0 reads what xc_rows_kernel<1> reads and multiplies with the same
+// expression, so its lag, peak and margin are K5's bit for bit.
+//
+// Bins run in batches of `nb` (one rows launch + one columns launch per batch) so that the batch's D buffers stay in
+// the Infinity Cache.  Hand-over, two levels, both by arrive_release / last_arriver_acquire: the column workgroups of
+// one (pair, bin) meet in the last of them, which reduces the bin to one record; the bins of a pair -- across all
+// batches of the call -- meet in the last of THOSE, which picks the pair's winner.  No workgroup waits for another.
+struct CafBatch {
+    int bin_first;   // first bin of the call
+    int n_bins;      // bins of the call
+    int b0;          // first bin of this launch, counted from bin_first
+    int nb;          // bins of this launch
+};
+constexpr int kSyncCafPair = kSyncXcorr + kMaxPairs;   // + pair: bins of the pair that are done (all batches of a call)
+constexpr int kSyncCafBin = kSyncCafPair + kMaxPairs;  // + pair * nb + bin of the launch: column workgroups that are done
+constexpr int kCafBinWords = kSyncWords - kSyncCafBin; // pairs x bins one launch may hold
+static_assert(kCafBinWords >= kMaxPairs, "at least one bin per launch at the largest pair count");
+constexpr int kCafMaxBins = GJ_CAF_MAX_BINS;
+
+__global__ __launch_bounds__(kBlockThreads) void caf_rows_kernel(XcParams P, CafBatch B, const cf* __restrict__ twtab,
+                                                                 const cf* __restrict__ spec, cf* __restrict__ dbuf) {
+    constexpr int N = kRow, TF = N / 16;
+    __shared__ cf lds[lds_span(kBlockPoints)];
+    const int jl = threadIdx.x;
+    const unsigned r = blockIdx.x;   // k1
+    const int p = blockIdx.y;        // pair
+    const int q = blockIdx.z;        // bin of this launch
+    const long long b = (long long)B.bin_first + B.b0 + q;
+    const unsigned bb = (unsigned)((unsigned long long)(b + (long long)P.L) & (P.L - 1));   // b mod L (|b| < L / 2)
+    const unsigned L1 = (unsigned)P.L1;
+    const unsigned rs = r + (bb & (L1 - 1));
+    const unsigned rj = rs & (L1 - 1);                                   // row of the shifted operand
+    const unsigned rot = (bb / L1 + (rs >= L1 ? 1u : 0u)) & (N - 1);     // its rotation, carry included
+    const cf* zi = spec + (size_t)P.pair_i[p] * P.L + (size_t)r * N;
+    const cf* zj = spec + (size_t)P.pair_j[p] * P.L + (size_t)rj * N;
+    c2 v[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const cf a = zj[((unsigned)(jl + TF * s) + rot) & (N - 1)], bb2 = zi[jl + TF * s];
+        v[s] = make_c2(a.x * bb2.x + a.y * bb2.y, a.x * bb2.y - a.y * bb2.x);   // conj(a) * b, as xc_rows_kernel<1>
+    }
+    xc_passes<N, 0>(v, lds, 0, jl, twtab);
+    cf* dst = dbuf + ((size_t)p * B.nb + q) * P.L + (size_t)r * N;
+    c2 w = twiddle_big((unsigned long long)r * jl, P.L);
+    const c2 step = twiddle_big(((unsigned long long)r * TF) & (P.L - 1), P.L);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const int n2 = jl + TF * s;
+        dst[n2] = to_cf(cmul(v[s], w));
+        w = cmul(w, step);
+    }
+}
+
+// the workgroup's winner of one candidate per thread, in thread 0 (red: one slot per wave)
+__device__ __forceinline__ XcCand caf_block_merge(XcCand c, XcCand* red, int tid) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        XcCand o;
+        o.val = __shfl_xor(c.val, off, 64);
+        o.m = __shfl_xor(c.m, off, 64);
+        o.val2 = __shfl_xor(c.val2, off, 64);
+        o.pad = 0;
+        c = xc_merge(c, o);
+    }
+    if ((tid & 63) == 0) red[tid >> 6] = c;
+    __syncthreads();
+    XcCand r = red[0];
+    for (int k = 1; k < kBlockThreads / 64; ++k) r = xc_merge(r, red[k]);
+    __syncthreads();   // red is free again
+    return r;
+}
+
+// inverse columns of D[(pair, bin)] with |.|^2 + arg-max fused: xc_cols_kernel<L1, 1> with one candidate stream per
+// (pair, bin) and the two-level hand-over described above.  binrec[pair][bin of the call] = the bin's record.
+template <int L1>
+__global__ __launch_bounds__(kBlockThreads) void caf_cols_kernel(XcParams P, CafBatch B, const cf* __restrict__ twtab,
+                                                                 const cf* __restrict__ dbuf, XcCand* __restrict__ cand,
+                                                                 XcCand* __restrict__ binrec, unsigned* __restrict__ sync,
+                                                                 gj_caf_result* __restrict__ out, int* __restrict__ bin_lags,
+                                                                 float* __restrict__ bin_peaks) {
+    constexpr int TF = L1 / 16, NB = kBlockPoints / L1;
+    constexpr int RS = lds_span(L1) + 1;
+    __shared__ cf lds[NB * RS + 16];
+    __shared__ XcCand red[kBlockThreads / 64];
+    __shared__ int last_s;
+    const int tid = threadIdx.x;
+    const int b = tid % NB, jl = tid / NB;
+    const int t = blockIdx.y;                 // pair * nb + bin of this launch
+    const int p = t / B.nb, q = t - p * B.nb;
+    const unsigned tile = blockIdx.x, tiles = gridDim.x;
+    const int n2 = (int)tile * NB + b;
+    c2 v[16];
+    const cf* src = dbuf + (size_t)t * P.L;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) v[s] = xc_load(src + (unsigned)(jl + TF * s) * (unsigned)kRow + (unsigned)n2);
+    xc_passes<L1, 0>(v, lds, b * RS, jl, twtab);
+    XcCand c{-1.f, 0x7fffffff, -1.f, 0};
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const unsigned long long n = (unsigned long long)(jl + TF * s) * kRow + n2;
+        long long m;
+        if (n < P.n) m = (long long)n + (long long)P.n - 1;                 // lag = n >= 0
+        else if (n > P.L - P.n) m = (long long)n - (long long)P.L + (long long)P.n - 1;   // lag = n - L < 0
+        else continue;
+        const float val = v[s].x * v[s].x + v[s].y * v[s].y;
+        c = xc_merge(c, XcCand{val, (int)m, -1.f, 0});
+    }
+    XcCand r = caf_block_merge(c, red, tid);
+    unsigned* arrive_bin = sync + kSyncCafBin + t;
+    unsigned* arrive_pair = sync + kSyncCafPair + p;
+    if (tid == 0) {
+        cand[(size_t)t * tiles + tile] = r;
+        const int last = arrive_release(arrive_bin) == tiles - 1;
+        if (last) last_arriver_acquire(arrive_bin);
+        last_s = last;
+    }
+    __syncthreads();
+    if (!last_s) return;
+    // the bin's last column workgroup: its record, in candidate order (xc_merge is a total order)
+    r = XcCand{-1.f, 0x7fffffff, -1.f, 0};
+    for (unsigned k = tid; k < tiles; k += kBlockThreads) r = xc_merge(r, cand[(size_t)t * tiles + k]);
+    r = caf_block_merge(r, red, tid);
+    const int kbin = B.b0 + q;
+    XcCand* recs = binrec + (size_t)p * B.n_bins;
+    const float peak_scale = 0.25f / (float)P.L;   // inputs were 2(u-127.5): |c| = sqrt(val) / L / 4
+    if (tid == 0) {
+        long long e;
+        const bool ok = xc_start(P, P.pair_i[p], e) && xc_start(P, P.pair_j[p], e);
+        recs[kbin] = r;
+        if (bin_lags) bin_lags[(size_t)p * B.n_bins + kbin] = ok ? r.m - (int)(P.n - 1) : GJ_LAG_INVALID;
+        if (bin_peaks) bin_peaks[(size_t)p * B.n_bins + kbin] = ok ? sqrtf(r.val) * peak_scale : 0.f;
+        const int last = arrive_release(arrive_pair) == (unsigned)B.n_bins - 1;
+        if (last) last_arriver_acquire(arrive_pair);
+        last_s = last;
+    }
+    __syncthreads();
+    if (!last_s) return;
+    // the pair's last bin: larger peak first, then the earlier bin; the loser's peak is the runner-up BIN
+    XcCand w{-1.f, 0x7fffffff, -1.f, 0};
+    for (int k = tid; k < B.n_bins; k += kBlockThreads) w = xc_merge(w, XcCand{recs[k].val, k, -1.f, 0});
+    w = caf_block_merge(w, red, tid);
+    if (tid == 0) {
+        long long e;
+        const bool ok = xc_start(P, P.pair_i[p], e) && xc_start(P, P.pair_j[p], e);
+        const XcCand best = recs[w.m];
+        gj_caf_result o;
+        o.lag = ok ? best.m - (int)(P.n - 1) : GJ_LAG_INVALID;
+        o.bin = ok ? B.bin_first + w.m : 0;
+        o.peak = ok ? sqrtf(best.val) * peak_scale : 0.f;
+        o.margin_lag = (ok && best.val > 0.f) ? 1.0f - sqrtf(fmaxf(best.val2, 0.f) / best.val) : 0.f;
+        o.margin_bin = (ok && best.val > 0.f) ? 1.0f - sqrtf(fmaxf(w.val2, 0.f) / best.val) : 0.f;
+        o.reserved = 0.f;
+        out[p] = o;
+    }
+}
+
+// bins of one launch: 0 = so that the batch's D buffers (L * 8 bytes per pair and bin) fill half of the 256-MB
+// Infinity Cache; never more than the arrival counters hold, never more than the call has
+static int caf_bins_per_launch(unsigned long long L, int n_pairs, int n_bins, int requested) {
+    long long nb = requested > 0 ? requested : (long long)((128ull << 20) / (L * sizeof(cf) * (unsigned)n_pairs));
+    if (nb > kCafBinWords / n_pairs) nb = kCafBinWords / n_pairs;
+    if (nb > n_bins) nb = n_bins;
+    return nb < 1 ? 1 : (int)nb;
+}
+
+size_t xcorr_caf_workspace(gj_ctx*, int n_ant, size_t n_samples, int n_pairs, int n_bins, int bins_per_launch) {
+    if (n_samples == 0 || n_ant < 1 || n_pairs < 1 || n_pairs > kMaxPairs || n_bins < 1) return 0;
+    const unsigned long long L = xc_fft_len(n_samples);
+    const size_t ncand = (size_t)(L / kBlockPoints);
+    const size_t nb = (size_t)caf_bins_per_launch(L, n_pairs, n_bins, bins_per_launch);
+    return (size_t)n_ant * L * sizeof(cf) + (size_t)n_pairs * nb * (L * sizeof(cf) + ncand * sizeof(XcCand)) +
+           (size_t)n_pairs * (size_t)n_bins * sizeof(XcCand) + 4096;
+}
+
+template <int L1>
+static void caf_launch_cols(gj_ctx* ctx, const XcParams& P, const CafBatch& B, const cf* dbuf, XcCand* cand, XcCand* binrec,
+                            gj_caf_result* out, int* bin_lags, float* bin_peaks) {
+    hipLaunchKernelGGL((caf_cols_kernel<L1>), dim3((unsigned)(P.L / kBlockPoints), (unsigned)(P.n_pairs * B.nb)),
+                       dim3(kBlockThreads), 0, ctx->stream, P, B, ctx->d_twiddle, dbuf, cand, binrec, ctx->d_sync, out, bin_lags,
+                       bin_peaks);
+}
+
+int launch_xcorr_caf(gj_ctx* ctx, const uint8_t* const* d_iq, const size_t* nbytes, int n_ant,
+                     const int64_t* const* start_ptrs, size_t n_samples, const int32_t* pairs, int n_pairs, int bin_first,
+                     int n_bins, int bins_per_launch, gj_caf_result* d_out, int32_t* d_bin_lags, float* d_bin_peaks) {
+    XcParams P;
+    int rc = xc_params(ctx, d_iq, nbytes, n_ant, start_ptrs, n_samples, pairs, n_pairs, P);
+    if (rc) return rc;
+    if (n_bins < 1) return fail(ctx, GJ_ERR_INVALID, "n_bins must be >= 1");
+    if (bins_per_launch < 0) return fail(ctx, GJ_ERR_INVALID, "bins_per_launch must be >= 0");
+    const long long half = (long long)(P.L / 2), lo = bin_first, hi = (long long)bin_first + n_bins - 1;
+    if (lo <= -half || hi >= half) return fail(ctx, GJ_ERR_INVALID, "every bin must lie inside (-L/2, L/2), L = %llu", P.L);
+    if (n_bins > kCafMaxBins) return fail(ctx, GJ_ERR_UNSUPPORTED, "more than %d bins in one call", kCafMaxBins);
+    const int nb_max = caf_bins_per_launch(P.L, n_pairs, n_bins, bins_per_launch);
+    rc = ensure_workspace(ctx, xcorr_caf_workspace(ctx, n_ant, n_samples, n_pairs, n_bins, bins_per_launch));
+    if (rc) return rc;
+    const size_t ncand = (size_t)(P.L / kBlockPoints);
+    cf* spec = reinterpret_cast<cf*>(ctx->ws);
+    cf* dbuf = spec + (size_t)n_ant * P.L;
+    XcCand* cand = reinterpret_cast<XcCand*>(dbuf + (size_t)n_pairs * nb_max * P.L);
+    XcCand* binrec = cand + (size_t)n_pairs * nb_max * ncand;
+
+    // forward: K5's columns, then the rows of every antenna with the spectra stored
+    xc_cols(ctx, 0, P, n_ant, spec, nullptr);
+    GJ_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL((xc_rows_kernel<0>), dim3((unsigned)P.L1, (unsigned)n_ant), dim3(kBlockThreads), 0, ctx->stream, P,
+                       ctx->d_twiddle, spec, dbuf);
+    GJ_LAUNCH_CHECK(ctx);
+    for (int b0 = 0; b0 < n_bins; b0 += nb_max) {
+        const CafBatch B{bin_first, n_bins, b0, n_bins - b0 < nb_max ? n_bins - b0 : nb_max};
+        hipLaunchKernelGGL(caf_rows_kernel, dim3((unsigned)P.L1, (unsigned)n_pairs, (unsigned)B.nb), dim3(kBlockThreads), 0,
+                           ctx->stream, P, B, ctx->d_twiddle, spec, dbuf);
+        GJ_LAUNCH_CHECK(ctx);
+        switch (P.L1) {
+            case 16: caf_launch_cols<16>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+            case 32: caf_launch_cols<32>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+            case 64: caf_launch_cols<64>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+            case 128: caf_launch_cols<128>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+            case 256: caf_launch_cols<256>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+            case 512: caf_launch_cols<512>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+            case 1024: caf_launch_cols<1024>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+            case 2048: caf_launch_cols<2048>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+            default: caf_launch_cols<4096>(ctx, P, B, dbuf, cand, binrec, d_out, d_bin_lags, d_bin_peaks); break;
+        }
+        GJ_LAUNCH_CHECK(ctx);
+    }
+    return GJ_OK;
+}
+
+size_t xcorr_fft_len(size_t n_samples) { return n_samples ? (size_t)xc_fft_len(n_samples) : 0; }
 
 // ---- TDOA slot (layout and rules: tdoa_slot_body, gj_common.h) ----
 __global__ __launch_bounds__(256) void tdoa_slot_kernel(const uint8_t* __restrict__ iq, size_t nsamples,

@@ -16,7 +16,7 @@ raises ``GpsJamLibraryError``.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -26,7 +26,7 @@ from ._ffi import (AmpStats, GpsJamError, GpsJamLibraryError, Onset, SynthParams
 
 __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "device_count",
            "library_path", "as_u8", "default_device", "read_capture", "resident_capture",
-           "release_resident"]
+           "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -132,6 +132,33 @@ def device_count() -> int:
     n = C.c_int(0)
     _ffi.load().gj_device_count(C.byref(n))
     return n.value
+
+
+def xcorr_fft_len(n_samples: int) -> int:
+    """FFT length L of K5 and of the cross-ambiguity search for a slice of n_samples (gj_xcorr_fft_len)."""
+    return int(_ffi.load().gj_xcorr_fft_len(int(n_samples)))
+
+
+def xcorr_bin_hz(n_samples: int, fs: float = 2.048e6) -> float:
+    """Width of one frequency bin of ``Device.xcorr_caf`` for slices of n_samples: fs / L."""
+    return float(fs) / xcorr_fft_len(n_samples)
+
+
+def caf_bin_range(n_samples: int, max_offset_hz: float, fs: float = 2.048e6):
+    """(bin_first, n_bins) of the symmetric bin range that covers +-max_offset_hz."""
+    k = int(np.ceil(abs(float(max_offset_hz)) / xcorr_bin_hz(n_samples, fs) - 1e-9))
+    return -k, 2 * k + 1
+
+
+class CafPeak(NamedTuple):
+    """One pair of ``Device.xcorr_caf``: the maximum of |correlate(slice_j rotated by -bin, slice_i)| over lag and bin
+    (gj_caf_result, include/gpsjam.h).  ``offset_hz`` = bin * fs / L: receiver j sees the source that much higher."""
+    lag: int
+    bin: int
+    offset_hz: float
+    peak: float
+    margin_lag: float
+    margin_bin: float
 
 
 def as_u8(raw) -> np.ndarray:
@@ -638,6 +665,46 @@ class Device:
             return lags, peaks, margins
         return lags, peaks
 
+    def xcorr_caf(self, slices: Sequence, pairs: Sequence[Sequence[int]], max_offset_hz: Optional[float] = None,
+                  bins: Optional[Sequence[int]] = None, fs: float = 2.048e6, want_ridge: bool = False):
+        """Lag AND frequency offset of slice j relative to slice i, for receivers on separate oscillators
+        (gj_xcorr_caf_u8): a list of ``CafPeak``, one per pair.  ``slices``: equal-length uint8 arrays or resident
+        ``Capture``s.  The bins searched: ``bins = (bin_first, n_bins)``, or the symmetric range that covers
+        ``max_offset_hz``; neither: bin 0 alone (= ``xcorr_lags``).  ``want_ridge``: also the best lag and its peak
+        of every bin, two arrays [n_pairs][n_bins]."""
+        ins = [self._input(s) for s in slices]
+        n = ins[0][1] // 2
+        if any(nb != 2 * n for _, nb, _ in ins):
+            raise ValueError("slices must have equal, even length")
+        if bins is not None and max_offset_hz is not None:
+            raise ValueError("give max_offset_hz or bins, not both")
+        if bins is not None:
+            bin_first, n_bins = int(bins[0]), int(bins[1])
+        elif max_offset_hz is not None:
+            bin_first, n_bins = caf_bin_range(n, max_offset_hz, fs)
+        else:
+            bin_first, n_bins = 0, 1
+        ptrs = (C.c_void_p * len(ins))(*[p for p, _, _ in ins])
+        flat = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1))
+        npairs = flat.size // 2
+        out = (_ffi.CafResult * max(npairs, 1))()
+        cells = max(npairs * max(n_bins, 0), 1)
+        ridge_lags = np.empty(cells, np.int32) if want_ridge else None
+        ridge_peaks = np.empty(cells, np.float32) if want_ridge else None
+        ms = C.c_float(0)
+        self._count("xcorr_caf")
+        self._check(self._lib.gj_xcorr_caf_u8(
+            self._ctx, ptrs, len(ins), n, flat.ctypes.data_as(C.POINTER(C.c_int32)), npairs, bin_first, n_bins, out,
+            ridge_lags.ctypes.data_as(C.POINTER(C.c_int32)) if want_ridge else None,
+            ridge_peaks.ctypes.data_as(C.POINTER(C.c_float)) if want_ridge else None, C.byref(ms)))
+        self.last_kernel_ms = ms.value
+        hz = xcorr_bin_hz(n, fs)
+        res = [CafPeak(int(r.lag), int(r.bin), r.bin * hz, float(r.peak), float(r.margin_lag), float(r.margin_bin))
+               for r in out[:npairs]]
+        if want_ridge:
+            return res, ridge_lags.reshape(npairs, n_bins), ridge_peaks.reshape(npairs, n_bins)
+        return res
+
     # ------------------------------------------------------------------ device pointers
     def chunk_count(self, nbytes: int, chunk_bytes: int) -> int:
         return self._lib.gj_chunk_count(nbytes, chunk_bytes)
@@ -746,6 +813,31 @@ class Device:
             self._ctx, ptrs, sizes, n_ant, _ptr(d_starts), n_samples,
             flat.ctypes.data_as(C.POINTER(C.c_int32)), flat.size // 2, _ptr(d_lags), _ptr(d_peaks),
             _ptr(d_margins) or None))
+
+    def xcorr_caf_workspace(self, n_ant: int, n_samples: int, n_pairs: int, n_bins: int, bins_per_launch: int = 0) -> int:
+        return self._lib.gj_xcorr_caf_workspace(self._ctx, n_ant, n_samples, n_pairs, n_bins, bins_per_launch)
+
+    def xcorr_caf_dev(self, d_iqs, nbytes_list, d_starts, n_samples, pairs, bin_first, n_bins, d_out, d_bin_lags=None,
+                      d_bin_peaks=None, bins_per_launch=0):
+        """gj_xcorr_caf_dev: ``d_out`` receives one gj_caf_result (24 bytes) per pair, the optional ridge arrays
+        [n_pairs][n_bins] int32 / float32.  Enqueues and returns."""
+        n_ant = len(d_iqs)
+        ptrs = (C.c_void_p * n_ant)(*[_ptr(p) for p in d_iqs])
+        sizes = (C.c_size_t * n_ant)(*[int(b) for b in nbytes_list])
+        flat = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1))
+        self._check(self._lib.gj_xcorr_caf_dev(
+            self._ctx, ptrs, sizes, n_ant, _ptr(d_starts), n_samples, flat.ctypes.data_as(C.POINTER(C.c_int32)),
+            flat.size // 2, int(bin_first), int(n_bins), int(bins_per_launch), _ptr(d_out), _ptr(d_bin_lags) or None,
+            _ptr(d_bin_peaks) or None))
+
+    def xcorr_caf_slots_dev(self, d_slots, slot_stride, n_ant, n_samples, pairs, bin_first, n_bins, d_out, d_bin_lags=None,
+                            d_bin_peaks=None, bins_per_launch=0):
+        """gj_xcorr_caf_slots_dev: the same over an array of TDOA slots."""
+        flat = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1))
+        self._check(self._lib.gj_xcorr_caf_slots_dev(
+            self._ctx, _ptr(d_slots), slot_stride, n_ant, n_samples, flat.ctypes.data_as(C.POINTER(C.c_int32)),
+            flat.size // 2, int(bin_first), int(n_bins), int(bins_per_launch), _ptr(d_out), _ptr(d_bin_lags) or None,
+            _ptr(d_bin_peaks) or None))
 
     def pack_result_dev(self, n_chunks, d_power, d_stats, d_amp, d_onset, d_psd, rows, nperseg, rank, n_pairs,
                         pair_capacity, d_pairs, d_lags, d_peaks, d_margins, d_out):

@@ -124,6 +124,12 @@ class SynthParams(C.Structure):
                 ("jam_k", C.c_int32), ("dc_i_q8", C.c_int32), ("dc_q_q8", C.c_int32)]
 
 
+class CafResult(C.Structure):
+    """gj_caf_result: one pair of the cross-ambiguity search (include/gpsjam.h)."""
+    _fields_ = [("lag", C.c_int32), ("bin", C.c_int32), ("peak", C.c_float), ("margin_lag", C.c_float),
+                ("margin_bin", C.c_float), ("reserved", C.c_float)]
+
+
 GJ_CP_ODD_CHUNK_ZERO = 1
 GJ_WELCH_SHIFT = 1
 GJ_MAX_ANTENNAS = 16
@@ -131,6 +137,7 @@ GJ_LAG_INVALID = -(1 << 31)
 GJ_SLOT_HEADER = 16
 GJ_COMM_ID_BYTES = 128
 GJ_VERSION = 150
+GJ_CAF_MAX_BINS = 4096
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
 _pf, _psz = C.POINTER(C.c_float), C.POINTER(C.c_size_t)
@@ -223,6 +230,12 @@ SIGNATURES = {
     "gj_comm_bcast_dev": (_i, [_vp, _vp, _sz, _i]),
     "gj_comm_destroy": (_i, [_vp]),
     "gj_xcorr_workspace": (_sz, [_vp, _i, _sz, _i]),
+    "gj_xcorr_fft_len": (_sz, [_sz]),
+    "gj_xcorr_caf_dev": (_i, [_vp, C.POINTER(_vp), _psz, _i, _vp, _sz, C.POINTER(C.c_int32), _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gj_xcorr_caf_slots_dev": (_i, [_vp, _vp, _sz, _i, _sz, C.POINTER(C.c_int32), _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gj_xcorr_caf_u8": (_i, [_vp, C.POINTER(_vp), _i, _sz, C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(CafResult),
+                             C.POINTER(C.c_int32), _pf, _pf]),
+    "gj_xcorr_caf_workspace": (_sz, [_vp, _i, _sz, _i, _i, _i]),
     "gj_pack_result_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gj_synth_u8_dev": (_i, [_vp, C.POINTER(SynthParams), C.c_int64, _sz, _vp]),
 }

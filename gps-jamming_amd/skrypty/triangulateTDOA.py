@@ -36,6 +36,9 @@ DETECTION_WINDOW_SIZE = 1000
 DETECTION_THRESHOLD_FACTOR = 50.0
 CORRELATION_SLICE_SIZE = 50000
 SPEED_OF_LIGHT = 299792458
+# Half-width in Hz of the receiver frequency-offset search (not in the reference, whose two captures share a clock).
+# 0: off, the script is the reference's.  Dongles on their own oscillators: e.g. 1000.0 (0.6 ppm at L1).
+FREQ_SEARCH_HZ = 0.0
 
 
 class IQCapture:
@@ -185,6 +188,28 @@ def correlation_lag(signal1_slice, signal0_slice):
     return k - (len(signal0_slice) - 1), float(np.abs(corr[k]))
 
 
+def correlation_lag_offset(signal1_slice, signal0_slice, max_offset_hz):
+    """correlation_lag for receivers that do not share a clock: the lag is searched together with the frequency offset
+    of antenna 1 against antenna 0 within +-max_offset_hz, in steps of SAMPLE_RATE / L (L: the correlation's FFT
+    length, gpsjam.xcorr_fft_len).  Returns (lag, peak, offset_hz)."""
+    r1, r0 = _raw_of(signal1_slice), _raw_of(signal0_slice)
+    if r1 is None or r0 is None or r1.size != r0.size:
+        raise TypeError("correlation_lag_offset expects two equal-length slices of load_iq_data captures")
+    res = gpsjam.default_device().xcorr_caf([r0, r1], [(0, 1)], max_offset_hz=float(max_offset_hz), fs=SAMPLE_RATE)[0]
+    if res.margin_lag >= LAG_NEAR_TIE:
+        return res.lag, res.peak, res.offset_hz
+    # as in correlation_lag: the reference's own call decides, here on the slice rotated by the winning bin
+    near_tie_events.append(("lag", float(res.margin_lag)))
+    _log.warning("lag decided inside the rounding of a complex64 FFT (peak margin %.2e, bin %d): scipy.signal.correlate "
+                 "evaluated on the host", res.margin_lag, res.bin)
+    from scipy import signal
+    n = len(signal0_slice)
+    rot = np.exp(-2j * np.pi * res.bin * np.arange(n) / gpsjam.xcorr_fft_len(n))
+    corr = signal.correlate((np.asarray(signal1_slice) * rot).astype(np.complex64), np.asarray(signal0_slice), mode='full')
+    k = int(np.argmax(np.abs(corr)))
+    return k - (n - 1), float(np.abs(corr[k])), res.offset_hz
+
+
 def bearing_from_lag(lag_samples, ant0_pos=ANT0_POS, ant1_pos=ANT1_POS, sample_rate=SAMPLE_RATE):
     """Scalar geometry of reference :92-119 (including its baseline-angle expression, :114).
     Returns a dict, or a dict with 'error' when the geometry is impossible."""
@@ -233,8 +258,13 @@ def main(file0=FILE_ANT0, file1=FILE_ANT1):
     print(f"\nSygnały wyrównane. Przetwarzanie wycinka {CORRELATION_SLICE_SIZE} próbek.")
 
     print("Obliczanie korelacji wzajemnej na wycinkach sygnału...")
-    lag_samples, _ = correlation_lag(signal1_slice, signal0_slice)
+    if FREQ_SEARCH_HZ > 0:
+        lag_samples, _, offset_hz = correlation_lag_offset(signal1_slice, signal0_slice, FREQ_SEARCH_HZ)
+    else:
+        lag_samples, _ = correlation_lag(signal1_slice, signal0_slice)
     print(f"Znaleziono maksymalną korelację przy przesunięciu {lag_samples} próbek.")
+    if FREQ_SEARCH_HZ > 0:
+        print(f"Oszacowane przesunięcie częstotliwości odbiornika 1 względem 0: {offset_hz:.1f} Hz")
 
     geo = bearing_from_lag(lag_samples)
     print(f"Różnica czasu dotarcia (TDOA): {geo['tdoa'] * 1e9:.2f} ns")

@@ -395,6 +395,52 @@ int gj_xcorr_slots_dev(gj_ctx* ctx, const uint8_t* d_slots, size_t slot_stride, 
                        size_t n_samples, const int32_t* pairs, int n_pairs, int32_t* d_lags,
                        float* d_peaks, float* d_margins);
 
+/* ------------------------------------------------- cross-ambiguity search ------------ */
+/* K5 for receivers that do NOT share a clock (one oscillator per dongle): the lag is searched together
+ * with the frequency offset between the two receivers.  For a slice length n, L = gj_xcorr_fft_len(n) is
+ * K5's FFT length (the power of two >= 2n-1, at least 65536) and one BIN is fs / L Hz.  For a pair (i, j)
+ * and an integer bin b
+ *     x_j^(b)[t] = x_j[t] * exp(-2 pi i b t / L),  t = 0 .. n-1 from the start of the slice
+ *     c_b        = correlate(x_j^(b), x_i, 'full')      (skrypty/triangulateTDOA.py:86)
+ * and the pair's result is the (b, m) with the largest |c_b[m]| over b = bin_first .. bin_first+n_bins-1,
+ * lag = m - (n-1) as in K5.  Positive b: receiver j sees the source b*fs/L Hz higher than receiver i.
+ * Ties: the larger value, then the earlier bin of the range, then the smaller m (numpy's first maximum
+ * inside a bin, as K5).  x is K5's unpacking, (I - offset) + j(Q - offset), un-normalised.
+ * The slice is zero-padded to L, so the rotation is an exact shift of the spectrum; every antenna is
+ * transformed once per call and only product, inverse transform and arg-max repeat per (pair, bin).
+ * With n_bins = 1, bin_first = 0 lag, peak and margin_lag equal gj_xcorr_lags_dev's bit for bit.
+ *
+ * Arguments as gj_xcorr_lags_dev / gj_xcorr_slots_dev / gj_xcorr_lags_u8.  n_bins >= 1 and every |b| < L/2,
+ * else GJ_ERR_INVALID; more than GJ_CAF_MAX_BINS bins in one call: GJ_ERR_UNSUPPORTED.  Bins run in batches
+ * of bins_per_launch (0 = a default sized to keep a batch's intermediate buffers in the Infinity Cache; a
+ * request is clipped to what the arrival counters hold, 688 / n_pairs); the results do not depend on it.
+ * d_bin_lags / d_bin_peaks (optional, [n_pairs][n_bins]) receive the best lag and its |c| of EVERY bin:
+ * the ridge of the surface.  The *_dev calls enqueue and return; they allocate nothing when
+ * gj_xcorr_caf_workspace bytes were reserved (gj_reserve), and a refused call enqueues nothing. */
+#define GJ_CAF_MAX_BINS 4096
+typedef struct gj_caf_result {
+    int32_t lag;        /* GJ_LAG_INVALID if an antenna of the pair is invalid */
+    int32_t bin;        /* the winning bin b */
+    float peak;         /* max |c| over the searched surface */
+    float margin_lag;   /* 1 - runner-up/peak among the OTHER lags of the winning bin (K5's margin) */
+    float margin_bin;   /* 1 - (largest per-bin peak of any OTHER bin)/peak; 1 when n_bins == 1 */
+    float reserved;
+} gj_caf_result;
+size_t gj_xcorr_fft_len(size_t n_samples); /* L; pure host arithmetic, no context (0 for n_samples 0) */
+int gj_xcorr_caf_dev(gj_ctx* ctx, const uint8_t* const* d_iq, const size_t* nbytes, int n_ant,
+                     const int64_t* d_starts, size_t n_samples, const int32_t* pairs, int n_pairs,
+                     int bin_first, int n_bins, int bins_per_launch, gj_caf_result* d_out,
+                     int32_t* d_bin_lags, float* d_bin_peaks);
+int gj_xcorr_caf_slots_dev(gj_ctx* ctx, const uint8_t* d_slots, size_t slot_stride, int n_ant,
+                           size_t n_samples, const int32_t* pairs, int n_pairs, int bin_first, int n_bins,
+                           int bins_per_launch, gj_caf_result* d_out, int32_t* d_bin_lags,
+                           float* d_bin_peaks);
+int gj_xcorr_caf_u8(gj_ctx* ctx, const uint8_t* const* slices, int n_ant, size_t n_samples,
+                    const int32_t* pairs, int n_pairs, int bin_first, int n_bins, gj_caf_result* out,
+                    int32_t* bin_lags, float* bin_peaks, float* kernel_ms);
+size_t gj_xcorr_caf_workspace(gj_ctx* ctx, int n_ant, size_t n_samples, int n_pairs, int n_bins,
+                              int bins_per_launch);
+
 /* ------------------------------------------------- per-stream result vector ---------- */
 /* What one rank sends to rank 0 (gpsjam/sharded.py):
  * double[40 + n_chunks + nperseg + 5*pair_capacity] =
