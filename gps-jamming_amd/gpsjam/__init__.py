@@ -26,7 +26,8 @@ from ._ffi import (AmpStats, GpsJamError, GpsJamLibraryError, Onset, SynthParams
 
 __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "device_count",
            "library_path", "as_u8", "default_device", "read_capture", "resident_capture",
-           "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range"]
+           "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
+           "ridge_frames"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -159,6 +160,54 @@ class CafPeak(NamedTuple):
     peak: float
     margin_lag: float
     margin_bin: float
+
+
+RIDGE_DTYPE = np.dtype([("total", np.float32), ("peak", np.float32), ("second", np.float32), ("peak_bin", np.int32)])
+
+
+def ridge_frames(nbytes: int, first_sample: int, nfft: int, hop: int) -> int:
+    """Whole frames of nfft points that fit from first_sample at the given hop (gj_ridge_frames); 0 when none do."""
+    if min(int(nbytes), int(first_sample), int(hop)) < 0 or not -2 ** 31 <= int(nfft) < 2 ** 31:
+        return 0
+    return int(_ffi.load().gj_ridge_frames(int(nbytes), int(first_sample), int(nfft), int(hop)))
+
+
+class Ridge:
+    """The short-time spectral ridge of a capture (``Device.ridge``; gj_ridge_frame, include/gpsjam.h): per frame the
+    total power, the peak |X[k]|^2, the largest value outside the guard band around the peak and the peak's bin, as
+    the numpy structured array ``records`` (RIDGE_DTYPE) plus the geometry they were computed with.  Frame f starts
+    at sample ``first_sample + f * hop``.  ``ridge[a:b]`` is the Ridge of those frames."""
+
+    def __init__(self, records, nfft: int, hop: int, first_sample: int = 0, guard: int = 2):
+        self.records = np.ascontiguousarray(records, dtype=RIDGE_DTYPE).reshape(-1)
+        self.nfft, self.hop, self.first_sample, self.guard = int(nfft), int(hop), int(first_sample), int(guard)
+
+    def __len__(self) -> int:
+        return self.records.size
+
+    def __getitem__(self, key) -> "Ridge":
+        if not isinstance(key, slice):
+            raise TypeError("a Ridge is sliced by frame: ridge[a:b]")
+        start, _, step = key.indices(len(self))
+        if step != 1:
+            raise ValueError("a Ridge keeps consecutive frames: the step must be 1")
+        return Ridge(self.records[key], self.nfft, self.hop, self.first_sample + start * self.hop, self.guard)
+
+    total = property(lambda self: self.records["total"])
+    peak = property(lambda self: self.records["peak"])
+    second = property(lambda self: self.records["second"])
+    peak_bin = property(lambda self: self.records["peak_bin"])
+
+    @property
+    def concentration(self) -> np.ndarray:
+        """peak / total: the share of each frame's power in its peak bin (0 for an empty frame)."""
+        t = self.total.astype(np.float64)
+        return np.divide(self.peak, t, out=np.zeros(t.shape), where=t > 0)
+
+    def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
+        """Signed frequency of peak_bin: bins from nfft/2 on are negative frequencies."""
+        k = self.peak_bin.astype(np.int64)
+        return np.where(k >= self.nfft // 2, k - self.nfft, k) * (float(fs) / self.nfft)
 
 
 def as_u8(raw) -> np.ndarray:
@@ -705,7 +754,39 @@ class Device:
             return res, ridge_lags.reshape(npairs, n_bins), ridge_peaks.reshape(npairs, n_bins)
         return res
 
+    def ridge(self, raw, nfft: int = 256, hop: Optional[int] = None, first_sample: int = 0,
+              n_frames: Optional[int] = None, guard: int = 2) -> Ridge:
+        """Short-time spectral ridge (gj_ridge_dev): per frame of nfft points, hop samples apart (default nfft // 2),
+        where the spectral peak is and how much of the frame's power it holds; n_frames defaults to all that fit.
+        ``raw``: host bytes (uploaded once, like a ``Capture``) or a resident ``Capture``.  16 bytes per frame come back."""
+        hop = int(nfft) // 2 if hop is None else int(hop)
+        own = None if isinstance(raw, Capture) else Capture(self, raw)
+        cap = raw if own is None else own
+        try:
+            if not cap.ptr and cap.nbytes:
+                raise ValueError("the capture has been freed")
+            if n_frames is None:
+                n_frames = ridge_frames(cap.nbytes, first_sample, nfft, hop)
+                if n_frames == 0 and 16 <= int(nfft) <= 4096 and hop >= 1:
+                    return Ridge(np.empty(0, RIDGE_DTYPE), nfft, hop, first_sample, guard)
+            self._count("ridge")
+            out = DevBuf(self, max(int(n_frames), 1) * RIDGE_DTYPE.itemsize)
+            try:
+                self.ridge_dev(cap, cap.nbytes, first_sample, nfft, hop, n_frames, guard, out)
+                rec = out.download(RIDGE_DTYPE, int(n_frames))
+            finally:
+                out.free()
+        finally:
+            if own is not None:
+                own.free()
+        return Ridge(rec, nfft, hop, first_sample, guard)
+
     # ------------------------------------------------------------------ device pointers
+    def ridge_dev(self, d_iq, nbytes, first_sample, nfft, hop, n_frames, guard, d_out):
+        """gj_ridge_dev: n_frames records of 16 bytes (RIDGE_DTYPE) into d_out, on the context's stream."""
+        self._check(self._lib.gj_ridge_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(nfft), int(hop),
+                                           int(n_frames), int(guard), _ptr(d_out)))
+
     def chunk_count(self, nbytes: int, chunk_bytes: int) -> int:
         return self._lib.gj_chunk_count(nbytes, chunk_bytes)
 

@@ -130,6 +130,11 @@ class CafResult(C.Structure):
                 ("margin_bin", C.c_float), ("reserved", C.c_float)]
 
 
+class RidgeFrame(C.Structure):
+    """gj_ridge_frame: one frame of the short-time spectral ridge (include/gpsjam.h)."""
+    _fields_ = [("total", C.c_float), ("peak", C.c_float), ("second", C.c_float), ("peak_bin", C.c_int32)]
+
+
 GJ_CP_ODD_CHUNK_ZERO = 1
 GJ_WELCH_SHIFT = 1
 GJ_MAX_ANTENNAS = 16
@@ -185,6 +190,8 @@ SIGNATURES = {
     "gj_welch_timed_dev": (_i, [_vp, _vp, _sz, _sz, _i, _d, _i, _vp, _vp, C.POINTER(_f), C.POINTER(_f)]),
     "gj_welch_u8": (_i, [_vp, _vp, _sz, _sz, _i, _d, _i, _vp, _vp, _sz, _psz, _pf]),
     "gj_welch_workspace": (_sz, [_vp, _sz, _sz, _i]),
+    "gj_ridge_frames": (_sz, [_sz, _sz, _i, _sz]),
+    "gj_ridge_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _sz, _i, _vp]),
     "gj_byte_histogram_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),
     "gj_amp_stats_dev": (_i, [_vp, _vp, _sz, _f, _vp]),
     "gj_amp_stats_u8": (_i, [_vp, _vp, _sz, _f, C.POINTER(AmpStats), _pf]),

@@ -214,6 +214,36 @@ int gj_welch_timed_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t c
 /* workspace bytes gj_welch_dev needs for this input (for gj_reserve) */
 size_t gj_welch_workspace(gj_ctx* ctx, size_t nbytes, size_t chunk_samples, int nperseg);
 
+/* ------------------------------------------------- short-time spectral ridge -------- */
+/* Per short frame: where the spectral peak is and how much of the frame's power it holds -- the time series that tells
+ * the reference simulator's four interferers apart (simulate/frontend/jammers/: cwJammer.py, chirpJammer.py,
+ * pulsedJammer.py, broadbandJammer.py; gpsjam/classify.py reads it).  For frame f = 0 .. n_frames-1, with
+ * s_f = first_sample + f*hop and N = nfft:
+ *
+ *   x[t]    = ((I_t - offset) + j(Q_t - offset)) * scale      K2's unpacking; honours gj_set_unpack
+ *   w[n]    = 0.5 - 0.5 cos(2 pi n / N)                        periodic Hann, K2's table
+ *   X_f[k]  = sum_{n<N} w[n] x[s_f + n] exp(-2 pi i k n / N)   NO mean removal, NO 1/(fs sum w^2) scaling
+ *   P_f[k]  = |X_f[k]|^2
+ *
+ * (no mean removal: pulsedJammer.py's carrier sits at 0 Hz, and a detrend would erase it).
+ * nfft: a power of two, 16..4096 (GJ_ERR_UNSUPPORTED otherwise).  hop >= 1, otherwise arbitrary (odd, larger than nfft,
+ * not a divisor of it); first_sample may be odd; 0 <= guard and 2*guard + 1 < nfft.  n_frames == 0, a last frame that
+ * runs past the capture, a null or odd d_iq, a d_out that is not 4-byte aligned: GJ_ERR_INVALID.  A refused call
+ * enqueues nothing.  Needs no workspace.
+ * Determinism: one transform group computes one frame and `total` is summed in an order that depends on nfft alone, so
+ * frame f of a call is bit-identical to frame f-k of the same call started at first_sample + k*hop, and two identical
+ * calls give identical bytes. */
+typedef struct gj_ridge_frame {   /* 16 bytes */
+    float total;      /* sum_k P_f[k] */
+    float peak;       /* max_k P_f[k] */
+    float second;     /* max P_f[k] over bins whose circular distance to peak_bin is > guard; 0 if none */
+    int32_t peak_bin; /* 0..N-1 in FFT order (k >= N/2 is negative frequency); equal values: smallest k */
+} gj_ridge_frame;
+/* whole frames that fit: pure host arithmetic, no context; 0 for an impossible geometry (nfft < 1, hop < 1, no room) */
+size_t gj_ridge_frames(size_t nbytes, size_t first_sample, int nfft, size_t hop);
+int gj_ridge_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, int nfft, size_t hop,
+                 size_t n_frames, int guard, gj_ridge_frame* d_out /* [n_frames] */);
+
 /* raw-byte histogram of every `stride`-th byte (widmo_plot.py:35,85: stride 100,
  * 256 bins).  Strided per chunk exactly like raw_chunk[::100]. */
 int gj_byte_histogram_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t chunk_samples,
