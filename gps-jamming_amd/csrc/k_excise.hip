@@ -1,0 +1,298 @@
+// Frequency-domain interference excision (gfx950): windowed 50 %-overlap FFT, per-bin threshold mask, inverse FFT and
+// overlap-add back to uint8 I/Q -- gj_excise_dev / gj_excise_frames of include/gpsjam.h, which states the definition.
+// The classical excisor of GPS receivers; simulate/frontend/jammers/ of the reference defines the interferers it has
+// to remove.  The project's first kernel whose output is a capture.
+//
+// The transform is K2's (k_welch.hip), the per-frame shape k_ridge.hip's: one 256-thread workgroup holds 4096 / N
+// transform groups of N / 16 threads, every thread pulls its 16 samples from the uint8 stream, applies unpack and the
+// periodic Hann window of K2's table and runs the register-resident Stockham passes of fft_core.h.  What differs:
+//   * frames hop by N / 2, and a transform group owns a RUN of consecutive frames that it walks in order.  After the
+//     last pass a thread holds points jl + TF s (TF = N / 16); its slots s and s + 8 are N / 2 apart, so the
+//     overlap-add is prev[s + 8] + cur[s] in registers and eight c2 are carried from frame to frame: no LDS, no atomics;
+//   * a run is primed by transforming the frame in front of it once more, writing nothing: that frame's record and
+//     bytes belong to the run before.  Run boundaries come from the geometry alone (excise_launch);
+//   * the inverse transform is the forward passes on the conjugate, IFFT(X) = conj(FFT(conj(X))) / N.  The output
+//     pattern of the forward transform (jl + TF s) is the input pattern pass 0 wants, so the mask and the second
+//     transform run on the registers as they are, with the same twiddle registers;
+//   * 4096 points run the generic exchange schedule of fft_core.h, not X4096: X4096 changes the thread's role between
+//     pass 0 and the end, which the register-to-register hand-over above does not survive without one more exchange;
+//   * thr[jl + TF s] is constant per thread: 16 registers, loaded once;
+//   * per frame the group reduces total, removed and the excised count to one 16-byte record with the DPP / LDS
+//     pattern of ridge_kernel.
+// Determinism: a frame's spectrum, mask and inverse are computed from that frame's bytes alone by the same
+// instructions whichever group, run or launch computes it (the priming pass IS the loop body), every sum runs in an
+// order fixed by N, and an output sample is prev + cur of its two frames: a call started k N / 2 samples later
+// reproduces the interior bytes and the shared records bit for bit.
+//
+// The first half frame and the tail behind the last whole hop are copied from the input by a second small launch.
+//
+// This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it.
+#include "gj_common.h"
+
+namespace gj {
+
+extern const float* window_table(gj_ctx* ctx, int n);   // api.hip: K2's periodic Hann tables
+
+template <int N>
+struct ExciseCfg {
+    // ~160 live registers (32 data, 60 twiddles, 16 each for window, thresholds, carry and prefetch): two workgroups
+    // per CU leave the compiler 256 VGPRs, three (168) would spill; the one- and two-pass sizes hold no second
+    // twiddle set but keep the same bound (profiles/NOTES_excise.md has the compiler's figures)
+    static constexpr int min_waves = 2;
+    static constexpr int min_run = 4;   // frames per run at least (but for short calls): bounds the priming overhead at 25 %
+};
+
+struct ExciseGeom {
+    unsigned long long first_sample, n_frames, per_run;
+    float offset;    // offset of the unpack convention
+    float scale2;    // scale^2: the transform runs on u8 - offset, the powers are scaled to the units of gj_ridge_dev
+};
+
+template <int G>
+__device__ __forceinline__ float group_sum_f(float v) {
+#define GJ_DPP_F(x, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, 0xf, 0xf, false))
+    if constexpr (G >= 2) v += GJ_DPP_F(v, 0xB1);     // quad_perm [1,0,3,2]
+    if constexpr (G >= 4) v += GJ_DPP_F(v, 0x4E);     // quad_perm [2,3,0,1]
+    if constexpr (G >= 8) v += GJ_DPP_F(v, 0x141);    // row_half_mirror
+    if constexpr (G >= 16) v += GJ_DPP_F(v, 0x140);   // row_mirror
+#undef GJ_DPP_F
+    if constexpr (G >= 32) v += __shfl_xor(v, 16, 64);
+    if constexpr (G >= 64) v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+// the exchange barrier of k_ridge.hip / K2: a wavefront fence while a transform group lies inside one wave
+template <int N>
+__device__ __forceinline__ void excise_exchange_sync() {
+    if constexpr (N / 16 <= 64) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    } else {
+        __syncthreads();
+    }
+}
+
+template <int N, int PASS>
+__device__ __forceinline__ void excise_passes(c2 (&v)[16], cf* lds, int base, int jl, const c2 (&tw)[3][15], const InnerTw& ktw) {
+    fft_pass<N, PASS, true>(v, tw[PASS], ktw);
+    if constexpr (PASS + 1 < fft_npass(N)) {
+        lds_scatter<N, PASS>(v, lds, base, jl);
+        excise_exchange_sync<N>();
+        lds_gather<N>(v, lds, base, jl);
+        excise_exchange_sync<N>();
+        excise_passes<N, PASS + 1>(v, lds, base, jl, tw, ktw);
+    }
+}
+
+template <int N>
+__global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise_kernel(const uint8_t* __restrict__ iq, ExciseGeom g,
+                                                                                        const cf* __restrict__ twtab,
+                                                                                        const float* __restrict__ wintab,
+                                                                                        const float* __restrict__ thr_tab,
+                                                                                        uint8_t* __restrict__ out,
+                                                                                        gj_excise_frame* __restrict__ frames) {
+    constexpr int TF = N / 16, B = kBlockPoints / N, NP = fft_npass(N), H = N / 2;
+    constexpr int WPF = (TF >= 64) ? TF / 64 : 1;   // waves per transform
+    __shared__ cf lds0[NP > 1 ? lds_span(kBlockPoints) : 1];
+    // wave results of a transform group that spans waves (2048, 4096 points), one array per reduction as in ridge_kernel
+    constexpr int RB = WPF > 1 ? B : 1;
+    __shared__ float red_tot[RB][WPF], red_rem[RB][WPF], red_cnt[RB][WPF];
+    static_assert(TF > 64 || (64 % TF == 0 && WPF == 1 && kBlockThreads % 64 == 0 && B * TF == kBlockThreads),
+                  "the wave-fence exchange needs a transform group inside one wave");
+    const int tid = threadIdx.x;
+    const int b = (TF >= 64) ? __builtin_amdgcn_readfirstlane(tid / TF) : tid / TF;
+    const int jl = tid % TF;   // input points, bins and output points of this thread: jl + TF s
+
+    const InnerTw ktw = inner_twiddles();
+    c2 tw[3][15];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int k = 0; k < 15; ++k) tw[p][k] = make_c2(1.f, 0.f);
+    if constexpr (NP > 1) load_twiddles<N, 1>(tw[1], twtab, jl);
+    if constexpr (NP > 2) load_twiddles<N, 2>(tw[2], twtab, jl);
+
+    c2 wp[8];   // (w[2i], w[2i+1]) share a register pair, op_sel picks the half
+#pragma unroll
+    for (int s = 0; s < 8; ++s) wp[s] = make_c2(wintab[jl + TF * (2 * s)], wintab[jl + TF * (2 * s + 1)]);
+    float thr[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) thr[s] = thr_tab[jl + TF * s];
+    const c2 koff = make_c2(-g.offset, -g.offset);
+    constexpr float inv_n = 1.0f / (float)N;
+
+    // this group's run: frames [run_first, run_end); iteration 0 primes the carry with the frame in front of it.  Every
+    // group of the grid makes per_run + 1 iterations (the barriers of the large sizes are workgroup-wide, and lanes of
+    // one wave must stay together for the DPP steps); a frame index outside the call is clamped and writes nothing.
+    const long long last = (long long)g.n_frames - 1;
+    const long long run_first = (long long)(((unsigned long long)blockIdx.x * B + (unsigned)b) * g.per_run);
+    const long long run_end = run_first + (long long)g.per_run;
+    auto frame_base = [&](long long f) {
+        f = f < 0 ? 0 : (f > last ? last : f);
+        return iq + 2ull * (g.first_sample + (unsigned long long)f * H) + 2 * jl;
+    };
+    auto load_frame = [&](unsigned (&dst)[16], const uint8_t* p) {
+#pragma unroll
+        for (int s = 0; s < 16; ++s) dst[s] = *reinterpret_cast<const uint16_t*>(p + 2 * TF * s);
+    };
+
+    unsigned raw[16];   // the NEXT frame's samples are fetched while the current ones are transformed
+    load_frame(raw, frame_base(run_first - 1));
+    c2 carry[8];        // second half of the previous frame's inverse transform: y_{f-1}[jl + TF (s + 8)]
+#pragma unroll
+    for (int s = 0; s < 8; ++s) carry[s] = make_c2(0.f, 0.f);
+
+    for (long long f = run_first - 1; f < run_end; ++f) {
+        const bool owned = f >= run_first && f <= last;
+        c2 v[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const unsigned u = raw[s];
+            const c2 x = cadd(make_c2((float)(u & 255u), (float)((u >> 8) & 255u)), koff);   // exact: u8 minus a multiple of 0.5
+            v[s] = (s & 1) ? scale_hi(x, wp[s >> 1]) : scale_lo(x, wp[s >> 1]);
+        }
+        if (f + 1 < run_end) load_frame(raw, frame_base(f + 1));   // workgroup-uniform
+
+        excise_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
+
+        // this thread's bins jl + TF s: power, mask, conjugate for the way back
+        float tot = 0.f, rem = 0.f, cnt = 0.f;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            // no contraction here: the compiler otherwise fuses the scaling into the addition to `tot` (one rounding) but
+            // not into the selected addition to `rem` (two), and the two sum differently rounded values -- removed must
+            // equal total, bit for bit, when every bin is excised
+#pragma clang fp contract(off)
+            const float p = __builtin_fmaf(v[s].x, v[s].x, v[s].y * v[s].y) * g.scale2;
+            const bool cut = p > thr[s];   // strict; false for a NaN threshold
+            tot += p;
+            rem += cut ? p : 0.f;
+            cnt += cut ? 1.f : 0.f;        // at most 4096: exact in float
+            v[s] = cut ? make_c2(0.f, 0.f) : make_c2(v[s].x, -v[s].y);
+        }
+        constexpr int G = TF >= 64 ? 64 : TF;
+        tot = group_sum_f<G>(tot);
+        rem = group_sum_f<G>(rem);
+        cnt = group_sum_f<G>(cnt);
+        if constexpr (WPF > 1) {
+            const int wv = (tid >> 6) % WPF;
+            if ((tid & 63) == 0) { red_tot[b][wv] = tot; red_rem[b][wv] = rem; red_cnt[b][wv] = cnt; }
+            __syncthreads();
+            tot = red_tot[b][0]; rem = red_rem[b][0]; cnt = red_cnt[b][0];
+#pragma unroll
+            for (int k = 1; k < WPF; ++k) { tot += red_tot[b][k]; rem += red_rem[b][k]; cnt += red_cnt[b][k]; }
+        }
+        if (frames && owned && jl == 0) {   // one lane per transform group
+            gj_excise_frame r;
+            r.total = tot;
+            r.removed = rem;
+            r.n_excised = (int)cnt;
+            r.reserved = 0;
+            frames[f] = r;
+        }
+
+        excise_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
+
+        // y_f = conj(v) / N; samples [f H, (f + 1) H) of the range = previous frame's second half + this one's first
+        const bool store = owned && f >= 1;
+        uint8_t* dst = out + 2ull * ((unsigned long long)(f < 0 ? 0 : f) * H) + 2 * jl;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const float yi = fmaf(v[s].x, inv_n, carry[s].x) + g.offset;
+            const float yq = fmaf(-v[s].y, inv_n, carry[s].y) + g.offset;
+            carry[s] = make_c2(v[s + 8].x * inv_n, -v[s + 8].y * inv_n);
+            if (store) {
+                const unsigned ui = (unsigned)fminf(fmaxf(__builtin_rintf(yi), 0.f), 255.f);
+                const unsigned uq = (unsigned)fminf(fmaxf(__builtin_rintf(yq), 0.f), 255.f);
+                struct __attribute__((packed, aligned(1))) U16 { uint16_t v; };
+                reinterpret_cast<U16*>(dst + 2 * TF * s)->v = (uint16_t)(ui | (uq << 8));
+            }
+        }
+    }
+}
+
+// the first half frame [0, n_head) and the tail [tail_first, n_bytes) come back as they went in
+__global__ __launch_bounds__(256) void excise_edges_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
+                                                           unsigned long long n_head, unsigned long long tail_first,
+                                                           unsigned long long n_bytes) {
+    const unsigned long long n_tail = n_bytes - tail_first;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_head + n_tail;
+         i += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long at = i < n_head ? i : tail_first + (i - n_head);
+        out[at] = src[at];
+    }
+}
+
+template <int N>
+static void excise_launch(gj_ctx* ctx, const uint8_t* d_iq, ExciseGeom g, const float* d_thr, uint8_t* d_out, gj_excise_frame* d_frames) {
+    constexpr unsigned long long B = kBlockPoints / N;
+    // one round of transform groups; runs of equal length, the length from the frame count alone
+    const unsigned long long slots = (unsigned long long)ctx->num_cus * ExciseCfg<N>::min_waves * B;
+    unsigned long long per = (g.n_frames + slots - 1) / slots;
+    if (per < (unsigned long long)ExciseCfg<N>::min_run) per = ExciseCfg<N>::min_run;
+    if (per > g.n_frames) per = g.n_frames;
+    g.per_run = per;
+    const unsigned long long runs = (g.n_frames + per - 1) / per;
+    const unsigned grid = (unsigned)((runs + B - 1) / B);
+    hipLaunchKernelGGL(excise_kernel<N>, dim3(grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle, window_table(ctx, N),
+                       d_thr, d_out, d_frames);
+}
+
+}   // namespace gj
+
+using namespace gj;
+
+extern "C" {
+
+size_t gj_excise_frames(size_t n_samples, int nfft) {
+    if (nfft < 2 || n_samples < (size_t)nfft) return 0;
+    return (n_samples - (size_t)nfft) / ((size_t)nfft / 2) + 1;
+}
+
+int gj_excise_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples, int nfft,
+                  const float* d_threshold, uint8_t* d_out, gj_excise_frame* d_frames) {
+    if (!ctx) return GJ_ERR_INVALID;
+    Guard lock(ctx);
+    if (nfft < 16 || nfft > 4096 || (nfft & (nfft - 1))) return fail(ctx, GJ_ERR_UNSUPPORTED, "nfft must be a power of two in [16, 4096]");
+    if (!d_iq || !d_out || !d_threshold) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+    if (reinterpret_cast<uintptr_t>(d_iq) & 1) return fail(ctx, GJ_ERR_INVALID, "capture must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
+    const size_t total = nbytes / 2;
+    if (n_samples < (size_t)nfft) return fail(ctx, GJ_ERR_INVALID, "n_samples %zu is less than one frame of %d points", n_samples, nfft);
+    if (first_sample > total || n_samples > total - first_sample)
+        return fail(ctx, GJ_ERR_INVALID, "samples %zu .. +%zu run past the capture's %zu", first_sample, n_samples, total);
+    {   // frames read their neighbours: the output may not lie in the capture
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_iq), a1 = a0 + nbytes;
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + 2 * n_samples;
+        if (o0 < a1 && a0 < o1) return fail(ctx, GJ_ERR_INVALID, "d_out overlaps the capture");
+    }
+    ExciseGeom g;
+    g.first_sample = first_sample;
+    g.n_frames = gj_excise_frames(n_samples, nfft);
+    g.per_run = 0;
+    g.offset = 0.5f * (float)ctx->off2;
+    g.scale2 = (float)(ctx->scale * ctx->scale);
+    switch (nfft) {
+        case 16: excise_launch<16>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+        case 32: excise_launch<32>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+        case 64: excise_launch<64>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+        case 128: excise_launch<128>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+        case 256: excise_launch<256>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+        case 512: excise_launch<512>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+        case 1024: excise_launch<1024>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+        case 2048: excise_launch<2048>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+        default: excise_launch<4096>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
+    }
+    GJ_LAUNCH_CHECK(ctx);
+    const unsigned long long h2 = (unsigned long long)nfft;   // bytes of half a frame
+    const unsigned long long tail_first = g.n_frames * h2, n_bytes = 2ull * n_samples;
+    const unsigned long long edge = h2 + (n_bytes - tail_first);   // < 3 nfft bytes
+    hipLaunchKernelGGL(excise_edges_kernel, dim3((unsigned)((edge + 255) / 256)), dim3(256), 0, ctx->stream, d_iq + 2 * first_sample,
+                       d_out, h2, tail_first, n_bytes);
+    GJ_LAUNCH_CHECK(ctx);
+    return GJ_OK;
+}
+
+}   // extern "C"

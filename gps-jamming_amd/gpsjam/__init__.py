@@ -27,7 +27,7 @@ from ._ffi import (AmpStats, GpsJamError, GpsJamLibraryError, Onset, SynthParams
 __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "device_count",
            "library_path", "as_u8", "default_device", "read_capture", "resident_capture",
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
-           "ridge_frames"]
+           "ridge_frames", "EXCISE_DTYPE", "excise_frames"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -172,6 +172,16 @@ def ridge_frames(nbytes: int, first_sample: int, nfft: int, hop: int) -> int:
     return int(_ffi.load().gj_ridge_frames(int(nbytes), int(first_sample), int(nfft), int(hop)))
 
 
+EXCISE_DTYPE = np.dtype([("total", np.float32), ("removed", np.float32), ("n_excised", np.int32), ("reserved", np.int32)])
+
+
+def excise_frames(n_samples: int, nfft: int) -> int:
+    """Frames of the excisor over n_samples at nfft points, hop nfft // 2 (gj_excise_frames); 0 when none fits."""
+    if int(n_samples) < 0 or not -2 ** 31 <= int(nfft) < 2 ** 31:
+        return 0
+    return int(_ffi.load().gj_excise_frames(int(n_samples), int(nfft)))
+
+
 class Ridge:
     """The short-time spectral ridge of a capture (``Device.ridge``; gj_ridge_frame, include/gpsjam.h): per frame the
     total power, the peak |X[k]|^2, the largest value outside the guard band around the peak and the peak's bin, as
@@ -296,6 +306,17 @@ class Capture:
         self.dev, self.ptr, self.nbytes, self.path = dev, int(ptr or 0), int(nbytes), path
         self.results, self.ingest_ms, self.results_unpack = {}, None, None
         Capture._count()
+        return self
+
+    @classmethod
+    def from_device(cls, dev: "Device", buf: "DevBuf", nbytes: Optional[int] = None) -> "Capture":
+        """A Capture that takes over a device allocation a kernel has filled (``Device.excise``): no host->device pass,
+        so ``uploads`` does not count it.  ``buf`` gives its memory up; the Capture frees it."""
+        self = cls.__new__(cls)
+        self.dev, self.ptr, self.path = dev, int(buf.ptr), None
+        self.nbytes = int(buf.nbytes if nbytes is None else nbytes)
+        self.results, self.ingest_ms, self.results_unpack = {}, None, None
+        buf.ptr = 0
         return self
 
     def __init__(self, dev: "Device", source, offset: int = 0, max_bytes: int = 0):
@@ -781,7 +802,50 @@ class Device:
                 own.free()
         return Ridge(rec, nfft, hop, first_sample, guard)
 
+    def excise(self, raw, threshold, nfft: int = 1024, first_sample: int = 0, n_samples: Optional[int] = None):
+        """Frequency-domain excision (gj_excise_dev): samples first_sample .. + n_samples of ``raw`` (default: to the
+        end) with every bin of every nfft-point frame whose power exceeds ``threshold[k]`` taken out.  ``raw``: host
+        bytes (uploaded once) or a resident ``Capture``; ``threshold``: nfft floats in FFT order, in the units of
+        ``ridge`` (+inf: never, negative: always), or a device buffer that holds them.  Returns
+        ``(cleaned, records)``: the cleaned range as a resident ``Capture`` of its own (the caller frees it) and one
+        EXCISE_DTYPE record per frame."""
+        nfft, first_sample = int(nfft), int(first_sample)
+        own = None if isinstance(raw, Capture) else Capture(self, raw)
+        cap = raw if own is None else own
+        d_thr = d_out = d_rec = None
+        try:
+            if not cap.ptr and cap.nbytes:
+                raise ValueError("the capture has been freed")
+            if n_samples is None:
+                n_samples = max(0, cap.nsamples - first_sample)
+            n_samples = int(n_samples)
+            frames = excise_frames(n_samples, nfft)
+            if isinstance(threshold, (DevBuf, int)) or hasattr(threshold, "data_ptr"):
+                thr = threshold
+            else:
+                host = np.ascontiguousarray(threshold, dtype=np.float32).reshape(-1)
+                if host.size != nfft:
+                    raise ValueError(f"threshold holds {host.size} values, nfft is {nfft}")
+                thr = d_thr = DevBuf(self, 4 * nfft).upload(host)
+            self._count("excise")
+            d_out = DevBuf(self, max(2 * n_samples, 1))
+            d_rec = DevBuf(self, max(frames, 1) * EXCISE_DTYPE.itemsize)
+            self.excise_dev(cap, cap.nbytes, first_sample, n_samples, nfft, thr, d_out, d_rec)
+            rec = d_rec.download(EXCISE_DTYPE, frames)
+            cleaned, d_out = Capture.from_device(self, d_out, 2 * n_samples), None
+        finally:
+            for b in (d_thr, d_rec, d_out, own):
+                if b is not None:
+                    b.free()
+        return cleaned, rec
+
     # ------------------------------------------------------------------ device pointers
+    def excise_dev(self, d_iq, nbytes, first_sample, n_samples, nfft, d_threshold, d_out, d_frames=None):
+        """gj_excise_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 16-byte record (EXCISE_DTYPE) per
+        frame into d_frames, on the context's stream."""
+        self._check(self._lib.gj_excise_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples), int(nfft),
+                                            _ptr(d_threshold), _ptr(d_out), _ptr(d_frames) or None))
+
     def ridge_dev(self, d_iq, nbytes, first_sample, nfft, hop, n_frames, guard, d_out):
         """gj_ridge_dev: n_frames records of 16 bytes (RIDGE_DTYPE) into d_out, on the context's stream."""
         self._check(self._lib.gj_ridge_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(nfft), int(hop),

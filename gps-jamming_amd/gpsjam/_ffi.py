@@ -135,6 +135,11 @@ class RidgeFrame(C.Structure):
     _fields_ = [("total", C.c_float), ("peak", C.c_float), ("second", C.c_float), ("peak_bin", C.c_int32)]
 
 
+class ExciseFrame(C.Structure):
+    """gj_excise_frame: one frame of the frequency-domain excisor (include/gpsjam.h)."""
+    _fields_ = [("total", C.c_float), ("removed", C.c_float), ("n_excised", C.c_int32), ("reserved", C.c_int32)]
+
+
 GJ_CP_ODD_CHUNK_ZERO = 1
 GJ_WELCH_SHIFT = 1
 GJ_MAX_ANTENNAS = 16
@@ -192,6 +197,8 @@ SIGNATURES = {
     "gj_welch_workspace": (_sz, [_vp, _sz, _sz, _i]),
     "gj_ridge_frames": (_sz, [_sz, _sz, _i, _sz]),
     "gj_ridge_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _sz, _i, _vp]),
+    "gj_excise_frames": (_sz, [_sz, _i]),
+    "gj_excise_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp]),
     "gj_byte_histogram_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),
     "gj_amp_stats_dev": (_i, [_vp, _vp, _sz, _f, _vp]),
     "gj_amp_stats_u8": (_i, [_vp, _vp, _sz, _f, C.POINTER(AmpStats), _pf]),

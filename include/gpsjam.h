@@ -244,6 +244,48 @@ size_t gj_ridge_frames(size_t nbytes, size_t first_sample, int nfft, size_t hop)
 int gj_ridge_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, int nfft, size_t hop,
                  size_t n_frames, int guard, gj_ridge_frame* d_out /* [n_frames] */);
 
+/* ------------------------------------------------- frequency-domain excision -------- */
+/* The windowed 50 %-overlap FFT excisor of GPS receivers: a cleaned capture, uint8 I/Q again, with every bin above its
+ * threshold taken out (the interferers of simulate/frontend/jammers/; gpsjam/mitigate.py builds the thresholds).  For a
+ * range of n_samples I/Q pairs starting at first_sample, with N = nfft, h = N/2 and frames f = 0 .. F-1 at
+ * s_f = first_sample + f*h:
+ *
+ *   F = gj_excise_frames(n_samples, nfft) = (n_samples - N) / h + 1   (0 if n_samples < N)
+ *
+ *   x[t]   = (I_t - offset) + j(Q_t - offset)          un-normalised; honours gj_set_unpack's offset
+ *   w[n]   = 0.5 - 0.5 cos(2 pi n / N)                 K2's periodic Hann table
+ *   X_f[k] = sum_n w[n] x[s_f + n] exp(-2 pi i k n / N)        no mean removal
+ *   P_f[k] = |X_f[k]|^2 * scale^2                      the units of gj_ridge_dev
+ *   M_f[k] = 0 if P_f[k] > thr[k] else 1               strict; thr = DEVICE float[N] in FFT order
+ *   y_f    = IFFT_N(M_f * X_f)                         with the 1/N
+ *   y[t]   = y_{f-1}[t - s_{f-1}] + y_f[t - s_f]       for t covered by two frames
+ *
+ * Periodic Hann at hop N/2 sums to exactly 1, so an all-ones mask gives y = x.
+ * Output: d_out[2*n_samples] is range-relative, byte 0 is I of first_sample.  Samples [h, F*h) of the range receive
+ * u = min(255, max(0, rint(fl32(y + offset)))) per component (rint: round half to even); the first half frame [0, h)
+ * and everything from F*h to n_samples are copied from the input unchanged, so the cleaned capture has the length and
+ * the byte coordinates of the original.  The call writes exactly 2*n_samples bytes.
+ * Threshold values: +inf never excises, a negative value always does (a fixed notch), NaN never does.
+ * d_frames (optional, may be NULL) receives one record per frame.
+ * nfft: a power of two, 16..4096 (GJ_ERR_UNSUPPORTED otherwise).  GJ_ERR_INVALID: n_samples < nfft, a range that runs
+ * past the capture, a null or odd d_iq, a null d_out or d_threshold, a d_threshold or d_frames that is not 4-byte
+ * aligned, d_out[0, 2*n_samples) overlapping d_iq[0, nbytes) (frames read their neighbours: in place is wrong).
+ * first_sample may be odd.  A refused call enqueues nothing.  Needs no workspace; enqueues and returns.
+ * Determinism: an excised sample depends only on the bytes of the two frames that cover it and every sum runs in an
+ * order fixed by nfft, so a call started k*h samples later reproduces the overlapping interior bytes and the records of
+ * the shared frames bit for bit, and two identical calls give identical bytes. */
+typedef struct gj_excise_frame {   /* 16 bytes */
+    float total;       /* sum_k P_f[k] */
+    float removed;     /* sum of P_f[k] over the excised bins */
+    int32_t n_excised; /* bins with M_f[k] = 0 */
+    int32_t reserved;  /* 0 */
+} gj_excise_frame;
+/* frames of the excisor: pure host arithmetic, no context */
+size_t gj_excise_frames(size_t n_samples, int nfft);
+int gj_excise_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples, int nfft,
+                  const float* d_threshold /* [nfft] */, uint8_t* d_out /* [2*n_samples] */,
+                  gj_excise_frame* d_frames /* [F] or NULL */);
+
 /* raw-byte histogram of every `stride`-th byte (widmo_plot.py:35,85: stride 100,
  * 256 bins).  Strided per chunk exactly like raw_chunk[::100]. */
 int gj_byte_histogram_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t chunk_samples,
