@@ -27,7 +27,7 @@ from ._ffi import (AmpStats, GpsJamError, GpsJamLibraryError, Onset, SynthParams
 __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "device_count",
            "library_path", "as_u8", "default_device", "read_capture", "resident_capture",
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
-           "ridge_frames", "EXCISE_DTYPE", "excise_frames"]
+           "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -217,6 +217,49 @@ class Ridge:
     def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
         """Signed frequency of peak_bin: bins from nfft/2 on are negative frequencies."""
         k = self.peak_bin.astype(np.int64)
+        return np.where(k >= self.nfft // 2, k - self.nfft, k) * (float(fs) / self.nfft)
+
+
+def sk_rows(nbytes: int, first_sample: int, nfft: int, hop: int, frames_per_row: int) -> int:
+    """Whole rows of frames_per_row frames of nfft points that fit from first_sample at the given hop (gj_sk_rows);
+    0 when none do."""
+    if min(int(nbytes), int(first_sample), int(hop)) < 0 or not -2 ** 31 <= int(nfft) < 2 ** 31 or not -2 ** 31 <= int(frames_per_row) < 2 ** 31:
+        return 0
+    return int(_ffi.load().gj_sk_rows(int(nbytes), int(first_sample), int(nfft), int(hop), int(frames_per_row)))
+
+
+def _sk_estimate(s1, s2, frames: int) -> np.ndarray:
+    """(M+1)/(M-1) * (M * S2 / S1^2 - 1) in float64 with M = frames; NaN where S1 == 0 (include/gpsjam.h)."""
+    s1, s2, m = np.asarray(s1, np.float64), np.asarray(s2, np.float64), float(frames)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sk = (m + 1.0) / (m - 1.0) * (m * s2 / (s1 * s1) - 1.0)
+    return np.where(s1 == 0, np.nan, sk)
+
+
+class SpectralKurtosis:
+    """Spectral kurtosis of a capture (``Device.spectral_kurtosis``; gj_sk_dev, include/gpsjam.h): per row of
+    ``frames_per_row`` frames and per bin the sums ``s1`` of P and ``s2`` of P^2 and the estimator ``sk``, each
+    float32[rows, nfft] in FFT order, plus the geometry they were computed with.  Row r starts at sample
+    ``first_sample + r * frames_per_row * hop``.  Noise gives sk = 1 with standard deviation 2 / sqrt(frames_per_row)."""
+
+    def __init__(self, s1, s2, sk, nfft: int, hop: int, frames_per_row: int, first_sample: int = 0):
+        self.nfft, self.hop, self.frames_per_row, self.first_sample = int(nfft), int(hop), int(frames_per_row), int(first_sample)
+        self.s1 = np.ascontiguousarray(s1, dtype=np.float32).reshape(-1, self.nfft)
+        self.s2 = np.ascontiguousarray(s2, dtype=np.float32).reshape(-1, self.nfft)
+        self.sk = np.ascontiguousarray(sk, dtype=np.float32).reshape(-1, self.nfft)
+
+    def __len__(self) -> int:
+        return self.s1.shape[0]
+
+    def merged(self) -> np.ndarray:
+        """SK of all rows together, float64[nfft]: the estimator on the summed sums with M = frames_per_row * rows."""
+        if len(self) == 0:
+            return np.full(self.nfft, np.nan)
+        return _sk_estimate(self.s1.astype(np.float64).sum(axis=0), self.s2.astype(np.float64).sum(axis=0), self.frames_per_row * len(self))
+
+    def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
+        """Signed frequency of every bin in FFT order: bins from nfft/2 on are negative frequencies."""
+        k = np.arange(self.nfft)
         return np.where(k >= self.nfft // 2, k - self.nfft, k) * (float(fs) / self.nfft)
 
 
@@ -802,6 +845,38 @@ class Device:
                 own.free()
         return Ridge(rec, nfft, hop, first_sample, guard)
 
+    def spectral_kurtosis(self, capture, nfft: int = 256, hop: Optional[int] = None, frames_per_row: int = 256,
+                          first_sample: int = 0, n_rows: Optional[int] = None) -> SpectralKurtosis:
+        """Spectral kurtosis (gj_sk_dev): per row of frames_per_row frames of nfft points, hop samples apart (default
+        nfft: independent frames), the per-bin sums of P and P^2 and the estimator; n_rows defaults to all that fit.
+        ``capture``: host bytes (uploaded once, like a ``Capture``) or a resident ``Capture``."""
+        nfft, frames_per_row, first_sample = int(nfft), int(frames_per_row), int(first_sample)
+        hop = nfft if hop is None else int(hop)
+        own = None if isinstance(capture, Capture) else Capture(self, capture)
+        cap = capture if own is None else own
+        out = None
+        try:
+            if not cap.ptr and cap.nbytes:
+                raise ValueError("the capture has been freed")
+            if n_rows is None:
+                n_rows = sk_rows(cap.nbytes, first_sample, nfft, hop, frames_per_row)
+                if n_rows == 0 and 16 <= nfft <= 4096 and hop >= 1 and 2 <= frames_per_row <= 65536:
+                    empty = np.empty((0, nfft), np.float32)
+                    return SpectralKurtosis(empty, empty, empty, nfft, hop, frames_per_row, first_sample)
+            n_rows = int(n_rows)
+            self._count("spectral_kurtosis")
+            cells = max(n_rows, 1) * max(nfft, 1)
+            out = DevBuf(self, 3 * 4 * cells)
+            self.spectral_kurtosis_dev(cap, cap.nbytes, first_sample, nfft, hop, frames_per_row, n_rows, out.ptr,
+                                       out.ptr + 4 * cells, out.ptr + 8 * cells)
+            got = out.download(np.float32, 3 * cells).reshape(3, cells)[:, :n_rows * nfft]
+        finally:
+            if out is not None:
+                out.free()
+            if own is not None:
+                own.free()
+        return SpectralKurtosis(got[0], got[1], got[2], nfft, hop, frames_per_row, first_sample)
+
     def excise(self, raw, threshold, nfft: int = 1024, first_sample: int = 0, n_samples: Optional[int] = None):
         """Frequency-domain excision (gj_excise_dev): samples first_sample .. + n_samples of ``raw`` (default: to the
         end) with every bin of every nfft-point frame whose power exceeds ``threshold[k]`` taken out.  ``raw``: host
@@ -845,6 +920,15 @@ class Device:
         frame into d_frames, on the context's stream."""
         self._check(self._lib.gj_excise_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples), int(nfft),
                                             _ptr(d_threshold), _ptr(d_out), _ptr(d_frames) or None))
+
+    def spectral_kurtosis_dev(self, d_iq, nbytes, first_sample, nfft, hop, frames_per_row, n_rows, d_s1, d_s2, d_sk=None):
+        """gj_sk_dev: float32[n_rows][nfft] sums of P into d_s1 and of P^2 into d_s2 and, if asked for, the estimator
+        into d_sk, on the context's stream."""
+        self._check(self._lib.gj_sk_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(nfft), int(hop),
+                                        int(frames_per_row), int(n_rows), _ptr(d_s1), _ptr(d_s2), _ptr(d_sk) or None))
+
+    def sk_workspace(self, nfft: int, frames_per_row: int, n_rows: int) -> int:
+        return self._lib.gj_sk_workspace(self._ctx, int(nfft), int(frames_per_row), int(n_rows))
 
     def ridge_dev(self, d_iq, nbytes, first_sample, nfft, hop, n_frames, guard, d_out):
         """gj_ridge_dev: n_frames records of 16 bytes (RIDGE_DTYPE) into d_out, on the context's stream."""

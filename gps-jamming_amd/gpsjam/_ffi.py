@@ -197,6 +197,9 @@ SIGNATURES = {
     "gj_welch_workspace": (_sz, [_vp, _sz, _sz, _i]),
     "gj_ridge_frames": (_sz, [_sz, _sz, _i, _sz]),
     "gj_ridge_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _sz, _i, _vp]),
+    "gj_sk_rows": (_sz, [_sz, _sz, _i, _sz, _i]),
+    "gj_sk_workspace": (_sz, [_vp, _i, _i, _sz]),
+    "gj_sk_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _i, _sz, _vp, _vp, _vp]),
     "gj_excise_frames": (_sz, [_sz, _i]),
     "gj_excise_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp]),
     "gj_byte_histogram_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

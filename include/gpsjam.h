@@ -244,6 +244,42 @@ size_t gj_ridge_frames(size_t nbytes, size_t first_sample, int nfft, size_t hop)
 int gj_ridge_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, int nfft, size_t hop,
                  size_t n_frames, int guard, gj_ridge_frame* d_out /* [n_frames] */);
 
+/* ------------------------------------------------- spectral kurtosis ---------------- */
+/* Floor-free per-bin interference detection (Nita & Gary's estimator; gpsjam/kurtosis.py reads it): for every bin the
+ * sums of P and of P^2 over the M = frames_per_row short spectra of a row.  Gaussian noise gives SK = 1 whatever its
+ * level or the passband's shape, a steady carrier pulls its bin toward 0, anything intermittent (pulses, a chirp that
+ * crosses the bin) pushes it above 1; the estimator's standard deviation under noise is 2 / sqrt(M).  Blind spots, by
+ * construction: a Gaussian broadband jammer and a pulse train of exactly 50 % duty both have SK = 1.
+ * With N = nfft, row r = 0 .. n_rows-1 holds the frames f = r*M + m, m = 0 .. M-1, at s_f = first_sample + f*hop:
+ *
+ *   x[t]     = (I_t - offset) + j(Q_t - offset)                  un-normalised; honours gj_set_unpack's offset
+ *   w[n]     = 0.5 - 0.5 cos(2 pi n / N)                          periodic Hann, K2's table
+ *   X_f[k]   = sum_{n<N} w[n] x[s_f + n] exp(-2 pi i k n / N)     no mean removal
+ *   P_f[k]   = |X_f[k]|^2 * scale^2                               the units of gj_ridge_dev and gj_excise_dev
+ *   S1[r][k] = sum_m P_f[k]          S2[r][k] = sum_m P_f[k]^2
+ *   SK[r][k] = (M+1)/(M-1) * (M * S2 / S1^2 - 1)                  NaN where S1 == 0
+ *
+ * S1 / M is the mean of the very P_f[k] that gj_excise_dev compares with its threshold.
+ * d_s1, d_s2: float32[n_rows][nfft] in FFT order; d_sk: the same shape, or NULL.  SK is evaluated in double from the
+ * float32 values written to d_s1 and d_s2 and rounded once.
+ * nfft: a power of two, 16..4096 (GJ_ERR_UNSUPPORTED otherwise).  hop >= 1, otherwise arbitrary (hop = nfft gives
+ * independent frames); first_sample may be odd.  2 <= frames_per_row <= 65536 (below 2: GJ_ERR_INVALID, the estimator
+ * is undefined; above: GJ_ERR_UNSUPPORTED).  n_rows == 0 or more rows than fit, a null or odd d_iq, a null d_s1 or
+ * d_s2, an output that is not 4-byte aligned: GJ_ERR_INVALID.  A refused call enqueues nothing.  Enqueues on the
+ * context's stream (two launches) and returns; allocates nothing when gj_sk_workspace bytes were reserved.
+ * Determinism: a row is cut into blocks of at most 16 consecutive frames by a rule that depends on frames_per_row
+ * alone; one transform group sums a block frame by frame in float32, and the blocks of a row are added in order.  So
+ * row r of a call is bit-identical to row r-k of the same call started at first_sample + k*frames_per_row*hop and to
+ * row r of a call with fewer rows, and two identical calls give identical bytes. */
+/* whole rows that fit: pure host arithmetic, no context; 0 for an impossible geometry (nfft < 1, hop < 1,
+ * frames_per_row < 1, no room) */
+size_t gj_sk_rows(size_t nbytes, size_t first_sample, int nfft, size_t hop, int frames_per_row);
+/* workspace bytes gj_sk_dev needs for the partial sums (for gj_reserve); 0 for parameters gj_sk_dev refuses */
+size_t gj_sk_workspace(gj_ctx* ctx, int nfft, int frames_per_row, size_t n_rows);
+int gj_sk_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, int nfft, size_t hop,
+              int frames_per_row, size_t n_rows, float* d_s1 /* [n_rows*nfft] */, float* d_s2 /* [n_rows*nfft] */,
+              float* d_sk /* [n_rows*nfft] or NULL */);
+
 /* ------------------------------------------------- frequency-domain excision -------- */
 /* The windowed 50 %-overlap FFT excisor of GPS receivers: a cleaned capture, uint8 I/Q again, with every bin above its
  * threshold taken out (the interferers of simulate/frontend/jammers/; gpsjam/mitigate.py builds the thresholds).  For a
