@@ -3,9 +3,8 @@
 // The classical excisor of GPS receivers; simulate/frontend/jammers/ of the reference defines the interferers it has
 // to remove.  The project's first kernel whose output is a capture.
 //
-// The transform is K2's (k_welch.hip), the per-frame shape k_ridge.hip's: one 256-thread workgroup holds 4096 / N
-// transform groups of N / 16 threads, every thread pulls its 16 samples from the uint8 stream, applies unpack and the
-// periodic Hann window of K2's table and runs the register-resident Stockham passes of fft_core.h.  What differs:
+// The transform front end -- the workgroup of transform groups, the loads, the window, the passes and their exchange
+// barrier, the group reductions -- is stft_group.h, shared with k_ridge.hip and k_skurt.hip.  What is the excisor's own:
 //   * frames hop by N / 2, and a transform group owns a RUN of consecutive frames that it walks in order.  After the
 //     last pass a thread holds points jl + TF s (TF = N / 16); its slots s and s + 8 are N / 2 apart, so the
 //     overlap-add is prev[s + 8] + cur[s] in registers and eight c2 are carried from frame to frame: no LDS, no atomics;
@@ -27,11 +26,9 @@
 // The first half frame and the tail behind the last whole hop are copied from the input by a second small launch.
 //
 // This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it.
-#include "gj_common.h"
+#include "stft_group.h"
 
 namespace gj {
-
-extern const float* window_table(gj_ctx* ctx, int n);   // api.hip: K2's periodic Hann tables
 
 template <int N>
 struct ExciseCfg {
@@ -48,43 +45,6 @@ struct ExciseGeom {
     float scale2;    // scale^2: the transform runs on u8 - offset, the powers are scaled to the units of gj_ridge_dev
 };
 
-template <int G>
-__device__ __forceinline__ float group_sum_f(float v) {
-#define GJ_DPP_F(x, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, 0xf, 0xf, false))
-    if constexpr (G >= 2) v += GJ_DPP_F(v, 0xB1);     // quad_perm [1,0,3,2]
-    if constexpr (G >= 4) v += GJ_DPP_F(v, 0x4E);     // quad_perm [2,3,0,1]
-    if constexpr (G >= 8) v += GJ_DPP_F(v, 0x141);    // row_half_mirror
-    if constexpr (G >= 16) v += GJ_DPP_F(v, 0x140);   // row_mirror
-#undef GJ_DPP_F
-    if constexpr (G >= 32) v += __shfl_xor(v, 16, 64);
-    if constexpr (G >= 64) v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
-// the exchange barrier of k_ridge.hip / K2: a wavefront fence while a transform group lies inside one wave
-template <int N>
-__device__ __forceinline__ void excise_exchange_sync() {
-    if constexpr (N / 16 <= 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-template <int N, int PASS>
-__device__ __forceinline__ void excise_passes(c2 (&v)[16], cf* lds, int base, int jl, const c2 (&tw)[3][15], const InnerTw& ktw) {
-    fft_pass<N, PASS, true>(v, tw[PASS], ktw);
-    if constexpr (PASS + 1 < fft_npass(N)) {
-        lds_scatter<N, PASS>(v, lds, base, jl);
-        excise_exchange_sync<N>();
-        lds_gather<N>(v, lds, base, jl);
-        excise_exchange_sync<N>();
-        excise_passes<N, PASS + 1>(v, lds, base, jl, tw, ktw);
-    }
-}
-
 template <int N>
 __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise_kernel(const uint8_t* __restrict__ iq, ExciseGeom g,
                                                                                         const cf* __restrict__ twtab,
@@ -92,30 +52,21 @@ __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise
                                                                                         const float* __restrict__ thr_tab,
                                                                                         uint8_t* __restrict__ out,
                                                                                         gj_excise_frame* __restrict__ frames) {
-    constexpr int TF = N / 16, B = kBlockPoints / N, NP = fft_npass(N), H = N / 2;
-    constexpr int WPF = (TF >= 64) ? TF / 64 : 1;   // waves per transform
+    using S = StftShape<N>;
+    constexpr int TF = S::TF, B = S::B, NP = S::NP, WPF = S::WPF, H = N / 2;
     __shared__ cf lds0[NP > 1 ? lds_span(kBlockPoints) : 1];
     // wave results of a transform group that spans waves (2048, 4096 points), one array per reduction as in ridge_kernel
     constexpr int RB = WPF > 1 ? B : 1;
     __shared__ float red_tot[RB][WPF], red_rem[RB][WPF], red_cnt[RB][WPF];
-    static_assert(TF > 64 || (64 % TF == 0 && WPF == 1 && kBlockThreads % 64 == 0 && B * TF == kBlockThreads),
-                  "the wave-fence exchange needs a transform group inside one wave");
     const int tid = threadIdx.x;
-    const int b = (TF >= 64) ? __builtin_amdgcn_readfirstlane(tid / TF) : tid / TF;
-    const int jl = tid % TF;   // input points, bins and output points of this thread: jl + TF s
+    const StftRoles role = stft_roles<N, false>(tid);
+    const int b = role.b, jl = role.jl;   // input points, bins and output points of this thread: jl + TF s
 
     const InnerTw ktw = inner_twiddles();
-    c2 tw[3][15];
+    c2 tw[3][15], wp[8];
+    stft_load_twiddles<N>(tw, twtab, jl);
 #pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int k = 0; k < 15; ++k) tw[p][k] = make_c2(1.f, 0.f);
-    if constexpr (NP > 1) load_twiddles<N, 1>(tw[1], twtab, jl);
-    if constexpr (NP > 2) load_twiddles<N, 2>(tw[2], twtab, jl);
-
-    c2 wp[8];   // (w[2i], w[2i+1]) share a register pair, op_sel picks the half
-#pragma unroll
-    for (int s = 0; s < 8; ++s) wp[s] = make_c2(wintab[jl + TF * (2 * s)], wintab[jl + TF * (2 * s + 1)]);
+    for (int s = 0; s < 8; ++s) wp[s] = stft_window_pair<N>(wintab, jl, s);
     float thr[16];
 #pragma unroll
     for (int s = 0; s < 16; ++s) thr[s] = thr_tab[jl + TF * s];
@@ -130,12 +81,9 @@ __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise
     const long long run_end = run_first + (long long)g.per_run;
     auto frame_base = [&](long long f) {
         f = f < 0 ? 0 : (f > last ? last : f);
-        return iq + 2ull * (g.first_sample + (unsigned long long)f * H) + 2 * jl;
+        return iq + 2ull * (g.first_sample + (unsigned long long)f * H);
     };
-    auto load_frame = [&](unsigned (&dst)[16], const uint8_t* p) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) dst[s] = *reinterpret_cast<const uint16_t*>(p + 2 * TF * s);
-    };
+    auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, false>(dst, base, jl); };
 
     unsigned raw[16];   // the NEXT frame's samples are fetched while the current ones are transformed
     load_frame(raw, frame_base(run_first - 1));
@@ -146,15 +94,10 @@ __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise
     for (long long f = run_first - 1; f < run_end; ++f) {
         const bool owned = f >= run_first && f <= last;
         c2 v[16];
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const unsigned u = raw[s];
-            const c2 x = cadd(make_c2((float)(u & 255u), (float)((u >> 8) & 255u)), koff);   // exact: u8 minus a multiple of 0.5
-            v[s] = (s & 1) ? scale_hi(x, wp[s >> 1]) : scale_lo(x, wp[s >> 1]);
-        }
+        stft_unpack_window(v, raw, wp, koff);
         if (f + 1 < run_end) load_frame(raw, frame_base(f + 1));   // workgroup-uniform
 
-        excise_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
+        stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
 
         // this thread's bins jl + TF s: power, mask, conjugate for the way back
         float tot = 0.f, rem = 0.f, cnt = 0.f;
@@ -171,17 +114,18 @@ __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise
             cnt += cut ? 1.f : 0.f;        // at most 4096: exact in float
             v[s] = cut ? make_c2(0.f, 0.f) : make_c2(v[s].x, -v[s].y);
         }
-        constexpr int G = TF >= 64 ? 64 : TF;
-        tot = group_sum_f<G>(tot);
-        rem = group_sum_f<G>(rem);
-        cnt = group_sum_f<G>(cnt);
+        const auto add = [](float a, float c) { return a + c; };
+        tot = group_reduce_f<S::G>(tot, add);
+        rem = group_reduce_f<S::G>(rem, add);
+        cnt = group_reduce_f<S::G>(cnt, add);
         if constexpr (WPF > 1) {
-            const int wv = (tid >> 6) % WPF;
-            if ((tid & 63) == 0) { red_tot[b][wv] = tot; red_rem[b][wv] = rem; red_cnt[b][wv] = cnt; }
+            waves_post(red_tot[b], tid, tot);
+            waves_post(red_rem[b], tid, rem);
+            waves_post(red_cnt[b], tid, cnt);
             __syncthreads();
-            tot = red_tot[b][0]; rem = red_rem[b][0]; cnt = red_cnt[b][0];
-#pragma unroll
-            for (int k = 1; k < WPF; ++k) { tot += red_tot[b][k]; rem += red_rem[b][k]; cnt += red_cnt[b][k]; }
+            tot = waves_fold(red_tot[b], add);
+            rem = waves_fold(red_rem[b], add);
+            cnt = waves_fold(red_cnt[b], add);
         }
         if (frames && owned && jl == 0) {   // one lane per transform group
             gj_excise_frame r;
@@ -192,7 +136,7 @@ __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise
             frames[f] = r;
         }
 
-        excise_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
+        stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
 
         // y_f = conj(v) / N; samples [f H, (f + 1) H) of the range = previous frame's second half + this one's first
         const bool store = owned && f >= 1;
@@ -254,9 +198,9 @@ int gj_excise_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_
                   const float* d_threshold, uint8_t* d_out, gj_excise_frame* d_frames) {
     if (!ctx) return GJ_ERR_INVALID;
     Guard lock(ctx);
-    if (nfft < 16 || nfft > 4096 || (nfft & (nfft - 1))) return fail(ctx, GJ_ERR_UNSUPPORTED, "nfft must be a power of two in [16, 4096]");
+    if (int rc = stft_check_nfft(ctx, nfft)) return rc;
     if (!d_iq || !d_out || !d_threshold) return fail(ctx, GJ_ERR_INVALID, "null buffer");
-    if (reinterpret_cast<uintptr_t>(d_iq) & 1) return fail(ctx, GJ_ERR_INVALID, "capture must be 2-byte aligned");
+    if (int rc = stft_check_capture(ctx, d_iq)) return rc;
     if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
     const size_t total = nbytes / 2;
@@ -274,17 +218,7 @@ int gj_excise_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_
     g.per_run = 0;
     g.offset = 0.5f * (float)ctx->off2;
     g.scale2 = (float)(ctx->scale * ctx->scale);
-    switch (nfft) {
-        case 16: excise_launch<16>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-        case 32: excise_launch<32>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-        case 64: excise_launch<64>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-        case 128: excise_launch<128>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-        case 256: excise_launch<256>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-        case 512: excise_launch<512>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-        case 1024: excise_launch<1024>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-        case 2048: excise_launch<2048>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-        default: excise_launch<4096>(ctx, d_iq, g, d_threshold, d_out, d_frames); break;
-    }
+    stft_dispatch(nfft, [&](auto n) { excise_launch<decltype(n)::value>(ctx, d_iq, g, d_threshold, d_out, d_frames); });
     GJ_LAUNCH_CHECK(ctx);
     const unsigned long long h2 = (unsigned long long)nfft;   // bytes of half a frame
     const unsigned long long tail_first = g.n_frames * h2, n_bytes = 2ull * n_samples;

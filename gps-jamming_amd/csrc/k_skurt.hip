@@ -4,10 +4,8 @@
 // Gaussian noise gives 1 whatever its level or the passband's shape, a steady carrier pulls its bin toward 0 and
 // anything intermittent pushes it above 1 (gpsjam/kurtosis.py reads it).
 //
-// The transform is K2's (k_welch.hip), the per-frame shape k_ridge.hip's: one 256-thread workgroup holds 4096 / N
-// transform groups of N / 16 threads, every thread pulls its 16 samples straight from the uint8 stream, applies unpack
-// and the periodic Hann window of K2's table and runs the register-resident Stockham passes of fft_core.h with LDS
-// exchanges.  What differs:
+// The transform front end -- the workgroup of transform groups, the loads, the window, the passes and their exchange
+// barrier -- is stft_group.h, shared with k_ridge.hip and k_excise.hip.  What is the kurtosis's own:
 //   * a transform group, not a workgroup, is the unit of work: it takes one BLOCK of a row, a run of up to kSkMaxRun
 //     consecutive frames, and keeps 16 + 16 accumulators in registers for sum P and sum P^2 of its 16 bins.  Nothing
 //     is reduced across lanes: a bin belongs to one thread;
@@ -23,13 +21,11 @@
 //
 // This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it
 // (tests/hip_stub builds those by name), and K2's module is compiled exactly as before.
-#include "gj_common.h"
+#include "stft_group.h"
 
 #include <cmath>
 
 namespace gj {
-
-extern const float* window_table(gj_ctx* ctx, int n);   // api.hip: K2's periodic Hann tables
 
 constexpr int kSkMaxRun = 16;       // frames per block at most: a partial pair (8 N bytes) per 32 N bytes read at hop = N
 constexpr int kSkMaxFrames = 65536; // frames per row at most
@@ -60,76 +56,28 @@ struct SkGeom {
     float neg_off;   // -offset of the unpack convention
 };
 
-// the exchange barrier of k_ridge.hip / K2: a wavefront fence while a transform group lies inside one wave
-template <int N>
-__device__ __forceinline__ void sk_exchange_sync() {
-    if constexpr (N / 16 <= 64) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    } else {
-        __syncthreads();
-    }
-}
-
-template <int N, int PASS>
-__device__ __forceinline__ void sk_passes(c2 (&v)[16], cf* lds, int base, int jl, const c2 (&tw)[3][15], const InnerTw& ktw) {
-    fft_pass<N, PASS, true>(v, tw[PASS], ktw);
-    if constexpr (PASS + 1 < fft_npass(N)) {
-        lds_scatter<N, PASS>(v, lds, base, jl);
-        sk_exchange_sync<N>();
-        lds_gather<N>(v, lds, base, jl);
-        sk_exchange_sync<N>();
-        sk_passes<N, PASS + 1>(v, lds, base, jl, tw, ktw);
-    }
-}
-
-// 4096 points: pass 0 in role jl0 = tid, passes 1 and 2 in role jl1 (fft_core.h, X4096)
-__device__ __forceinline__ void sk_passes_x4096(c2 (&v)[16], cf* lds, int tid, const c2 (&tw)[3][15], const InnerTw& ktw) {
-    fft_pass<4096, 0, true>(v, tw[0], ktw);
-    x4096_scatter<0>(v, lds, tid);
-    __syncthreads();
-    x4096_gather<0>(v, lds, tid);
-    __syncthreads();
-    fft_pass<4096, 1, true>(v, tw[1], ktw);
-    x4096_scatter<1>(v, lds, tid);
-    __syncthreads();
-    x4096_gather<1>(v, lds, tid);
-    __syncthreads();
-    fft_pass<4096, 2, true>(v, tw[2], ktw);
-}
-
 template <int N>
 __global__ __launch_bounds__(kBlockThreads, SkCfg<N>::min_waves) void sk_kernel(const uint8_t* __restrict__ iq, SkGeom g,
                                                                                 const cf* __restrict__ twtab,
                                                                                 const float* __restrict__ wintab,
                                                                                 float* __restrict__ partial) {
     using Cfg = SkCfg<N>;
-    constexpr int TF = N / 16, B = kBlockPoints / N, NP = fft_npass(N);
-    constexpr int WPF = (TF >= 64) ? TF / 64 : 1;   // waves per transform
+    using S = StftShape<N>;
+    constexpr int TF = S::TF, B = S::B, NP = S::NP;
     constexpr bool XP = Cfg::xpose;
     constexpr int SPAN = XP ? X4096::kSpan : lds_span(kBlockPoints);
     __shared__ cf lds0[NP > 1 ? SPAN : 1];
-    // what the wave fence rests on (k_welch.hip): a transform group is an aligned fraction of ONE wave
-    static_assert(TF > 64 || (64 % TF == 0 && WPF == 1 && kBlockThreads % 64 == 0 && B * TF == kBlockThreads),
-                  "the wave-fence exchange needs a transform group inside one wave");
     const int tid = threadIdx.x;
-    const int b = (TF >= 64) ? __builtin_amdgcn_readfirstlane(tid / TF) : tid / TF;
-    const int jl0 = tid % TF;                    // butterfly of pass 0 (input index jl0 + TF s)
-    const int jl = XP ? X4096::jl1(tid) : jl0;   // butterfly of the later passes = bins held at the end: jl + TF s
+    const StftRoles role = stft_roles<N, XP>(tid);
+    const int b = role.b, jl0 = role.jl0, jl = role.jl;
 
     const InnerTw ktw = inner_twiddles();
     c2 tw[3][15];
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int k = 0; k < 15; ++k) tw[p][k] = make_c2(1.f, 0.f);
-    if constexpr (NP > 1) load_twiddles<N, 1>(tw[1], twtab, jl);
-    if constexpr (NP > 2) load_twiddles<N, 2>(tw[2], twtab, jl);
+    stft_load_twiddles<N>(tw, twtab, jl);
 
-    c2 wp[8];   // (w[2i], w[2i+1]) share a register pair, op_sel picks the half
+    c2 wp[8];
 #pragma unroll
-    for (int s = 0; s < 8; ++s) wp[s] = make_c2(wintab[jl0 + TF * (2 * s)], wintab[jl0 + TF * (2 * s + 1)]);
+    for (int s = 0; s < 8; ++s) wp[s] = stft_window_pair<N>(wintab, jl0, s);
     const c2 koff = make_c2(g.neg_off, g.neg_off);
 
     // This group's block in workgroup step `step`: its first frame and how many frames it holds.  A group behind the
@@ -149,30 +97,7 @@ __global__ __launch_bounds__(kBlockThreads, SkCfg<N>::min_waves) void sk_kernel(
         if (f > g.last_frame) f = g.last_frame;   // a short block's spare iterations
         return iq + 2ull * (g.first_sample + f * g.hop);
     };
-    auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) {
-        if constexpr (Cfg::wide_load) {
-            // the whole frame (2 N bytes) in 16-byte loads; sample jl0 + TF s is one half of dword (jl0 + TF s) / 2.
-            // The frame is only 2-byte aligned: global memory takes unaligned vector loads.
-            struct __attribute__((packed, aligned(2))) Vec16 { unsigned x, y, z, w; };
-            constexpr int NV = 2 * N / 16;
-            const Vec16* src = reinterpret_cast<const Vec16*>(base);
-            unsigned w[4 * NV];
-#pragma unroll
-            for (int q = 0; q < NV; ++q) {
-                const Vec16 t = src[q];
-                w[4 * q] = t.x; w[4 * q + 1] = t.y; w[4 * q + 2] = t.z; w[4 * q + 3] = t.w;
-            }
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                if constexpr (TF == 1) dst[s] = (s & 1) ? (w[s >> 1] >> 16) : (w[s >> 1] & 0xffffu);
-                else dst[s] = (w[s] >> (16u * (unsigned)jl0)) & 0xffffu;
-            }
-        } else {
-            const uint8_t* p = base + 2 * jl0;
-#pragma unroll
-            for (int s = 0; s < 16; ++s) dst[s] = *reinterpret_cast<const uint16_t*>(p + 2 * TF * s);
-        }
-    };
+    auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, Cfg::wide_load>(dst, base, jl0); };
 
     unsigned raw[16];   // the NEXT frame's samples are fetched while the current ones are transformed
     unsigned long long step = blockIdx.x;   // the grid never exceeds nsteps
@@ -189,17 +114,12 @@ __global__ __launch_bounds__(kBlockThreads, SkCfg<N>::min_waves) void sk_kernel(
 
         for (unsigned i = 0; i < g.run; ++i) {
             c2 v[16];
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const unsigned u = raw[s];
-                const c2 x = cadd(make_c2((float)(u & 255u), (float)((u >> 8) & 255u)), koff);   // exact: u8 minus a multiple of 0.5
-                v[s] = (s & 1) ? scale_hi(x, wp[s >> 1]) : scale_lo(x, wp[s >> 1]);
-            }
+            stft_unpack_window(v, raw, wp, koff);
             if (i + 1 < g.run) load_frame(raw, frame_base(f0 + i + 1));
             else if (more) load_frame(raw, frame_base(next_f0));
 
-            if constexpr (XP) sk_passes_x4096(v, lds0, tid, tw, ktw);
-            else sk_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
+            if constexpr (XP) stft_passes_x4096(v, lds0, tid, tw, ktw);
+            else stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
 
             // this thread's bins jl + TF s.  A spare iteration adds zeros: the sums keep their bits.
             const bool counted = i < count;
@@ -263,10 +183,7 @@ template <int N>
 static void sk_launch(gj_ctx* ctx, const uint8_t* d_iq, SkGeom g, float* partial) {
     constexpr unsigned long long B = kBlockPoints / N;
     g.nsteps = (g.n_units + B - 1) / B;
-    // one round of workgroups, each with the same number of steps (but for the last ones, one fewer)
-    const unsigned long long slots = (unsigned long long)ctx->num_cus * SkCfg<N>::min_waves;
-    const unsigned long long per_wg = (g.nsteps + slots - 1) / slots;
-    const unsigned grid = (unsigned)((g.nsteps + per_wg - 1) / per_wg);
+    const unsigned grid = stft_one_round_grid(ctx, SkCfg<N>::min_waves, g.nsteps);
     hipLaunchKernelGGL(sk_kernel<N>, dim3(grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle, window_table(ctx, N),
                        partial);
 }
@@ -285,7 +202,7 @@ size_t gj_sk_rows(size_t nbytes, size_t first_sample, int nfft, size_t hop, int 
 
 size_t gj_sk_workspace(gj_ctx* ctx, int nfft, int frames_per_row, size_t n_rows) {
     (void)ctx;
-    if (nfft < 16 || nfft > 4096 || (nfft & (nfft - 1)) || frames_per_row < 2 || frames_per_row > kSkMaxFrames) return 0;
+    if (!stft_nfft_ok(nfft) || frames_per_row < 2 || frames_per_row > kSkMaxFrames) return 0;
     return sk_workspace_bytes(nfft, frames_per_row, n_rows);
 }
 
@@ -293,11 +210,11 @@ int gj_sk_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_samp
               size_t n_rows, float* d_s1, float* d_s2, float* d_sk) {
     if (!ctx) return GJ_ERR_INVALID;
     Guard lock(ctx);
-    if (nfft < 16 || nfft > 4096 || (nfft & (nfft - 1))) return fail(ctx, GJ_ERR_UNSUPPORTED, "nfft must be a power of two in [16, 4096]");
+    if (int rc = stft_check_nfft(ctx, nfft)) return rc;
     if (frames_per_row < 2) return fail(ctx, GJ_ERR_INVALID, "frames_per_row must be >= 2");
     if (frames_per_row > kSkMaxFrames) return fail(ctx, GJ_ERR_UNSUPPORTED, "frames_per_row must be <= %d", kSkMaxFrames);
     if (!d_iq || !d_s1 || !d_s2) return fail(ctx, GJ_ERR_INVALID, "null buffer");
-    if (reinterpret_cast<uintptr_t>(d_iq) & 1) return fail(ctx, GJ_ERR_INVALID, "capture must be 2-byte aligned");
+    if (int rc = stft_check_capture(ctx, d_iq)) return rc;
     if ((reinterpret_cast<uintptr_t>(d_s1) | reinterpret_cast<uintptr_t>(d_s2) | reinterpret_cast<uintptr_t>(d_sk)) & 3)
         return fail(ctx, GJ_ERR_INVALID, "outputs must be 4-byte aligned");
     if (hop < 1) return fail(ctx, GJ_ERR_INVALID, "hop must be >= 1");
@@ -321,17 +238,7 @@ int gj_sk_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_samp
     g.nb = blk.nb;
     g.run = blk.run;
     g.neg_off = -0.5f * (float)ctx->off2;
-    switch (nfft) {
-        case 16: sk_launch<16>(ctx, d_iq, g, partial); break;
-        case 32: sk_launch<32>(ctx, d_iq, g, partial); break;
-        case 64: sk_launch<64>(ctx, d_iq, g, partial); break;
-        case 128: sk_launch<128>(ctx, d_iq, g, partial); break;
-        case 256: sk_launch<256>(ctx, d_iq, g, partial); break;
-        case 512: sk_launch<512>(ctx, d_iq, g, partial); break;
-        case 1024: sk_launch<1024>(ctx, d_iq, g, partial); break;
-        case 2048: sk_launch<2048>(ctx, d_iq, g, partial); break;
-        default: sk_launch<4096>(ctx, d_iq, g, partial); break;
-    }
+    stft_dispatch(nfft, [&](auto n) { sk_launch<decltype(n)::value>(ctx, d_iq, g, partial); });
     GJ_LAUNCH_CHECK(ctx);
     const unsigned long long n_out = (unsigned long long)n_rows * (unsigned)nfft;
     const unsigned long long want = (n_out + 255) / 256, cap = (unsigned long long)ctx->num_cus * 32;
