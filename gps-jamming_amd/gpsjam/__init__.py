@@ -27,7 +27,7 @@ from ._ffi import (AmpStats, GpsJamError, GpsJamLibraryError, Onset, SynthParams
 __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "device_count",
            "library_path", "as_u8", "default_device", "read_capture", "resident_capture",
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
-           "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows"]
+           "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -218,6 +218,65 @@ class Ridge:
         """Signed frequency of peak_bin: bins from nfft/2 on are negative frequencies."""
         k = self.peak_bin.astype(np.int64)
         return np.where(k >= self.nfft // 2, k - self.nfft, k) * (float(fs) / self.nfft)
+
+
+CHIRP_DTYPE = np.dtype([("total", np.float32), ("peak", np.float32), ("second", np.float32), ("peak_bin", np.int32),
+                        ("rate_index", np.int32), ("reserved", np.int32)])
+
+
+class ChirpScan:
+    """The chirp-rate search of a capture (``Device.chirp``; gj_chirp_frame, include/gpsjam.h): per frame the ridge's four
+    numbers behind the de-chirp that concentrates the frame best, and which rate that was, as the numpy structured array
+    ``records`` (CHIRP_DTYPE) plus the geometry and the rate grid ``rates = (first, step, n)`` they were computed with.
+    Rates count bins per frame length: one unit is fs^2 / nfft^2 Hz/s.  ``peaks``: the peak of every frame at every
+    rate, ``[frames, n]``, or None.  Frame f starts at sample ``first_sample + f * hop``; ``scan[a:b]`` is the
+    ChirpScan of those frames."""
+
+    def __init__(self, records, nfft: int, hop: int, rates, first_sample: int = 0, guard: int = 2, peaks=None):
+        self.records = np.ascontiguousarray(records, dtype=CHIRP_DTYPE).reshape(-1)
+        self.nfft, self.hop, self.first_sample, self.guard = int(nfft), int(hop), int(first_sample), int(guard)
+        self.rates = tuple(int(v) for v in rates)
+        if len(self.rates) != 3:
+            raise ValueError("rates is (first, step, n)")
+        self.peaks = None if peaks is None else np.ascontiguousarray(peaks, dtype=np.float32).reshape(self.records.size, self.rates[2])
+
+    def __len__(self) -> int:
+        return self.records.size
+
+    def __getitem__(self, key) -> "ChirpScan":
+        if not isinstance(key, slice):
+            raise TypeError("a ChirpScan is sliced by frame: scan[a:b]")
+        start, _, step = key.indices(len(self))
+        if step != 1:
+            raise ValueError("a ChirpScan keeps consecutive frames: the step must be 1")
+        return ChirpScan(self.records[key], self.nfft, self.hop, self.rates, self.first_sample + start * self.hop, self.guard,
+                         None if self.peaks is None else self.peaks[key])
+
+    total = property(lambda self: self.records["total"])
+    peak = property(lambda self: self.records["peak"])
+    second = property(lambda self: self.records["second"])
+    peak_bin = property(lambda self: self.records["peak_bin"])
+    rate_index = property(lambda self: self.records["rate_index"])
+
+    @property
+    def rate(self) -> np.ndarray:
+        """The q of each frame's rate_index, in bins per frame length."""
+        return self.rates[0] + self.rates[1] * self.rate_index.astype(np.int64)
+
+    @property
+    def concentration(self) -> np.ndarray:
+        """peak / total at the best rate: the share of each frame's power in its de-chirped peak bin (0 for an empty frame)."""
+        t = self.total.astype(np.float64)
+        return np.divide(self.peak, t, out=np.zeros(t.shape), where=t > 0)
+
+    def sweep_hz_per_s(self, fs: float = 2.048e6) -> np.ndarray:
+        """Each frame's best rate in Hz/s: q fs^2 / nfft^2."""
+        return self.rate * (float(fs) / self.nfft) ** 2
+
+    def centre_freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
+        """Signed frequency of the de-chirped line at the CENTRE of each frame: bin + q / 2, wrapped to [-fs/2, fs/2)."""
+        k = self.peak_bin.astype(np.float64) + 0.5 * self.rate
+        return ((k + self.nfft / 2.0) % self.nfft - self.nfft / 2.0) * (float(fs) / self.nfft)
 
 
 def sk_rows(nbytes: int, first_sample: int, nfft: int, hop: int, frames_per_row: int) -> int:
@@ -845,6 +904,40 @@ class Device:
                 own.free()
         return Ridge(rec, nfft, hop, first_sample, guard)
 
+    def chirp(self, raw, nfft: int = 256, hop: Optional[int] = None, rates=(0, 1, 1), first_sample: int = 0,
+              n_frames: Optional[int] = None, guard: int = 2, want_peaks: bool = False) -> ChirpScan:
+        """Chirp-rate search (gj_chirp_dev): the ridge of every frame behind a de-chirp at each of the rates
+        ``first + r * step``, r < n, of ``rates = (first, step, n)`` (bins per frame length, at most 256 per call); per
+        frame the rate that concentrates it best and the ridge's numbers there.  ``raw``: host bytes (uploaded once) or a
+        resident ``Capture``; n_frames defaults to all that fit.  ``want_peaks``: also every frame's peak at every rate."""
+        nfft, first_sample, guard = int(nfft), int(first_sample), int(guard)
+        hop = nfft // 2 if hop is None else int(hop)
+        first, step, n = (int(v) for v in rates)
+        own = None if isinstance(raw, Capture) else Capture(self, raw)
+        cap = raw if own is None else own
+        out = pk = None
+        try:
+            if not cap.ptr and cap.nbytes:
+                raise ValueError("the capture has been freed")
+            if n_frames is None:
+                n_frames = ridge_frames(cap.nbytes, first_sample, nfft, hop)
+                if n_frames == 0 and 16 <= nfft <= 4096 and hop >= 1 and 1 <= n <= _ffi.GJ_CHIRP_MAX_RATES:
+                    return ChirpScan(np.empty(0, CHIRP_DTYPE), nfft, hop, (first, step, n), first_sample, guard,
+                                     np.empty((0, n), np.float32) if want_peaks else None)
+            n_frames = int(n_frames)
+            self._count("chirp")
+            out = DevBuf(self, max(n_frames, 1) * CHIRP_DTYPE.itemsize)
+            if want_peaks:
+                pk = DevBuf(self, max(n_frames, 1) * max(n, 1) * 4)
+            self.chirp_dev(cap, cap.nbytes, first_sample, nfft, hop, n_frames, guard, first, step, n, out, pk)
+            rec = out.download(CHIRP_DTYPE, n_frames)
+            peaks = pk.download(np.float32, n_frames * n).reshape(n_frames, n) if want_peaks else None
+        finally:
+            for buf in (out, pk, own):
+                if buf is not None:
+                    buf.free()
+        return ChirpScan(rec, nfft, hop, (first, step, n), first_sample, guard, peaks)
+
     def spectral_kurtosis(self, capture, nfft: int = 256, hop: Optional[int] = None, frames_per_row: int = 256,
                           first_sample: int = 0, n_rows: Optional[int] = None) -> SpectralKurtosis:
         """Spectral kurtosis (gj_sk_dev): per row of frames_per_row frames of nfft points, hop samples apart (default
@@ -934,6 +1027,13 @@ class Device:
         """gj_ridge_dev: n_frames records of 16 bytes (RIDGE_DTYPE) into d_out, on the context's stream."""
         self._check(self._lib.gj_ridge_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(nfft), int(hop),
                                            int(n_frames), int(guard), _ptr(d_out)))
+
+    def chirp_dev(self, d_iq, nbytes, first_sample, nfft, hop, n_frames, guard, rate_first, rate_step, n_rates, d_out, d_peaks=None):
+        """gj_chirp_dev: n_frames records of 24 bytes (CHIRP_DTYPE) into d_out and, if asked for, float32[n_frames][n_rates]
+        peaks into d_peaks, on the context's stream."""
+        self._check(self._lib.gj_chirp_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(nfft), int(hop),
+                                           int(n_frames), int(guard), int(rate_first), int(rate_step), int(n_rates),
+                                           _ptr(d_out), _ptr(d_peaks) or None))
 
     def chunk_count(self, nbytes: int, chunk_bytes: int) -> int:
         return self._lib.gj_chunk_count(nbytes, chunk_bytes)

@@ -135,6 +135,12 @@ class RidgeFrame(C.Structure):
     _fields_ = [("total", C.c_float), ("peak", C.c_float), ("second", C.c_float), ("peak_bin", C.c_int32)]
 
 
+class ChirpFrame(C.Structure):
+    """gj_chirp_frame: one frame of the chirp-rate search (include/gpsjam.h)."""
+    _fields_ = [("total", C.c_float), ("peak", C.c_float), ("second", C.c_float), ("peak_bin", C.c_int32),
+                ("rate_index", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ExciseFrame(C.Structure):
     """gj_excise_frame: one frame of the frequency-domain excisor (include/gpsjam.h)."""
     _fields_ = [("total", C.c_float), ("removed", C.c_float), ("n_excised", C.c_int32), ("reserved", C.c_int32)]
@@ -148,6 +154,7 @@ GJ_SLOT_HEADER = 16
 GJ_COMM_ID_BYTES = 128
 GJ_VERSION = 150
 GJ_CAF_MAX_BINS = 4096
+GJ_CHIRP_MAX_RATES = 256
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
 _pf, _psz = C.POINTER(C.c_float), C.POINTER(C.c_size_t)
@@ -197,6 +204,7 @@ SIGNATURES = {
     "gj_welch_workspace": (_sz, [_vp, _sz, _sz, _i]),
     "gj_ridge_frames": (_sz, [_sz, _sz, _i, _sz]),
     "gj_ridge_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _sz, _i, _vp]),
+    "gj_chirp_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _sz, _i, _i, _i, _i, _vp, _vp]),
     "gj_sk_rows": (_sz, [_sz, _sz, _i, _sz, _i]),
     "gj_sk_workspace": (_sz, [_vp, _i, _i, _sz]),
     "gj_sk_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _i, _sz, _vp, _vp, _vp]),

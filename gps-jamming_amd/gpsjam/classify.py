@@ -4,7 +4,9 @@ The detector says THAT a capture is jammed (K1, K4), how strongly (K3) and from 
 interferer is.  The reference's simulator makes four kinds (simulate/frontend/jammers/): a continuous tone
 (cwJammer.py), a saw-tooth chirp (chirpJammer.py), a carrier gated by a square wave (pulsedJammer.py) and wide-band
 noise (broadbandJammer.py).  ``classify`` tells them apart from the records of ``Device.ridge`` alone -- pure numpy,
-no GPU call; ``characterise`` joins it to the onset detector.
+no GPU call; ``characterise`` joins it to the onset detector.  ``classify_swept`` reads the chirp-rate search
+(``Device.chirp``) the same way, for sweeps that cross many bins inside one frame and read as "broadband" on the ridge;
+``characterise_swept`` runs that search only where ``characterise`` leaves the question open.
 
 Every threshold below follows from the window and the frame length, not from any particular input:
 
@@ -206,4 +208,96 @@ def characterise(dev, capture, fs: float = 2.048e6, nfft: int = 256, **onset_arg
     first = -(-k // hop)                                           # first frame with s_f >= k
     res = classify(ridge[first:], fs, hop, nfft, noise=ridge[:quiet] if quiet >= 8 else None)
     res.evidence["onset"], res.evidence["first_frame"], res.evidence["quiet_frames"] = k, first, quiet
+    return res
+
+
+def search_noise_concentration(nfft: int, n_rates: int) -> float:
+    """``noise_concentration`` for the best of n_rates de-chirped spectra: the maximum of n_rates times as many cells."""
+    return float((np.log(nfft * max(1, int(n_rates)) / 1.5) + 0.58) / nfft)
+
+
+def classify_swept(scan, fs: float, noise=None) -> Interference:
+    """Kind and parameters of the interferer in ``scan`` (a ``gpsjam.ChirpScan``): ``classify``'s floor, on-frame and line
+    tests applied to the concentration BEHIND the best de-chirp.  ``noise``: a ChirpScan or Ridge of quiet frames (a
+    frame's total does not depend on the rate).
+
+    * "chirp" with ``sweep_hz_per_s`` when the de-chirped concentration passes the line test and the modal rate of the
+      frames that are on is not 0.  The sweep is the MEDIAN q of those frames times fs^2 / nfft^2: the frames that hold a
+      saw-tooth's fly-back do not concentrate at any rate and are out-voted.  Its resolution, one step of the rate grid,
+      is ``evidence["rate_resolution_hz_per_s"]``.
+    * at modal rate 0 the records are the ridge's own and the answer is ``classify``'s: "cw" for a steady tone.
+    * "pulsed", "none" and, without a line, "broadband" as ``classify``.
+
+    The one threshold that differs is the noise term of the line test: the best of n rates is the maximum of n times as
+    many noise cells, so ``search_noise_concentration`` takes the place of ``noise_concentration``."""
+    nfft, hop = int(scan.nfft), int(scan.hop)
+    first, step, n_rates = scan.rates
+    rec = np.asarray(scan.records)
+    base = classify(rec, fs, hop, nfft, noise=noise)
+    ev = base.evidence
+    unit = (float(fs) / nfft) ** 2
+    ev["rates"], ev["rate_resolution_hz_per_s"] = (int(first), int(step), int(n_rates)), unit * step
+    if base.kind in ("none", "pulsed") or "on_level" not in ev:
+        return base
+    total = rec["total"].astype(np.float64)
+    on = total > 0.5 * (ev["floor"] + ev["on_level"])                  # classify's frames that are on
+    noise_conc = search_noise_concentration(nfft, n_rates)
+    line = ev["concentration"] > max(0.5 * ev["line_min"], 2.0 * noise_conc)
+    ev["search_noise_concentration"], ev["dechirped_line"] = noise_conc, bool(line)
+    if not line:
+        return Interference("broadband", base.jnr_db, None, None, None, None, ev)
+    q = np.asarray(scan.rate)[on]
+    values, counts = np.unique(q, return_counts=True)
+    mode = int(values[counts.argmax()])
+    ev["modal_rate"], ev["modal_rate_fraction"] = mode, float((np.abs(q - mode) <= step).mean())
+    if mode == 0:
+        return base
+    ev["median_rate"] = float(np.median(q))
+    return Interference("chirp", base.jnr_db, None, ev["median_rate"] * unit, None, None, ev)
+
+
+def _scan_rates(dev, capture, nfft: int, hop: int, qmax: int):
+    """``Device.chirp`` over the rates -qmax .. qmax at step 1, in batches of at most 256 rates, joined into one
+    ChirpScan: per frame the batch with the largest peak, the smaller rate among equals."""
+    from . import ChirpScan, _ffi
+    best = None
+    for lo in range(-qmax, qmax + 1, _ffi.GJ_CHIRP_MAX_RATES):
+        n = min(_ffi.GJ_CHIRP_MAX_RATES, qmax + 1 - lo)
+        part = dev.chirp(capture, nfft=nfft, hop=hop, rates=(lo, 1, n))
+        rec = part.records.copy()
+        rec["rate_index"] += lo + qmax
+        if best is None:
+            best, scan = rec, part
+        else:
+            better = rec["peak"] > best["peak"]
+            best[better] = rec[better]
+    return ChirpScan(best, nfft, hop, (-qmax, 1, 2 * qmax + 1), scan.first_sample, scan.guard)
+
+
+def characterise_swept(dev, capture, fs: float = 2.048e6, nfft: int = 256, max_sweep_hz_per_s: float = 4.096e9,
+                       **onset_args) -> Interference:
+    """``characterise``, and where its answer leaves a fast sweep possible -- "broadband", or a "chirp" whose track less
+    than half of the frame steps follow -- the chirp-rate search over the symmetric range of integer rates that covers
+    ``max_sweep_hz_per_s`` (at most nfft^2 / 2 units of fs^2 / nfft^2), classified by ``classify_swept`` on the same
+    frames against the same quiet frames.  Returns the better-founded answer with both evidences: the search's "chirp"
+    with ``evidence["ridge"]`` = the ridge's evidence, otherwise ``characterise``'s own with ``evidence["swept"]``."""
+    res = characterise(dev, capture, fs=fs, nfft=nfft, **onset_args)
+    if not (res.kind == "broadband" or (res.kind == "chirp" and res.evidence.get("sweep_follow", 0.0) < 0.5)):
+        return res
+    hop = nfft // 2
+    unit = (float(fs) / nfft) ** 2
+    qmax = max(1, min(nfft * nfft // 2, int(np.ceil(abs(max_sweep_hz_per_s) / unit))))
+    scan = _scan_rates(dev, capture, nfft, hop, qmax)
+    if res.evidence.get("onset", -1) < 0:
+        swept = classify_swept(scan, fs)
+    else:
+        first, quiet = res.evidence["first_frame"], res.evidence["quiet_frames"]
+        swept = classify_swept(scan[first:], fs, noise=scan[:quiet] if quiet >= 8 else None)
+    if swept.kind == "chirp" and swept.evidence.get("modal_rate", 0) != 0:
+        swept.evidence["ridge"] = res.evidence
+        for key in ("onset", "first_frame", "quiet_frames"):
+            if key in res.evidence:
+                swept.evidence[key] = res.evidence[key]
+        return swept
+    res.evidence["swept"] = swept.evidence
     return res

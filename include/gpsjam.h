@@ -244,6 +244,47 @@ size_t gj_ridge_frames(size_t nbytes, size_t first_sample, int nfft, size_t hop)
 int gj_ridge_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, int nfft, size_t hop,
                  size_t n_frames, int guard, gj_ridge_frame* d_out /* [n_frames] */);
 
+/* ------------------------------------------------- chirp-rate search ---------------- */
+/* The ridge behind a de-chirp, for every rate of a grid: a sweep that crosses many bins inside ONE frame does not
+ * concentrate in any bin of that frame (gj_ridge_dev reads it as broadband); multiplied by the conjugate of a unit
+ * chirp of the right rate it is a tone again, and the rate that concentrates it best is the sweep rate, measured inside
+ * a frame instead of across frames (gpsjam/classify.py classify_swept reads the result).  For frame
+ * f = 0 .. n_frames-1 at s_f = first_sample + f*hop, with N = nfft and q_r = rate_first + r*rate_step, r = 0 .. n_rates-1:
+ *
+ *   x[t], w[n]     exactly gj_ridge_dev's (unpack convention honoured, periodic Hann, no mean removal)
+ *   m_r[n]  = (q_r * n^2) mod 2 N^2                                  exact integer arithmetic
+ *   c_r[n]  = exp(-i pi m_r[n] / N^2)
+ *   Y_fr[k] = sum_{n<N} w[n] x[s_f + n] c_r[n] exp(-2 pi i k n / N)
+ *   P_fr[k] = |Y_fr[k]|^2                                            the units of gj_ridge_dev
+ *   peak_fr = max_k P_fr[k]
+ *
+ * q counts bins per frame length: one unit is a sweep of fs/N Hz in N/fs seconds, fs^2 / N^2 Hz/s.  q > 0 de-chirps an
+ * up-sweep.  At the matching q the peak bin is the sweep's frequency at the START of the frame; its frequency at the
+ * frame's centre is bin + q/2 (in bins, modulo N).  Only integer q are searched.
+ * Limits: nfft a power of two, 16..4096, and n_rates <= GJ_CHIRP_MAX_RATES (GJ_ERR_UNSUPPORTED otherwise);
+ * n_rates >= 1, rate_step >= 1 and every |q_r| <= N^2 / 2 (beyond that the chirp's own frequency aliases); hop,
+ * first_sample, guard, n_frames (gj_ridge_frames counts the frames that fit), d_iq and d_out as gj_ridge_dev; d_peaks
+ * 4-byte aligned: GJ_ERR_INVALID otherwise.  A refused call enqueues nothing.  Needs no workspace; one launch on the
+ * context's stream.
+ * Determinism: one transform group computes all rates of one frame from that frame's bytes alone, and the rates are
+ * independent of each other: c_r is evaluated from q_r's integer phase, nothing is carried from one rate to the next.
+ * So d_peaks[f][r] is bit-identical to the `peak` of a call with the single rate q_r; frame f of a call is bit-identical
+ * to frame f-k of the same call started at first_sample + k*hop; two identical calls give identical bytes; and a call
+ * with the single rate 0 writes into the first 16 bytes of every record exactly the bytes gj_ridge_dev writes
+ * (c_0 = (1, 0), and multiplying by it is exact). */
+#define GJ_CHIRP_MAX_RATES 256
+typedef struct gj_chirp_frame {   /* 24 bytes; the first four fields are gj_ridge_frame's, taken at rate_index */
+    float total;        /* sum_k P_fr[k] */
+    float peak;         /* max_k P_fr[k] = peak_fr */
+    float second;       /* max P_fr[k] over bins whose circular distance to peak_bin is > guard; 0 if none */
+    int32_t peak_bin;   /* 0..N-1 in FFT order; equal values: smallest k */
+    int32_t rate_index; /* the r with the largest peak_fr; equal values: smallest r */
+    int32_t reserved;   /* 0 */
+} gj_chirp_frame;
+int gj_chirp_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, int nfft, size_t hop,
+                 size_t n_frames, int guard, int rate_first, int rate_step, int n_rates,
+                 gj_chirp_frame* d_out /* [n_frames] */, float* d_peaks /* [n_frames][n_rates] or NULL */);
+
 /* ------------------------------------------------- spectral kurtosis ---------------- */
 /* Floor-free per-bin interference detection (Nita & Gary's estimator; gpsjam/kurtosis.py reads it): for every bin the
  * sums of P and of P^2 over the M = frames_per_row short spectra of a row.  Gaussian noise gives SK = 1 whatever its
