@@ -29,6 +29,7 @@
 // Determinism: as ridge_kernel's, and per rate: d_peaks[f][r] depends on the frame's bytes and q_r alone.
 //
 // A translation unit of its own with its own extern "C" entry point, like k_ridge.hip.
+#include "chirp_phase.h"
 #include "stft_group.h"
 
 #include <climits>
@@ -65,9 +66,6 @@ __global__ __launch_bounds__(kBlockThreads, ChirpCfg<N>::min_waves) void chirp_k
     constexpr int TF = S::TF, B = S::B, NP = S::NP, WPF = S::WPF;
     constexpr bool XP = Cfg::xpose;
     constexpr int SPAN = XP ? X4096::kSpan : lds_span(kBlockPoints);
-    constexpr int LOG2N = __builtin_ctz((unsigned)N);
-    constexpr int PHASE_BITS = 2 * LOG2N + 1;          // m lives in [0, 2 N^2)
-    constexpr float INV_N2 = 1.0f / ((float)N * (float)N);
     __shared__ cf lds0[NP > 1 ? SPAN : 1];
     // Wave results of a transform group that spans waves (2048, 4096 points), one array per reduction as in ridge_kernel.
     // The arrays are reused once per RATE here.  Write after read still holds: red_sum / red_max of rate r are read between
@@ -113,12 +111,9 @@ __global__ __launch_bounds__(kBlockThreads, ChirpCfg<N>::min_waves) void chirp_k
         int best_bin = 0, best_rate = 0;
         for (int r = 0; r < g.n_rates; ++r) {
             const unsigned q = (unsigned)(g.rate_first + r * g.rate_step);
-            // exp(-i pi m / N^2) of a phase given modulo 2^32: the signed field of PHASE_BITS bits is m or m - 2 N^2, exact
-            // in a float, and m / N^2 an exact binary fraction (see the head of this file).  (cos, sin) of pi m / N^2.
-            const auto turn = [](unsigned ph, float& cs, float& sn) {
-                const int m = (int)(ph << (32 - PHASE_BITS)) >> (32 - PHASE_BITS);
-                sincospif((float)m * INV_N2, &sn, &cs);
-            };
+            // exp(-i pi m / N^2) of a phase given modulo 2^32, from its exactly reduced integer (chirp_phase.h, and the head
+            // of this file): (cos, sin) of pi m / N^2
+            const auto turn = [](unsigned ph, float& cs, float& sn) { chirp_turn<N>(ph, cs, sn); };
             // n = jl0 + TF s:  q n^2 = q jl0^2 + s (2 q jl0 TF) + s^2 (q TF^2), all modulo 2^32.  The last term is the same
             // in every thread: lane s of each wave evaluates it for slot s and v_readlane hands it round.
             const unsigned uj = (unsigned)jl0;

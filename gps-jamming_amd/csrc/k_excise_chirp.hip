@@ -1,0 +1,264 @@
+// Chirp-domain interference excision (gfx950): the excisor of k_excise.hip with a de-chirp in front of the forward
+// transform and the re-chirp behind the inverse one -- gj_excise_chirp_dev of include/gpsjam.h, which states the
+// definition -- and gj_chirp_rates_dev, which turns the records of the chirp-rate search (k_chirp.hip) into the per-frame
+// rates it reads.  A sweep that crosses hundreds of bins inside one frame is, behind the de-chirp of its rate, a line of
+// a few bins: the mask takes that line out and the re-chirp puts everything else back where it was.
+//
+// The structure is excise_kernel's, statement for statement: the run of consecutive frames per transform group, the
+// priming iteration, the carry of eight c2, the generic exchange schedule at 4096 points, the records, the edges copy.
+// What is this kernel's own:
+//   * the rate q_f of the frame is read by the transform group with the frame's samples (prefetched with them, clamped
+//     like them), so it is uniform in the group; the priming iteration reads the rate of the frame it primes with;
+//   * c_f[jl + TF s], the thread's sixteen factors, come from chirp_phase.h: exact integer phases, 2 + 16 / min(TF, 16)
+//     sincospif per thread and frame, nothing carried from frame to frame;
+//   * a thread's input points and output points are both jl + TF s, so the SAME sixteen factors serve both ends:
+//     v = (w x) c_f goes into the forward transform, and with z = FFT(conj(M X)) the re-chirped frame is
+//     conj(c_f) IFFT(M X) = conj(c_f) conj(z) / N = conj(z c_f) / N -- one more multiplication by c_f itself, then the
+//     parent's conjugate, 1 / N and overlap-add.  The factors are held across the two transforms: 32 registers on top of
+//     excise_kernel's, inside the 256 that two workgroups per CU leave (profiles/NOTES_excise_chirp.md has the counts);
+//   * at q_f = 0, or any multiple of 2 N^2, every factor is exactly (1, +0), both products return their other operand
+//     (up to the sign of a zero, which no later operation can tell apart) and the frame's record and bytes are
+//     gj_excise_dev's.
+// Barriers: every __syncthreads() of the loop body is executed by every thread in every iteration, clamped frames outside
+// the call included; the factor exchange is a lane permutation inside aligned sets of at most 16 lanes, with every lane
+// active.
+// Determinism: as excise_kernel, with "its own bytes" read as "its own bytes and its own q".
+//
+// A translation unit of its own with its own extern "C" entry points; the frame count is gj_excise_frames (k_excise.hip, by
+// its declaration in include/gpsjam.h), the edges copy is restated here: a kernel of another translation unit cannot be
+// launched from this one without relocatable device code.
+#include "chirp_phase.h"
+#include "stft_group.h"
+
+namespace gj {
+
+template <int N>
+struct ExciseChirpCfg {
+    // excise_kernel's ~160 live registers and the 32 of the held factors: two workgroups per CU (256 VGPRs)
+    static constexpr int min_waves = 2;
+    static constexpr int min_run = 4;   // as ExciseCfg: bounds the priming overhead at 25 %
+};
+
+struct ExciseChirpGeom {
+    unsigned long long first_sample, n_frames, per_run;
+    float offset;    // offset of the unpack convention
+    float scale2;    // scale^2
+};
+
+template <int N>
+__global__ __launch_bounds__(kBlockThreads, ExciseChirpCfg<N>::min_waves) void excise_chirp_kernel(
+    const uint8_t* __restrict__ iq, ExciseChirpGeom g, const cf* __restrict__ twtab, const float* __restrict__ wintab,
+    const int32_t* __restrict__ rate, const float* __restrict__ thr_tab, uint8_t* __restrict__ out,
+    gj_excise_frame* __restrict__ frames) {
+    using S = StftShape<N>;
+    constexpr int TF = S::TF, B = S::B, NP = S::NP, WPF = S::WPF, H = N / 2;
+    __shared__ cf lds0[NP > 1 ? lds_span(kBlockPoints) : 1];
+    constexpr int RB = WPF > 1 ? B : 1;
+    __shared__ float red_tot[RB][WPF], red_rem[RB][WPF], red_cnt[RB][WPF];
+    const int tid = threadIdx.x;
+    const StftRoles role = stft_roles<N, false>(tid);
+    const int b = role.b, jl = role.jl;   // input points, bins and output points of this thread: jl + TF s
+
+    const InnerTw ktw = inner_twiddles();
+    c2 tw[3][15], wp[8];
+    stft_load_twiddles<N>(tw, twtab, jl);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) wp[s] = stft_window_pair<N>(wintab, jl, s);
+    float thr[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) thr[s] = thr_tab[jl + TF * s];
+    const c2 koff = make_c2(-g.offset, -g.offset);
+    constexpr float inv_n = 1.0f / (float)N;
+
+    // this group's run: frames [run_first, run_end); iteration 0 primes the carry with the frame in front of it.  A frame
+    // index outside the call is clamped, for the samples and for the rate alike, and writes nothing.
+    const long long last = (long long)g.n_frames - 1;
+    const long long run_first = (long long)(((unsigned long long)blockIdx.x * B + (unsigned)b) * g.per_run);
+    const long long run_end = run_first + (long long)g.per_run;
+    auto clamped = [&](long long f) { return (unsigned long long)(f < 0 ? 0 : (f > last ? last : f)); };
+    auto frame_base = [&](long long f) { return iq + 2ull * (g.first_sample + clamped(f) * H); };
+    auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, false>(dst, base, jl); };
+
+    unsigned raw[16];   // the NEXT frame's samples and rate are fetched while the current ones are transformed
+    load_frame(raw, frame_base(run_first - 1));
+    unsigned q_next = (unsigned)rate[clamped(run_first - 1)];
+    c2 carry[8];        // second half of the previous frame's re-chirped inverse transform
+#pragma unroll
+    for (int s = 0; s < 8; ++s) carry[s] = make_c2(0.f, 0.f);
+
+    for (long long f = run_first - 1; f < run_end; ++f) {
+        const bool owned = f >= run_first && f <= last;
+        c2 v[16], c[16];
+        stft_unpack_window(v, raw, wp, koff);
+        chirp_factors<N>(c, q_next, jl);
+        if (f + 1 < run_end) {   // workgroup-uniform
+            load_frame(raw, frame_base(f + 1));
+            q_next = (unsigned)rate[clamped(f + 1)];
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], c[s]);
+
+        stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
+
+        // this thread's bins jl + TF s: power, mask, conjugate for the way back (excise_kernel's arithmetic)
+        float tot = 0.f, rem = 0.f, cnt = 0.f;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+#pragma clang fp contract(off)
+            const float p = __builtin_fmaf(v[s].x, v[s].x, v[s].y * v[s].y) * g.scale2;
+            const bool cut = p > thr[s];   // strict; false for a NaN threshold
+            tot += p;
+            rem += cut ? p : 0.f;
+            cnt += cut ? 1.f : 0.f;        // at most 4096: exact in float
+            v[s] = cut ? make_c2(0.f, 0.f) : make_c2(v[s].x, -v[s].y);
+        }
+        const auto add = [](float a, float c0) { return a + c0; };
+        tot = group_reduce_f<S::G>(tot, add);
+        rem = group_reduce_f<S::G>(rem, add);
+        cnt = group_reduce_f<S::G>(cnt, add);
+        if constexpr (WPF > 1) {
+            waves_post(red_tot[b], tid, tot);
+            waves_post(red_rem[b], tid, rem);
+            waves_post(red_cnt[b], tid, cnt);
+            __syncthreads();
+            tot = waves_fold(red_tot[b], add);
+            rem = waves_fold(red_rem[b], add);
+            cnt = waves_fold(red_cnt[b], add);
+        }
+        if (frames && owned && jl == 0) {   // one lane per transform group
+            gj_excise_frame r;
+            r.total = tot;
+            r.removed = rem;
+            r.n_excised = (int)cnt;
+            r.reserved = 0;
+            frames[f] = r;
+        }
+
+        stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
+
+        // y_f = conj(v c_f) / N; samples [f H, (f + 1) H) of the range = previous frame's second half + this one's first
+#pragma unroll
+        for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], c[s]);
+        const bool store = owned && f >= 1;
+        uint8_t* dst = out + 2ull * ((unsigned long long)(f < 0 ? 0 : f) * H) + 2 * jl;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const float yi = fmaf(v[s].x, inv_n, carry[s].x) + g.offset;
+            const float yq = fmaf(-v[s].y, inv_n, carry[s].y) + g.offset;
+            carry[s] = make_c2(v[s + 8].x * inv_n, -v[s + 8].y * inv_n);
+            if (store) {
+                const unsigned ui = (unsigned)fminf(fmaxf(__builtin_rintf(yi), 0.f), 255.f);
+                const unsigned uq = (unsigned)fminf(fmaxf(__builtin_rintf(yq), 0.f), 255.f);
+                struct __attribute__((packed, aligned(1))) U16 { uint16_t v; };
+                reinterpret_cast<U16*>(dst + 2 * TF * s)->v = (uint16_t)(ui | (uq << 8));
+            }
+        }
+    }
+}
+
+// the first half frame [0, n_head) and the tail [tail_first, n_bytes) come back as they went in
+__global__ __launch_bounds__(256) void excise_chirp_edges_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
+                                                                 unsigned long long n_head, unsigned long long tail_first,
+                                                                 unsigned long long n_bytes) {
+    const unsigned long long n_tail = n_bytes - tail_first;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_head + n_tail;
+         i += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long at = i < n_head ? i : tail_first + (i - n_head);
+        out[at] = src[at];
+    }
+}
+
+// d_rate[f] = rate_first + rate_index_f * rate_step where the search concentrated the frame, 0 elsewhere
+__global__ __launch_bounds__(256) void chirp_rates_kernel(const gj_chirp_frame* __restrict__ scan, unsigned long long n_frames,
+                                                          int rate_first, int rate_step, float min_concentration,
+                                                          int32_t* __restrict__ rate) {
+    for (unsigned long long f = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; f < n_frames;
+         f += (unsigned long long)gridDim.x * blockDim.x) {
+        const float total = scan[f].total, peak = scan[f].peak;
+        float need;
+        {
+#pragma clang fp contract(off)
+            need = min_concentration * total;   // one float multiply, rounded once
+        }
+        const bool on = total > 0.f && peak >= need;   // false for a NaN on either side
+        const unsigned q = (unsigned)rate_first + (unsigned)scan[f].rate_index * (unsigned)rate_step;   // modulo 2^32
+        rate[f] = on ? (int32_t)q : 0;
+    }
+}
+
+template <int N>
+static void excise_chirp_launch(gj_ctx* ctx, const uint8_t* d_iq, ExciseChirpGeom g, const int32_t* d_rate, const float* d_thr,
+                                uint8_t* d_out, gj_excise_frame* d_frames) {
+    constexpr unsigned long long B = kBlockPoints / N;
+    // one round of transform groups; runs of equal length, the length from the frame count alone (as excise_launch)
+    const unsigned long long slots = (unsigned long long)ctx->num_cus * ExciseChirpCfg<N>::min_waves * B;
+    unsigned long long per = (g.n_frames + slots - 1) / slots;
+    if (per < (unsigned long long)ExciseChirpCfg<N>::min_run) per = ExciseChirpCfg<N>::min_run;
+    if (per > g.n_frames) per = g.n_frames;
+    g.per_run = per;
+    const unsigned long long runs = (g.n_frames + per - 1) / per;
+    const unsigned grid = (unsigned)((runs + B - 1) / B);
+    hipLaunchKernelGGL(excise_chirp_kernel<N>, dim3(grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle,
+                       window_table(ctx, N), d_rate, d_thr, d_out, d_frames);
+}
+
+}   // namespace gj
+
+using namespace gj;
+
+extern "C" {
+
+int gj_excise_chirp_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples, int nfft,
+                        const int32_t* d_rate, const float* d_threshold, uint8_t* d_out, gj_excise_frame* d_frames) {
+    if (!ctx) return GJ_ERR_INVALID;
+    Guard lock(ctx);
+    if (int rc = stft_check_nfft(ctx, nfft)) return rc;
+    if (!d_iq || !d_out || !d_threshold || !d_rate) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+    if (int rc = stft_check_capture(ctx, d_iq)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_rate) & 3) return fail(ctx, GJ_ERR_INVALID, "rates must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
+    const size_t total = nbytes / 2;
+    if (n_samples < (size_t)nfft) return fail(ctx, GJ_ERR_INVALID, "n_samples %zu is less than one frame of %d points", n_samples, nfft);
+    if (first_sample > total || n_samples > total - first_sample)
+        return fail(ctx, GJ_ERR_INVALID, "samples %zu .. +%zu run past the capture's %zu", first_sample, n_samples, total);
+    {   // frames read their neighbours: the output may not lie in the capture
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_iq), a1 = a0 + nbytes;
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + 2 * n_samples;
+        if (o0 < a1 && a0 < o1) return fail(ctx, GJ_ERR_INVALID, "d_out overlaps the capture");
+    }
+    ExciseChirpGeom g;
+    g.first_sample = first_sample;
+    g.n_frames = gj_excise_frames(n_samples, nfft);
+    g.per_run = 0;
+    g.offset = 0.5f * (float)ctx->off2;
+    g.scale2 = (float)(ctx->scale * ctx->scale);
+    stft_dispatch(nfft, [&](auto n) { excise_chirp_launch<decltype(n)::value>(ctx, d_iq, g, d_rate, d_threshold, d_out, d_frames); });
+    GJ_LAUNCH_CHECK(ctx);
+    const unsigned long long h2 = (unsigned long long)nfft;   // bytes of half a frame
+    const unsigned long long tail_first = g.n_frames * h2, n_bytes = 2ull * n_samples;
+    const unsigned long long edge = h2 + (n_bytes - tail_first);   // < 3 nfft bytes
+    hipLaunchKernelGGL(excise_chirp_edges_kernel, dim3((unsigned)((edge + 255) / 256)), dim3(256), 0, ctx->stream,
+                       d_iq + 2 * first_sample, d_out, h2, tail_first, n_bytes);
+    GJ_LAUNCH_CHECK(ctx);
+    return GJ_OK;
+}
+
+int gj_chirp_rates_dev(gj_ctx* ctx, const gj_chirp_frame* d_scan, size_t n_frames, int rate_first, int rate_step,
+                       float min_concentration, int32_t* d_rate) {
+    if (!ctx) return GJ_ERR_INVALID;
+    Guard lock(ctx);
+    if (!d_scan || !d_rate) return fail(ctx, GJ_ERR_INVALID, "null buffer");
+    if (reinterpret_cast<uintptr_t>(d_scan) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_rate) & 3) return fail(ctx, GJ_ERR_INVALID, "rates must be 4-byte aligned");
+    if (n_frames == 0) return fail(ctx, GJ_ERR_INVALID, "n_frames must be >= 1");
+    if (rate_step < 1) return fail(ctx, GJ_ERR_INVALID, "rate_step must be >= 1");
+    const unsigned long long blocks = ((unsigned long long)n_frames + 255) / 256;
+    const unsigned long long cap = (unsigned long long)ctx->num_cus * 8;
+    hipLaunchKernelGGL(chirp_rates_kernel, dim3((unsigned)(blocks < cap ? blocks : cap)), dim3(256), 0, ctx->stream, d_scan,
+                       (unsigned long long)n_frames, rate_first, rate_step, min_concentration, d_rate);
+    GJ_LAUNCH_CHECK(ctx);
+    return GJ_OK;
+}
+
+}   // extern "C"

@@ -1007,7 +1007,65 @@ class Device:
                     b.free()
         return cleaned, rec
 
+    def excise_chirp(self, raw, threshold, rates, nfft: int = 1024, first_sample: int = 0, n_samples: Optional[int] = None):
+        """Chirp-domain excision (gj_excise_chirp_dev): ``excise`` with every frame de-chirped by its own rate in front
+        of the mask and re-chirped behind it, so that a sweep which crosses many bins inside a frame is cut as the few
+        bins of its de-chirped line.  ``rates``: one integer per frame (bins per frame length, the unit of ``chirp``; 0
+        leaves the frame to the plain excisor), a host array whose length must be the frame count, or a device buffer
+        of int32.  ``raw``, ``threshold`` and the result ``(cleaned, records)`` as ``excise``; the records are taken
+        behind the de-chirp."""
+        nfft, first_sample = int(nfft), int(first_sample)
+        own = None if isinstance(raw, Capture) else Capture(self, raw)
+        cap = raw if own is None else own
+        d_thr = d_rate = d_out = d_rec = None
+        try:
+            if not cap.ptr and cap.nbytes:
+                raise ValueError("the capture has been freed")
+            if n_samples is None:
+                n_samples = max(0, cap.nsamples - first_sample)
+            n_samples = int(n_samples)
+            frames = excise_frames(n_samples, nfft)
+            if isinstance(threshold, (DevBuf, int)) or hasattr(threshold, "data_ptr"):
+                thr = threshold
+            else:
+                host = np.ascontiguousarray(threshold, dtype=np.float32).reshape(-1)
+                if host.size != nfft:
+                    raise ValueError(f"threshold holds {host.size} values, nfft is {nfft}")
+                thr = d_thr = DevBuf(self, 4 * nfft).upload(host)
+            if isinstance(rates, (DevBuf, int)) or hasattr(rates, "data_ptr"):
+                rate = rates
+            else:
+                host = np.asarray(rates).reshape(-1)
+                if host.size != frames:
+                    raise ValueError(f"rates holds {host.size} values, the range has {frames} frames of {nfft} points")
+                if host.size and not np.issubdtype(host.dtype, np.integer):
+                    raise TypeError("rates must be integers")
+                rate = d_rate = DevBuf(self, max(4 * frames, 4)).upload(host.astype(np.int32))
+            self._count("excise_chirp")
+            d_out = DevBuf(self, max(2 * n_samples, 1))
+            d_rec = DevBuf(self, max(frames, 1) * EXCISE_DTYPE.itemsize)
+            self.excise_chirp_dev(cap, cap.nbytes, first_sample, n_samples, nfft, rate, thr, d_out, d_rec)
+            rec = d_rec.download(EXCISE_DTYPE, frames)
+            cleaned, d_out = Capture.from_device(self, d_out, 2 * n_samples), None
+        finally:
+            for b in (d_thr, d_rate, d_rec, d_out, own):
+                if b is not None:
+                    b.free()
+        return cleaned, rec
+
     # ------------------------------------------------------------------ device pointers
+    def excise_chirp_dev(self, d_iq, nbytes, first_sample, n_samples, nfft, d_rate, d_threshold, d_out, d_frames=None):
+        """gj_excise_chirp_dev: gj_excise_dev with the int32 rate of every frame in d_rate, on the context's stream."""
+        self._check(self._lib.gj_excise_chirp_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples),
+                                                  int(nfft), _ptr(d_rate), _ptr(d_threshold), _ptr(d_out),
+                                                  _ptr(d_frames) or None))
+
+    def chirp_rates_dev(self, d_scan, n_frames, rate_first, rate_step, min_concentration, d_rate):
+        """gj_chirp_rates_dev: the int32 rate of every frame of a gj_chirp_dev scan (0 where peak < min_concentration *
+        total) into d_rate, on the context's stream."""
+        self._check(self._lib.gj_chirp_rates_dev(self._ctx, _ptr(d_scan), int(n_frames), int(rate_first), int(rate_step),
+                                                 float(min_concentration), _ptr(d_rate)))
+
     def excise_dev(self, d_iq, nbytes, first_sample, n_samples, nfft, d_threshold, d_out, d_frames=None):
         """gj_excise_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 16-byte record (EXCISE_DTYPE) per
         frame into d_frames, on the context's stream."""

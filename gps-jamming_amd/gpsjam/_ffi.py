@@ -210,6 +210,8 @@ SIGNATURES = {
     "gj_sk_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _i, _sz, _vp, _vp, _vp]),
     "gj_excise_frames": (_sz, [_sz, _i]),
     "gj_excise_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp]),
+    "gj_excise_chirp_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp]),
+    "gj_chirp_rates_dev": (_i, [_vp, _vp, _sz, _i, _i, _f, _vp]),
     "gj_byte_histogram_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),
     "gj_amp_stats_dev": (_i, [_vp, _vp, _sz, _f, _vp]),
     "gj_amp_stats_u8": (_i, [_vp, _vp, _sz, _f, C.POINTER(AmpStats), _pf]),

@@ -363,6 +363,49 @@ int gj_excise_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_
                   const float* d_threshold /* [nfft] */, uint8_t* d_out /* [2*n_samples] */,
                   gj_excise_frame* d_frames /* [F] or NULL */);
 
+/* ------------------------------------------------- chirp-domain excision ------------ */
+/* De-chirp, notch, re-chirp: gj_excise_dev with every frame multiplied by the conjugate of a unit chirp of ITS OWN
+ * rate in front of the transform and by the chirp itself behind the inverse.  A sweep that crosses hundreds of bins
+ * inside one frame is a line of a few bins behind the de-chirp of its rate (gj_chirp_dev measures that rate), so the
+ * mask removes the sweep and little else; gj_excise_dev sees it smeared and cuts nothing, or the signal with it.
+ * With F, h, s_f, x, w, scale and the output rule exactly gj_excise_dev's, and c exactly gj_chirp_dev's:
+ *
+ *   q_f     = d_rate[f]                                 DEVICE int32[F]; any value, the phase is taken modulo 2 N^2
+ *   c_f[n]  = exp(-i pi ((q_f n^2) mod 2 N^2) / N^2)      exact integer arithmetic
+ *   X_f[k]  = sum_n w[n] x[s_f + n] c_f[n] exp(-2 pi i k n / N)
+ *   P_f[k]  = |X_f[k]|^2 * scale^2
+ *   M_f[k]  = 0 if P_f[k] > thr[k] else 1                strict; +inf, negative and NaN as gj_excise_dev
+ *   y_f[n]  = conj(c_f[n]) * IFFT_N(M_f * X_f)[n]
+ *   y[t]    = y_{f-1}[t - s_{f-1}] + y_f[t - s_f]
+ *
+ * |c| = 1, so an all-ones mask still gives y = x whatever the rates.  The records are gj_excise_frame, taken in the
+ * de-chirped domain.  Edges, length and byte coordinates as gj_excise_dev: exactly 2*n_samples bytes are written.
+ * One unit of q is fs^2 / N^2 Hz/s; only integer rates exist, and a frame has one rate.  A threshold that follows the
+ * passband's shape is of little use here: the de-chirp smears that shape over the bins.
+ * Refusals: those of gj_excise_dev, and a null d_rate or one that is not 4-byte aligned (GJ_ERR_INVALID).  No rate
+ * VALUE is refused; the host never reads d_rate.  A refused call enqueues nothing.  Needs no workspace; enqueues on the
+ * context's stream (two launches) and returns.
+ * Determinism: a frame's spectrum, mask and re-chirped inverse depend on that frame's bytes and its own q_f alone, so
+ * a call started k*h samples later with d_rate + k reproduces the overlapping interior bytes and the records of the
+ * shared frames bit for bit; two identical calls give identical bytes; and with every q_f = 0, or any multiple of
+ * 2 N^2, the call writes exactly the bytes and records of gj_excise_dev (every factor is then exactly (1, 0)). */
+int gj_excise_chirp_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples, int nfft,
+                        const int32_t* d_rate /* [F] */, const float* d_threshold /* [nfft] */,
+                        uint8_t* d_out /* [2*n_samples] */, gj_excise_frame* d_frames /* [F] or NULL */);
+/* The rates for gj_excise_chirp_dev out of a gj_chirp_dev scan, without a pass through the host.  Scan the same
+ * first_sample at hop = nfft/2 over the grid (rate_first, rate_step, n_rates): frame f of the scan is frame f of the
+ * excisor.  For f = 0 .. n_frames-1, with total, peak and rate_index the fields of d_scan[f]:
+ *
+ *   d_rate[f] = rate_first + rate_index * rate_step   if total > 0 and peak >= fl32(min_concentration * total)
+ *             = 0                                     otherwise (also when a NaN is compared)
+ *
+ * fl32(.) is ONE float32 multiplication.  The sum is taken modulo 2^32.  Frames the search could not concentrate --
+ * noise, a quiet lead-in, the frame that holds a saw-tooth's fly-back -- are thus excised as plain frames.
+ * GJ_ERR_INVALID: a null or not 4-byte aligned d_scan or d_rate, n_frames == 0, rate_step < 1.  A refused call enqueues
+ * nothing.  One launch on the context's stream. */
+int gj_chirp_rates_dev(gj_ctx* ctx, const gj_chirp_frame* d_scan, size_t n_frames, int rate_first, int rate_step,
+                       float min_concentration, int32_t* d_rate /* [n_frames] */);
+
 /* raw-byte histogram of every `stride`-th byte (widmo_plot.py:35,85: stride 100,
  * 256 bins).  Strided per chunk exactly like raw_chunk[::100]. */
 int gj_byte_histogram_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t chunk_samples,
