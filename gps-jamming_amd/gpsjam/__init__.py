@@ -27,7 +27,8 @@ from ._ffi import (AmpStats, GpsJamError, GpsJamLibraryError, Onset, SynthParams
 __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "device_count",
            "library_path", "as_u8", "default_device", "read_capture", "resident_capture",
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
-           "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE"]
+           "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE",
+           "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -180,6 +181,17 @@ def excise_frames(n_samples: int, nfft: int) -> int:
     if int(n_samples) < 0 or not -2 ** 31 <= int(nfft) < 2 ** 31:
         return 0
     return int(_ffi.load().gj_excise_frames(int(n_samples), int(nfft)))
+
+
+BLANK_BLOCK = _ffi.GJ_BLANK_BLOCK
+BLANK_DTYPE = np.dtype([("total", np.uint64), ("removed", np.uint64), ("n_blanked", np.int32), ("n_rising", np.int32)])
+
+
+def blank_blocks(n_samples: int) -> int:
+    """Records of the pulse blanker over n_samples: one per BLANK_BLOCK samples, the last one ragged (gj_blank_blocks)."""
+    if not 0 <= int(n_samples) < 2 ** 64:
+        return 0
+    return int(_ffi.load().gj_blank_blocks(int(n_samples)))
 
 
 class Ridge:
@@ -1053,7 +1065,44 @@ class Device:
                     b.free()
         return cleaned, rec
 
+    def blank(self, raw, threshold: float, window: int = 16, guard: int = 8, first_sample: int = 0,
+              n_samples: Optional[int] = None):
+        """Time-domain pulse blanking (gj_blank_dev): samples first_sample .. + n_samples of ``raw`` (default: to the
+        end) with every sample within ``guard`` of a ``window``-sample stretch whose mean power exceeds ``threshold``
+        put to mid-level.  ``raw``: host bytes (uploaded once) or a resident ``Capture``; ``threshold``: a mean power per
+        sample in LSB^2, the unit of ``onset(...).noise_power`` (+inf: never).  Returns ``(cleaned, records)``: the
+        cleaned range as a resident ``Capture`` of its own (the caller frees it) and one BLANK_DTYPE record per
+        BLANK_BLOCK samples."""
+        first_sample = int(first_sample)
+        own = None if isinstance(raw, Capture) else Capture(self, raw)
+        cap = raw if own is None else own
+        d_out = d_rec = None
+        try:
+            if not cap.ptr and cap.nbytes:
+                raise ValueError("the capture has been freed")
+            if n_samples is None:
+                n_samples = max(0, cap.nsamples - first_sample)
+            n_samples = int(n_samples)
+            blocks = blank_blocks(n_samples)
+            self._count("blank")
+            d_out = DevBuf(self, max(2 * n_samples, 1))
+            d_rec = DevBuf(self, max(blocks, 1) * BLANK_DTYPE.itemsize)
+            self.blank_dev(cap, cap.nbytes, first_sample, n_samples, window, guard, threshold, d_out, d_rec)
+            rec = d_rec.download(BLANK_DTYPE, blocks)
+            cleaned, d_out = Capture.from_device(self, d_out, 2 * n_samples), None
+        finally:
+            for b in (d_rec, d_out, own):
+                if b is not None:
+                    b.free()
+        return cleaned, rec
+
     # ------------------------------------------------------------------ device pointers
+    def blank_dev(self, d_iq, nbytes, first_sample, n_samples, window, guard, threshold, d_out, d_blocks=None):
+        """gj_blank_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 24-byte record (BLANK_DTYPE) per
+        BLANK_BLOCK samples into d_blocks, on the context's stream."""
+        self._check(self._lib.gj_blank_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples), int(window),
+                                           int(guard), float(threshold), _ptr(d_out), _ptr(d_blocks) or None))
+
     def excise_chirp_dev(self, d_iq, nbytes, first_sample, n_samples, nfft, d_rate, d_threshold, d_out, d_frames=None):
         """gj_excise_chirp_dev: gj_excise_dev with the int32 rate of every frame in d_rate, on the context's stream."""
         self._check(self._lib.gj_excise_chirp_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples),

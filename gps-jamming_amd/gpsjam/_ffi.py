@@ -146,6 +146,11 @@ class ExciseFrame(C.Structure):
     _fields_ = [("total", C.c_float), ("removed", C.c_float), ("n_excised", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BlankBlock(C.Structure):
+    """gj_blank_block: one GJ_BLANK_BLOCK-sample record of the pulse blanker (include/gpsjam.h)."""
+    _fields_ = [("total", C.c_uint64), ("removed", C.c_uint64), ("n_blanked", C.c_int32), ("n_rising", C.c_int32)]
+
+
 GJ_CP_ODD_CHUNK_ZERO = 1
 GJ_WELCH_SHIFT = 1
 GJ_MAX_ANTENNAS = 16
@@ -155,6 +160,7 @@ GJ_COMM_ID_BYTES = 128
 GJ_VERSION = 150
 GJ_CAF_MAX_BINS = 4096
 GJ_CHIRP_MAX_RATES = 256
+GJ_BLANK_BLOCK = 4096
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
 _pf, _psz = C.POINTER(C.c_float), C.POINTER(C.c_size_t)
@@ -212,6 +218,8 @@ SIGNATURES = {
     "gj_excise_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp]),
     "gj_excise_chirp_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp]),
     "gj_chirp_rates_dev": (_i, [_vp, _vp, _sz, _i, _i, _f, _vp]),
+    "gj_blank_blocks": (_sz, [_sz]),
+    "gj_blank_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _f, _vp, _vp]),
     "gj_byte_histogram_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),
     "gj_amp_stats_dev": (_i, [_vp, _vp, _sz, _f, _vp]),
     "gj_amp_stats_u8": (_i, [_vp, _vp, _sz, _f, C.POINTER(AmpStats), _pf]),

@@ -406,6 +406,51 @@ int gj_excise_chirp_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t 
 int gj_chirp_rates_dev(gj_ctx* ctx, const gj_chirp_frame* d_scan, size_t n_frames, int rate_first, int rate_step,
                        float min_concentration, int32_t* d_rate /* [n_frames] */);
 
+/* ------------------------------------------------- time-domain pulse blanking ------- */
+/* The pulse blanker a receiver puts in front of its FFT excisor: a cleaned capture, uint8 I/Q again, with every sample
+ * near a window of excess power put to mid-level (simulate/frontend/jammers/pulsedJammer.py and every sweep that crosses
+ * the band in a few samples; gpsjam/mitigate.py builds the threshold).  A pulse shorter than a frame is spread over every
+ * bin of that frame: gj_excise_dev either wipes the frame or lets the pulse through.  For a range of n_samples I/Q
+ * pairs, t = 0 .. n_samples-1 relative to the range (sample t of the range is sample first_sample + t of the capture),
+ * with W = window, G = guard and o2 = 2*offset of gj_set_unpack (an integer):
+ *
+ *   e[t] = (2 I_t - o2)^2 + (2 Q_t - o2)^2            4 |x|^2 in LSB^2, an exact integer; 0 outside the range, even
+ *                                                     where the capture has bytes there
+ *   S[t] = sum of e[u], u = t - W/2 .. t - W/2 + W - 1     W/2 rounded down
+ *   T    = floor(4 W threshold)                       in double, from the float32 threshold
+ *   D[t] = S[t] > T                                   strict
+ *   B[t] = OR of D[u] over |u - t| <= G, u inside the range
+ *
+ * threshold is a mean power per sample in LSB^2, the unit of gj_onset.noise_power.  +inf, or any T of 2^63 or more,
+ * never blanks.  A result depends on the bytes of its range alone.
+ * Output: d_out[2*n_samples] is range-relative, byte 0 is I of first_sample.  Where B[t] is false: the two input bytes,
+ * unchanged.  Where B[t] is true and o2 is even: both bytes are o2/2.  Where B[t] is true and o2 is odd the mid-level is
+ * not a byte and the two nearest bytes alternate on the ABSOLUTE sample index:
+ *   I = (o2-1)/2 + ((first_sample + t) & 1),   Q = (o2-1)/2 + ((first_sample + t + 1) & 1)
+ * so that a blanked stretch has mean `offset` exactly and the residue sits at +-fs/2.  The call writes exactly
+ * 2*n_samples bytes; length and byte coordinates are the range's, as in gj_excise_dev.
+ * d_blocks (optional, may be NULL) receives one record per GJ_BLANK_BLOCK samples of the range, the last one ragged.
+ * Limits: 1 <= window <= 1024 and 0 <= guard <= 1024 (GJ_ERR_UNSUPPORTED otherwise), so that a window sum stays under
+ * 2^30.  GJ_ERR_INVALID: n_samples == 0, a range that runs past the capture, a null or odd d_iq, a null d_out, a d_blocks
+ * that is not 8-byte aligned, a NaN or negative threshold, d_out[0, 2*n_samples) overlapping d_iq[0, nbytes) (windows
+ * read their neighbours: in place is wrong).  first_sample may be odd.  A refused call enqueues nothing.  Needs no
+ * workspace; one launch on the context's stream, then the call returns.
+ * Determinism: everything is integer arithmetic.  Two identical calls give identical bytes; a call on a sub-range
+ * reproduces the bytes of the larger call wherever t is at least W/2 + G from the sub-range's start and at least W + G
+ * from its end; and bytes and records equal those of the definition evaluated on the CPU, every one of them. */
+#define GJ_BLANK_BLOCK 4096        /* samples per record */
+typedef struct gj_blank_block {    /* 24 bytes, all exact integers */
+    uint64_t total;     /* sum of e[t] over the block's samples */
+    uint64_t removed;   /* sum of e[t] over its blanked samples */
+    int32_t n_blanked;  /* blanked samples in the block */
+    int32_t n_rising;   /* t in the block with B[t] and (t == 0 or !B[t-1]) */
+} gj_blank_block;
+/* records of the blanker: ceil(n_samples / GJ_BLANK_BLOCK); pure host arithmetic, no context */
+size_t gj_blank_blocks(size_t n_samples);
+int gj_blank_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples, int window,
+                 int guard, float threshold, uint8_t* d_out /* [2*n_samples] */,
+                 gj_blank_block* d_blocks /* [gj_blank_blocks(n_samples)] or NULL */);
+
 /* raw-byte histogram of every `stride`-th byte (widmo_plot.py:35,85: stride 100,
  * 256 bins).  Strided per chunk exactly like raw_chunk[::100]. */
 int gj_byte_histogram_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t chunk_samples,
