@@ -7,8 +7,10 @@
 // owns tiles of two record blocks (8192 samples) and walks a tile in five steps:
 //   1. every thread loads 16-byte chunks (8 samples) of the tile and of its halo, lane after lane, and keeps them in
 //      registers; e = 4 |x|^2 per sample, an inclusive prefix sum inside the chunk, a wave scan of the chunk totals and
-//      one LDS step across waves and chunk rows give P[x] = sum of e up to x as uint32 in LDS.  P wraps; every window sum
-//      is under 2^30, so a difference of two P is exact;
+//      one LDS step across waves and chunk rows give P[x] = sum of e up to x as uint32 in LDS.  e is at most 2 * 510^2 =
+//      520 200 (offsets 0 and 255; 130 050 at 127.5), so over the 12 288 samples of a pass P reaches 6.4e9 and WRAPS
+//      there (never at 127.5 or 128: 1.6e9).  A window sum is 1024 * 520 200 = 5.3e8 < 2^30 at most, so a difference
+//      of two P is exact all the same;
 //   2. a lane per sample: S = P[x - h + W - 1] - P[x - h - 1], D = S > T, and a ballot packs 64 D into one word;
 //   3. an exclusive scan of the words' bit counts: the number of D in any interval is two look-ups, so the dilation by
 //      `guard` costs the same whatever the guard; B again a lane per sample and a ballot per 64;
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(kBlankThreads, 3) void blank_kernel(const uint8_t* 
         __syncthreads();   // also the end of the tile: every LDS array is rewritten only behind a later barrier's wait
         const unsigned long long block = tile * kBlankTileBlocks + (unsigned)wave;
         if (blocks && lane == 0 && wave < kBlankTileBlocks && block < g.n_blocks) {
-            unsigned total = 0, removed = 0;   // a block's sum of e is under 2^32: 4096 * 2 * 510^2 at most
+            unsigned total = 0, removed = 0;   // a block's sum of e fits at every offset: 4096 * 2 * 510^2 = 2 130 739 200 at most (offsets 0, 255)
 #pragma unroll
             for (int w = 0; w < kBlankWaves; ++w) total += sums[w][wave], removed += sums[w][kBlankTileBlocks + wave];
             gj_blank_block rec;

@@ -27,13 +27,13 @@ __device__ __forceinline__ void acc_moments(const uint4& q, unsigned& s2, unsign
     s1 = __builtin_amdgcn_udot4(q.w, 0x01010101u, s1, false);
 }
 
-// sum u^2 and sum u over the bytes [begin, end) of `p`, whole workgroup cooperating;
-// result valid in thread 0.
-__device__ __forceinline__ void block_byte_moments(const uint8_t* __restrict__ p, size_t begin, size_t end,
-                                                   unsigned long long& s2_out, unsigned long long& s1_out) {
-    __shared__ unsigned long long red[2][kScanThreads / 64];
+// One thread's share of sum u^2 and sum u over the bytes [begin, end) of `p`, ADDED to s2 / s1.  32-bit sums
+// (v_dot4_u32_u8 does not clamp): a thread sees 1/256 of the range, so [begin, end) may hold at most
+// kMomentSpan bytes -- 4096 per thread x 255^2 = 2.7e8 -- for the sums not to wrap.
+constexpr size_t kMomentSpan = 1u << 20;
+__device__ __forceinline__ void thread_byte_moments(const uint8_t* __restrict__ p, size_t begin, size_t end,
+                                                    unsigned& s2, unsigned& s1) {
     const int tid = threadIdx.x;
-    unsigned s2 = 0, s1 = 0;
     size_t a0 = (begin + 15) & ~size_t(15);
     size_t a1 = end & ~size_t(15);
     if (a0 > a1) { a0 = end; a1 = end; }
@@ -51,7 +51,15 @@ __device__ __forceinline__ void block_byte_moments(const uint8_t* __restrict__ p
         uint4 w0 = v[i];
         acc_moments(w0, s2, s1);
     }
-    unsigned long long t2 = wave_sum_u64(s2), t1 = wave_sum_u64(s1);
+}
+
+// the threads' sums added up over the workgroup; result valid in thread 0
+__device__ __forceinline__ void block_reduce_moments(unsigned long long t2, unsigned long long t1,
+                                                     unsigned long long& s2_out, unsigned long long& s1_out) {
+    __shared__ unsigned long long red[2][kScanThreads / 64];
+    const int tid = threadIdx.x;
+    t2 = wave_sum_u64(t2);
+    t1 = wave_sum_u64(t1);
     if ((tid & 63) == 0) { red[0][tid >> 6] = t2; red[1][tid >> 6] = t1; }
     __syncthreads();
     if (tid == 0) {
@@ -59,6 +67,30 @@ __device__ __forceinline__ void block_byte_moments(const uint8_t* __restrict__ p
         s1_out = red[1][0] + red[1][1] + red[1][2] + red[1][3];
     }
     __syncthreads();
+}
+
+// sum u^2 and sum u over the bytes [begin, end) of `p`, whole workgroup cooperating; result valid in thread 0.
+// For ranges of at most kMomentSpan bytes (K1's and the fused scan's 64-KiB tiles).
+__device__ __forceinline__ void block_byte_moments(const uint8_t* __restrict__ p, size_t begin, size_t end,
+                                                   unsigned long long& s2_out, unsigned long long& s1_out) {
+    unsigned s2 = 0, s1 = 0;
+    thread_byte_moments(p, begin, end, s2, s1);
+    block_reduce_moments(s2, s1, s2_out, s1_out);
+}
+
+// The same over a range of ANY length (the noise span a part of a split capture brings along: the caller chooses
+// noise_samples): the 32-bit sums are carried into 64 bits after every kMomentSpan bytes.
+__device__ __forceinline__ void block_byte_moments_long(const uint8_t* __restrict__ p, size_t begin, size_t end,
+                                                        unsigned long long& s2_out, unsigned long long& s1_out) {
+    unsigned long long t2 = 0, t1 = 0;
+    for (size_t b = begin; b < end; b += kMomentSpan) {
+        const size_t e = end - b < kMomentSpan ? end : b + kMomentSpan;
+        unsigned s2 = 0, s1 = 0;
+        thread_byte_moments(p, b, e, s2, s1);
+        t2 += s2;
+        t1 += s1;
+    }
+    block_reduce_moments(t2, t1, s2_out, s1_out);
 }
 
 __device__ __forceinline__ float power_from_moments(unsigned long long s2, unsigned long long s1, size_t npairs,
@@ -597,7 +629,7 @@ __global__ __launch_bounds__(kScanThreads) void stream_scan_kernel(const uint8_t
     // that starts with the span needs nothing here: the tail adds up this kernel's own 512-sample block sums.
     if (blockIdx.x == noise_block) {
         unsigned long long s2 = 0, s1 = 0;
-        block_byte_moments(noise_src, 0, (size_t)2 * noise_samples, s2, s1);
+        block_byte_moments_long(noise_src, 0, (size_t)2 * noise_samples, s2, s1);
         if (threadIdx.x == 0)
             sc->noise_S = (unsigned long long)(4ll * (long long)s2 - 4ll * up.off2 * (long long)s1 + (long long)up.off2 * up.off2 * (2ll * noise_samples));
         return;
@@ -614,7 +646,7 @@ __global__ __launch_bounds__(kScanThreads) void stream_scan_kernel(const uint8_t
     const uint4* v = reinterpret_cast<const uint4*>(iq + b0);
     // Everything comes from the per-sample m = (2I-255)^2 + (2Q-255)^2 (exact integers, three instructions per
     // sample): amplitudes are sqrt(m) / 255, chunk power is sum(m) / (4 n), the K4 sums are sums of m.
-    unsigned S = 0;                                                // per lane: <= 16 vectors x 8 x 130050 < 2^32
+    unsigned S = 0;                                                // per lane: <= 16 vectors x 8 x 520200 = 6.7e7 < 2^32 (any offset)
     double sum = 0.0;                                              // sum of sqrt(m); scaled by 1/255 once per tile
     long long first = 0x7fffffffffffffffll;
     unsigned k2 = 0x00020002u, km255 = pk_minus_off2(up.off2);
@@ -945,12 +977,29 @@ __device__ void tail_onset_range(const TailArgs& A, unsigned w, unsigned* pre_c,
     unsigned long long first = ~0ull, guard = ~0ull;
     unsigned below = 0;
     const uint16_t* iq16_all = reinterpret_cast<const uint16_t*>(A.iq);
+    // The bound of block k: the sum of the cb block sums from k on, which covers every window that starts in the
+    // block.  pre_c wraps, so the difference of two of its words is that sum only while the sum is under 2^32.  A sample
+    // gives at most 2 max(off2, 510 - off2)^2 (130 050 at offset 127.5, 520 200 at offsets 0 and 255), so the sum is
+    // under 2^32 for every offset up to a window of 7681 (cb <= 16) and for offsets 7 .. 248 at every window (at 127.5:
+    // 17 x 512 x 130 050 = 1.13e9).  Outside that (workgroup-uniform, `wide`) the block sums are added in 64 bits and the bound saturates at
+    // 2^32 - 1, which still is a bound: an exact window sum is 8192 x 520 200 = 4 261 478 400 at most.
+    const unsigned far = (unsigned)(A.up.off2 > 510 - A.up.off2 ? A.up.off2 : 510 - A.up.off2);
+    const bool wide = (unsigned long long)cb * 512ull * 2ull * far * far > 0xffffffffull;
+    const auto bound = [&](int k) -> unsigned {
+        if (!wide) return pre_c[onset_pad(k + cb)] - pre_c[onset_pad(k)];
+        unsigned long long u = 0;
+        for (int b = 0; b < cb; ++b) {
+            const size_t j = j0 + (size_t)k + (size_t)b;
+            u += j < nblk_total ? A.cblk[j] : 0u;
+        }
+        return u > 0xffffffffull ? 0xffffffffu : (unsigned)u;
+    };
     int kstart = 0;
     while (kstart < nloc) {                              // workgroup-uniform
         // the first block from kstart on that fails the proof
         unsigned long long mine = ~0ull;
         for (int k = kstart + tid; k < nloc; k += kScanThreads) {
-            const unsigned U = pre_c[onset_pad(k + cb)] - pre_c[onset_pad(k)];
+            const unsigned U = bound(k);
             if ((double)U * scale > thr_lo) { mine = (unsigned long long)k; break; }
         }
         const unsigned long long k1u = block_min_u64(mine, sh, 0);
@@ -958,7 +1007,7 @@ __device__ void tail_onset_range(const TailArgs& A, unsigned w, unsigned* pre_c,
         // the blocks in front of it are quiet: they enter the margin with their bound
         unsigned quiet = 0;
         for (int k = kstart + tid; k < k1; k += kScanThreads) {
-            const unsigned U = pre_c[onset_pad(k + cb)] - pre_c[onset_pad(k)];
+            const unsigned U = bound(k);
             quiet = U > quiet ? U : quiet;
         }
         quiet = block_max_u32(quiet, sh);

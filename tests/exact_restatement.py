@@ -10,14 +10,16 @@ import numpy as np
 GUARD = 1e-6      # kOnsetGuard (include/gpsjam.h, gj_onset.guard_index)
 
 
-def msq(raw: np.ndarray) -> np.ndarray:
-    """4 |z|^2 = (2I-255)^2 + (2Q-255)^2 per I/Q pair, int64; a trailing odd byte is not used."""
+def msq(raw: np.ndarray, o2: int = 255) -> np.ndarray:
+    """4 |z|^2 = (2I-o2)^2 + (2Q-o2)^2 per I/Q pair, int64; a trailing odd byte is not used.  o2 = 2 * offset of the
+    unpack convention (gj_set_unpack): an integer in [0, 510], 255 for the default."""
+    assert o2 == int(o2) and 0 <= o2 <= 510
     n = raw.size // 2
-    v = 2 * raw[:2 * n].astype(np.int64) - 255
+    v = 2 * raw[:2 * n].astype(np.int64) - int(o2)
     return v[0::2] ** 2 + v[1::2] ** 2
 
 
-def chunk_power(raw: np.ndarray, chunk_bytes: int, eps=1e-10, odd_chunk_zero=False) -> np.ndarray:
+def chunk_power(raw: np.ndarray, chunk_bytes: int, eps=1e-10, odd_chunk_zero=False, o2: int = 255) -> np.ndarray:
     """K1: float32(sum / (4 n)) + float32(eps) per chunk; NaN for a chunk without a pair (numpy's mean of an empty
     slice, worker.py:228-235); with odd_chunk_zero an odd-length chunk is 0 (checkIfJamming.py:52-55)."""
     out = []
@@ -29,14 +31,14 @@ def chunk_power(raw: np.ndarray, chunk_bytes: int, eps=1e-10, odd_chunk_zero=Fal
         elif n == 0:
             out.append(np.float32(np.nan))
         else:
-            out.append(np.float32(np.float32(int(msq(piece).sum()) / (4.0 * n)) + np.float32(eps)))
+            out.append(np.float32(np.float32(int(msq(piece, o2).sum()) / (4.0 * n)) + np.float32(eps)))
     return np.array(out, np.float32)
 
 
-def onset(raw: np.ndarray, noise_samples=200000, window=1000, factor=50.0) -> dict:
+def onset(raw: np.ndarray, noise_samples=200000, window=1000, factor=50.0, o2: int = 255) -> dict:
     """K4 (gj_onset): exact integer window sums against float32(noise) * float32(factor).
     Returns start / guard (+ window // 2, -1 = none), noise, thr (float32) and margin_hit (float32)."""
-    m = msq(raw)
+    m = msq(raw, o2)
     n = m.size
     none = dict(start=-1, guard=-1, noise=np.float32(0), thr=np.float32(0), hit=np.float32(0))
     if n < noise_samples + window:
@@ -61,11 +63,11 @@ def onset(raw: np.ndarray, noise_samples=200000, window=1000, factor=50.0) -> di
     return out
 
 
-def amp_stats(raw: np.ndarray, threshold: float) -> dict:
+def amp_stats(raw: np.ndarray, threshold: float, o2: int = 255) -> dict:
     """K3 (gj_amp_stats): amplitude = float32(sqrt(float32(m))) * float32(1/255); first index with amplitude >
     threshold (float32 compare), count from there on, and the sum from there on in float64 (the kernels add float32
-    partial sums of eight samples: compare at 2e-7)."""
-    m = msq(raw)
+    partial sums of eight samples: compare at 2e-7).  The scale is the default 1/127.5 whatever o2."""
+    m = msq(raw, o2)
     hs = np.float32((1.0 / 127.5) * 0.5)
     r = np.sqrt(m.astype(np.float32))
     hit = np.flatnonzero((r * hs) > np.float32(threshold))

@@ -106,3 +106,37 @@ def test_xcorr_f64_is_a_direct_correlation(n1, n0):
         rest = np.delete(c, k)
         np.testing.assert_allclose(run, rest.max() if rest.size else 0.0, rtol=1e-9, atol=1e-9 * c[k])
         assert lag == orc.xcorr_lag(a.astype(np.complex64), b.astype(np.complex64))[0]
+
+
+@pytest.mark.parametrize("o2", [0, 1, 509, 510])
+def test_o2_is_held_to_a_per_sample_loop(o2):
+    """The o2 argument of msq / chunk_power / onset / amp_stats (2 * offset of gj_set_unpack, its ends and their
+    neighbours) against plain Python integers, sample by sample."""
+    import math
+    rng = np.random.RandomState(40 + o2)
+    raw = rng.randint(0, 256, 2 * 3001 + 1).astype(np.uint8)                 # a trailing odd byte
+    raw[:8] = (0, 0, 255, 255, 0, 255, 255, 0)
+    raw[2 * 2000:2 * 2600] = 255 if o2 < 255 else 0                          # loud from 2000 on
+    e = [(2 * int(raw[2 * k]) - o2) ** 2 + (2 * int(raw[2 * k + 1]) - o2) ** 2 for k in range(raw.size // 2)]
+    assert ex.msq(raw, o2).tolist() == e and max(e) == 2 * max(o2, 510 - o2) ** 2 and ex.msq(raw).tolist() == ex.msq(raw, 255).tolist()
+    # K1
+    got = ex.chunk_power(raw, 1000, eps=0.0, o2=o2)
+    for c in range(got.size):
+        part = e[500 * c:500 * (c + 1)]
+        assert got[c] == np.float32(sum(part) / (4.0 * len(part)))
+    # K4
+    noise_samples, window, factor = 1500, 64, 1.5
+    on = ex.onset(raw, noise_samples, window, factor, o2)
+    noise = np.float32(sum(e[:noise_samples]) / (4.0 * noise_samples))
+    thr = np.float32(noise * np.float32(factor))
+    first = next((k for k in range(len(e) - window + 1) if sum(e[k:k + window]) * (0.25 / window) > float(thr)), None)
+    assert first is not None and 1900 < first < 2000
+    assert on["noise"] == noise and on["thr"] == thr and on["start"] == first + window // 2
+    # K3
+    for threshold in (0.0, 1.5):
+        st = ex.amp_stats(raw, threshold, o2)
+        amp = [math.sqrt(v) / 255.0 for v in e]
+        k = next((k for k, a in enumerate(amp) if a > threshold), None)
+        assert st["first"] == (k if k is not None else -1) and st["count"] == (len(e) - k if k is not None else 0)
+        if k is not None:
+            np.testing.assert_allclose(st["mean"], sum(amp[k:]) / (len(e) - k), rtol=1e-6)

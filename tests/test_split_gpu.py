@@ -415,3 +415,68 @@ def test_emulated_world_random_ragged_captures(dev, seed, world):
     finally:
         torch.cuda.set_stream(torch.cuda.default_stream())
         dev.set_stream(None, external=False)
+
+
+# ---------------------------------------------------------------------------------------
+# The noise span a part brings along (gj_part_view.d_noise): summed by one extra workgroup of the part's scan launch,
+# over ANY span a caller can pass.  A part that starts 32 MiB into its capture, built by hand so that only the span and
+# the small part buffer exist; the capture's declared length covers both.
+# ---------------------------------------------------------------------------------------
+PART_FIRST_BYTE = 32 << 20
+PART_TOTAL_BYTES = 1 << 28
+NOISE_SPANS = {
+    # name -> (I byte, Q byte, noise_samples)
+    "rail 18 MB": (255, 255, 9_000_000),            # a thread's sum of u^2 passes 2^32 from ~16.9 MB of 255s on
+    "mid-level 80 MB": (128, 127, 40_000_000),      # ... and from ~67 MB on whatever the bytes are
+    "default 200000": (128, 127, 200_000),          # the control
+}
+
+
+def _onset_record(t):
+    import gpsjam._ffi as _ffi
+    return _ffi.Onset.from_buffer_copy(t.cpu().numpy().tobytes())
+
+
+@pytest.mark.parametrize("name", list(NOISE_SPANS))
+def test_part_noise_span_of_any_length_is_summed_exactly(dev, name):
+    """noise_power = float32(S / 4n) with S the exact integer sum over the span (tests/exact_restatement.py), threshold
+    = float32(noise_power * factor), and both the same bits as the unsplit gj_onset_dev over a buffer that begins with
+    the span."""
+    import torch
+    import exact_restatement as er
+    from gpsjam import _ffi
+    ui, uq, noise_samples = NOISE_SPANS[name]
+    window, factor, chunk, tile = 1000, 50.0, 65536, 65536
+    halo, own = tile, 4 * tile
+    assert PART_TOTAL_BYTES >= 2 * (noise_samples + window) and PART_TOTAL_BYTES >= PART_FIRST_BYTE + own
+    pair = (ui | (uq << 8)) - (1 << 16 if uq >= 128 else 0)                 # little-endian int16 holding (I, Q)
+    span = torch.full((noise_samples,), pair, dtype=torch.int16, device="cuda").view(torch.uint8)
+    rng = np.random.RandomState(5)
+    quiet = (np.clip(np.rint(rng.normal(0, 2.0, halo + own)), -128, 127) + 128).astype(np.uint8)
+    buf = torch.from_numpy(quiet).cuda()
+    assert span.numel() == 2 * noise_samples and span.data_ptr() % 16 == 0 and buf.data_ptr() % 16 == 0
+    S = noise_samples * int(er.msq(np.array([ui, uq], np.uint8))[0])        # exact: Python integers
+    want_noise = np.float32(S / (4.0 * noise_samples))
+    want_thr = np.float32(want_noise * np.float32(factor))
+
+    view = _ffi.PartView(buf.data_ptr(), buf.numel(), PART_FIRST_BYTE - halo, PART_FIRST_BYTE, own, PART_TOTAL_BYTES,
+                         span.data_ptr())
+    power = torch.zeros(own // chunk, dtype=torch.float32, device="cuda")
+    tiles = torch.zeros(2 * dev.amp_tile_count(own), dtype=torch.float64, device="cuda")
+    amp = torch.zeros(4, dtype=torch.int64, device="cuda")
+    d_part = torch.zeros(4, dtype=torch.int64, device="cuda")
+    d_whole = torch.zeros(4, dtype=torch.int64, device="cuda")
+    whole = torch.cat([span, buf[:2 * tile]])                                # begins with the same span
+    torch.cuda.synchronize()
+    dev.part_scan_dev(view, chunk, power, 0.0, tiles, amp, noise_samples, window, factor, d_part)
+    dev.onset_dev(whole, whole.numel(), noise_samples, window, factor, d_whole)
+    dev.synchronize()
+    part, unsplit = _onset_record(d_part), _onset_record(d_whole)
+    print(f"{name}: part noise {part.noise_power!r} thr {part.threshold!r}; unsplit noise {unsplit.noise_power!r} "
+          f"thr {unsplit.threshold!r}; exact {float(want_noise)!r} / {float(want_thr)!r}")
+    assert np.float32(unsplit.noise_power) == want_noise and np.float32(unsplit.threshold) == want_thr
+    assert np.float32(part.noise_power) == want_noise, (name, part.noise_power, float(want_noise))
+    assert np.float32(part.threshold) == want_thr, (name, part.threshold, float(want_thr))
+    assert (part.noise_power, part.threshold) == (unsplit.noise_power, unsplit.threshold)
+    # the part's power map is the quiet buffer's, whatever the span was
+    np.testing.assert_array_equal(power.cpu().numpy(), er.chunk_power(quiet[halo:], chunk))
