@@ -1,0 +1,65 @@
+// What the two excisors, k_excise.hip and k_excise_chirp.hip, share besides the transform front end (stft_group.h; those
+// two include this, nothing else does): the geometry their kernels take, the run arithmetic of their launches and the
+// copy of the edges no frame pair covers.  The transform kernels themselves stay apart, each in its own file.
+#pragma once
+#include "stft_group.h"
+
+namespace gj {
+
+struct ExciseGeom {
+    unsigned long long first_sample, n_frames, per_run;
+    float offset;    // offset of the unpack convention
+    float scale2;    // scale^2: the transform runs on u8 - offset, the powers are scaled to the units of gj_ridge_dev
+};
+
+// the geometry of a call that has passed its checks; per_run is the launch's to fill in (excise_runs)
+inline ExciseGeom excise_geom(const gj_ctx* ctx, size_t first_sample, size_t n_samples, int nfft) {
+    ExciseGeom g;
+    g.first_sample = first_sample;
+    g.n_frames = gj_excise_frames(n_samples, nfft);
+    g.per_run = 0;
+    g.offset = 0.5f * (float)ctx->off2;
+    g.scale2 = (float)(ctx->scale * ctx->scale);
+    return g;
+}
+
+// One round of transform groups, B to a workgroup: runs of equal length, the length from the frame count alone -- at least
+// min_run frames (but for short calls), which bounds the priming overhead.
+struct ExciseRuns {
+    unsigned long long per_run;
+    unsigned grid;
+};
+inline ExciseRuns excise_runs(unsigned long long n_frames, unsigned long long B, int min_waves, int min_run, int num_cus) {
+    const unsigned long long slots = (unsigned long long)num_cus * min_waves * B;
+    unsigned long long per = (n_frames + slots - 1) / slots;
+    if (per < (unsigned long long)min_run) per = min_run;
+    if (per > n_frames) per = n_frames;
+    const unsigned long long runs = (n_frames + per - 1) / per;
+    return ExciseRuns{per, (unsigned)((runs + B - 1) / B)};
+}
+
+// the first half frame [0, n_head) and the tail [tail_first, n_bytes) come back as they went in.  Internal linkage: the
+// library is built without relocatable device code, so each of the two translation units launches a copy of its own.
+static __global__ __launch_bounds__(256) void excise_edges_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
+                                                                  unsigned long long n_head, unsigned long long tail_first,
+                                                                  unsigned long long n_bytes) {
+    const unsigned long long n_tail = n_bytes - tail_first;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_head + n_tail;
+         i += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long at = i < n_head ? i : tail_first + (i - n_head);
+        out[at] = src[at];
+    }
+}
+
+// the second, small launch of both excisors, behind the transform kernel on the context's stream
+static int excise_copy_edges(gj_ctx* ctx, const uint8_t* d_iq, const ExciseGeom& g, size_t n_samples, int nfft, uint8_t* d_out) {
+    const unsigned long long h2 = (unsigned long long)nfft;   // bytes of half a frame
+    const unsigned long long tail_first = g.n_frames * h2, n_bytes = 2ull * n_samples;
+    const unsigned long long edge = h2 + (n_bytes - tail_first);   // < 3 nfft bytes
+    hipLaunchKernelGGL(excise_edges_kernel, dim3((unsigned)((edge + 255) / 256)), dim3(256), 0, ctx->stream,
+                       d_iq + 2 * g.first_sample, d_out, h2, tail_first, n_bytes);
+    GJ_LAUNCH_CHECK(ctx);
+    return GJ_OK;
+}
+
+}   // namespace gj

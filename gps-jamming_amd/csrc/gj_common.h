@@ -188,6 +188,20 @@ void reap_retired(gj_ctx* ctx);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// What the cleaners (gj_excise_dev, gj_excise_chirp_dev, gj_blank_dev) ask of the range they rewrite: samples
+// first_sample .. + n_samples lie inside the capture of nbytes, and the 2 n_samples bytes at d_out lie outside it --
+// frames and windows read their neighbours, so the output may not lie in the capture.
+inline int check_range_and_output(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples,
+                                  const uint8_t* d_out) {
+    const size_t total = nbytes / 2;
+    if (first_sample > total || n_samples > total - first_sample)
+        return fail(ctx, GJ_ERR_INVALID, "samples %zu .. +%zu run past the capture's %zu", first_sample, n_samples, total);
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_iq), a1 = a0 + nbytes;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + 2 * n_samples;
+    if (o0 < a1 && a0 < o1) return fail(ctx, GJ_ERR_INVALID, "d_out overlaps the capture");
+    return GJ_OK;
+}
+
 // ---- device helpers ---------------------------------------------------------------
 __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
 #pragma unroll

@@ -282,15 +282,8 @@ int gj_blank_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_s
     if (reinterpret_cast<uintptr_t>(d_iq) & 1) return fail(ctx, GJ_ERR_INVALID, "capture must be 2-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_blocks) & 7) return fail(ctx, GJ_ERR_INVALID, "records must be 8-byte aligned");
     if (!(threshold >= 0.f)) return fail(ctx, GJ_ERR_INVALID, "threshold must be a number >= 0");
-    const size_t total = nbytes / 2;
     if (n_samples == 0) return fail(ctx, GJ_ERR_INVALID, "n_samples is 0");
-    if (first_sample > total || n_samples > total - first_sample)
-        return fail(ctx, GJ_ERR_INVALID, "samples %zu .. +%zu run past the capture's %zu", first_sample, n_samples, total);
-    {   // windows read their neighbours: the output may not lie in the capture
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_iq), a1 = a0 + nbytes;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + 2 * n_samples;
-        if (o0 < a1 && a0 < o1) return fail(ctx, GJ_ERR_INVALID, "d_out overlaps the capture");
-    }
+    if (int rc = check_range_and_output(ctx, d_iq, nbytes, first_sample, n_samples, d_out)) return rc;
     BlankGeom g;
     g.first_sample = first_sample;
     g.n_samples = n_samples;

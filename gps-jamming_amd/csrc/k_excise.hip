@@ -24,9 +24,10 @@
 // reproduces the interior bytes and the shared records bit for bit.
 //
 // The first half frame and the tail behind the last whole hop are copied from the input by a second small launch.
+// That copy, the geometry struct and the run arithmetic are excise_host.h, shared with k_excise_chirp.hip.
 //
 // This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it.
-#include "stft_group.h"
+#include "excise_host.h"
 
 namespace gj {
 
@@ -37,12 +38,6 @@ struct ExciseCfg {
     // twiddle set but keep the same bound (profiles/NOTES_excise.md has the compiler's figures)
     static constexpr int min_waves = 2;
     static constexpr int min_run = 4;   // frames per run at least (but for short calls): bounds the priming overhead at 25 %
-};
-
-struct ExciseGeom {
-    unsigned long long first_sample, n_frames, per_run;
-    float offset;    // offset of the unpack convention
-    float scale2;    // scale^2: the transform runs on u8 - offset, the powers are scaled to the units of gj_ridge_dev
 };
 
 template <int N>
@@ -156,31 +151,12 @@ __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise
     }
 }
 
-// the first half frame [0, n_head) and the tail [tail_first, n_bytes) come back as they went in
-__global__ __launch_bounds__(256) void excise_edges_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
-                                                           unsigned long long n_head, unsigned long long tail_first,
-                                                           unsigned long long n_bytes) {
-    const unsigned long long n_tail = n_bytes - tail_first;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_head + n_tail;
-         i += (unsigned long long)gridDim.x * blockDim.x) {
-        const unsigned long long at = i < n_head ? i : tail_first + (i - n_head);
-        out[at] = src[at];
-    }
-}
-
 template <int N>
 static void excise_launch(gj_ctx* ctx, const uint8_t* d_iq, ExciseGeom g, const float* d_thr, uint8_t* d_out, gj_excise_frame* d_frames) {
-    constexpr unsigned long long B = kBlockPoints / N;
-    // one round of transform groups; runs of equal length, the length from the frame count alone
-    const unsigned long long slots = (unsigned long long)ctx->num_cus * ExciseCfg<N>::min_waves * B;
-    unsigned long long per = (g.n_frames + slots - 1) / slots;
-    if (per < (unsigned long long)ExciseCfg<N>::min_run) per = ExciseCfg<N>::min_run;
-    if (per > g.n_frames) per = g.n_frames;
-    g.per_run = per;
-    const unsigned long long runs = (g.n_frames + per - 1) / per;
-    const unsigned grid = (unsigned)((runs + B - 1) / B);
-    hipLaunchKernelGGL(excise_kernel<N>, dim3(grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle, window_table(ctx, N),
-                       d_thr, d_out, d_frames);
+    const ExciseRuns runs = excise_runs(g.n_frames, kBlockPoints / N, ExciseCfg<N>::min_waves, ExciseCfg<N>::min_run, ctx->num_cus);
+    g.per_run = runs.per_run;
+    hipLaunchKernelGGL(excise_kernel<N>, dim3(runs.grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle,
+                       window_table(ctx, N), d_thr, d_out, d_frames);
 }
 
 }   // namespace gj
@@ -203,30 +179,12 @@ int gj_excise_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_
     if (int rc = stft_check_capture(ctx, d_iq)) return rc;
     if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
-    const size_t total = nbytes / 2;
     if (n_samples < (size_t)nfft) return fail(ctx, GJ_ERR_INVALID, "n_samples %zu is less than one frame of %d points", n_samples, nfft);
-    if (first_sample > total || n_samples > total - first_sample)
-        return fail(ctx, GJ_ERR_INVALID, "samples %zu .. +%zu run past the capture's %zu", first_sample, n_samples, total);
-    {   // frames read their neighbours: the output may not lie in the capture
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_iq), a1 = a0 + nbytes;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + 2 * n_samples;
-        if (o0 < a1 && a0 < o1) return fail(ctx, GJ_ERR_INVALID, "d_out overlaps the capture");
-    }
-    ExciseGeom g;
-    g.first_sample = first_sample;
-    g.n_frames = gj_excise_frames(n_samples, nfft);
-    g.per_run = 0;
-    g.offset = 0.5f * (float)ctx->off2;
-    g.scale2 = (float)(ctx->scale * ctx->scale);
+    if (int rc = check_range_and_output(ctx, d_iq, nbytes, first_sample, n_samples, d_out)) return rc;
+    const ExciseGeom g = excise_geom(ctx, first_sample, n_samples, nfft);
     stft_dispatch(nfft, [&](auto n) { excise_launch<decltype(n)::value>(ctx, d_iq, g, d_threshold, d_out, d_frames); });
     GJ_LAUNCH_CHECK(ctx);
-    const unsigned long long h2 = (unsigned long long)nfft;   // bytes of half a frame
-    const unsigned long long tail_first = g.n_frames * h2, n_bytes = 2ull * n_samples;
-    const unsigned long long edge = h2 + (n_bytes - tail_first);   // < 3 nfft bytes
-    hipLaunchKernelGGL(excise_edges_kernel, dim3((unsigned)((edge + 255) / 256)), dim3(256), 0, ctx->stream, d_iq + 2 * first_sample,
-                       d_out, h2, tail_first, n_bytes);
-    GJ_LAUNCH_CHECK(ctx);
-    return GJ_OK;
+    return excise_copy_edges(ctx, d_iq, g, n_samples, nfft, d_out);
 }
 
 }   // extern "C"

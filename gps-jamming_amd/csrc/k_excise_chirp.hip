@@ -25,10 +25,11 @@
 // Determinism: as excise_kernel, with "its own bytes" read as "its own bytes and its own q".
 //
 // A translation unit of its own with its own extern "C" entry points; the frame count is gj_excise_frames (k_excise.hip, by
-// its declaration in include/gpsjam.h), the edges copy is restated here: a kernel of another translation unit cannot be
+// its declaration in include/gpsjam.h); the geometry struct, the run arithmetic and the edges copy are excise_host.h, which
+// gives this translation unit a copy of the edges kernel of its own: a kernel of another translation unit cannot be
 // launched from this one without relocatable device code.
 #include "chirp_phase.h"
-#include "stft_group.h"
+#include "excise_host.h"
 
 namespace gj {
 
@@ -39,15 +40,9 @@ struct ExciseChirpCfg {
     static constexpr int min_run = 4;   // as ExciseCfg: bounds the priming overhead at 25 %
 };
 
-struct ExciseChirpGeom {
-    unsigned long long first_sample, n_frames, per_run;
-    float offset;    // offset of the unpack convention
-    float scale2;    // scale^2
-};
-
 template <int N>
 __global__ __launch_bounds__(kBlockThreads, ExciseChirpCfg<N>::min_waves) void excise_chirp_kernel(
-    const uint8_t* __restrict__ iq, ExciseChirpGeom g, const cf* __restrict__ twtab, const float* __restrict__ wintab,
+    const uint8_t* __restrict__ iq, ExciseGeom g, const cf* __restrict__ twtab, const float* __restrict__ wintab,
     const int32_t* __restrict__ rate, const float* __restrict__ thr_tab, uint8_t* __restrict__ out,
     gj_excise_frame* __restrict__ frames) {
     using S = StftShape<N>;
@@ -156,18 +151,6 @@ __global__ __launch_bounds__(kBlockThreads, ExciseChirpCfg<N>::min_waves) void e
     }
 }
 
-// the first half frame [0, n_head) and the tail [tail_first, n_bytes) come back as they went in
-__global__ __launch_bounds__(256) void excise_chirp_edges_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
-                                                                 unsigned long long n_head, unsigned long long tail_first,
-                                                                 unsigned long long n_bytes) {
-    const unsigned long long n_tail = n_bytes - tail_first;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_head + n_tail;
-         i += (unsigned long long)gridDim.x * blockDim.x) {
-        const unsigned long long at = i < n_head ? i : tail_first + (i - n_head);
-        out[at] = src[at];
-    }
-}
-
 // d_rate[f] = rate_first + rate_index_f * rate_step where the search concentrated the frame, 0 elsewhere
 __global__ __launch_bounds__(256) void chirp_rates_kernel(const gj_chirp_frame* __restrict__ scan, unsigned long long n_frames,
                                                           int rate_first, int rate_step, float min_concentration,
@@ -187,18 +170,12 @@ __global__ __launch_bounds__(256) void chirp_rates_kernel(const gj_chirp_frame* 
 }
 
 template <int N>
-static void excise_chirp_launch(gj_ctx* ctx, const uint8_t* d_iq, ExciseChirpGeom g, const int32_t* d_rate, const float* d_thr,
+static void excise_chirp_launch(gj_ctx* ctx, const uint8_t* d_iq, ExciseGeom g, const int32_t* d_rate, const float* d_thr,
                                 uint8_t* d_out, gj_excise_frame* d_frames) {
-    constexpr unsigned long long B = kBlockPoints / N;
-    // one round of transform groups; runs of equal length, the length from the frame count alone (as excise_launch)
-    const unsigned long long slots = (unsigned long long)ctx->num_cus * ExciseChirpCfg<N>::min_waves * B;
-    unsigned long long per = (g.n_frames + slots - 1) / slots;
-    if (per < (unsigned long long)ExciseChirpCfg<N>::min_run) per = ExciseChirpCfg<N>::min_run;
-    if (per > g.n_frames) per = g.n_frames;
-    g.per_run = per;
-    const unsigned long long runs = (g.n_frames + per - 1) / per;
-    const unsigned grid = (unsigned)((runs + B - 1) / B);
-    hipLaunchKernelGGL(excise_chirp_kernel<N>, dim3(grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle,
+    const ExciseRuns runs = excise_runs(g.n_frames, kBlockPoints / N, ExciseChirpCfg<N>::min_waves, ExciseChirpCfg<N>::min_run,
+                                        ctx->num_cus);
+    g.per_run = runs.per_run;
+    hipLaunchKernelGGL(excise_chirp_kernel<N>, dim3(runs.grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle,
                        window_table(ctx, N), d_rate, d_thr, d_out, d_frames);
 }
 
@@ -218,30 +195,12 @@ int gj_excise_chirp_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t 
     if (reinterpret_cast<uintptr_t>(d_rate) & 3) return fail(ctx, GJ_ERR_INVALID, "rates must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
-    const size_t total = nbytes / 2;
     if (n_samples < (size_t)nfft) return fail(ctx, GJ_ERR_INVALID, "n_samples %zu is less than one frame of %d points", n_samples, nfft);
-    if (first_sample > total || n_samples > total - first_sample)
-        return fail(ctx, GJ_ERR_INVALID, "samples %zu .. +%zu run past the capture's %zu", first_sample, n_samples, total);
-    {   // frames read their neighbours: the output may not lie in the capture
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(d_iq), a1 = a0 + nbytes;
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + 2 * n_samples;
-        if (o0 < a1 && a0 < o1) return fail(ctx, GJ_ERR_INVALID, "d_out overlaps the capture");
-    }
-    ExciseChirpGeom g;
-    g.first_sample = first_sample;
-    g.n_frames = gj_excise_frames(n_samples, nfft);
-    g.per_run = 0;
-    g.offset = 0.5f * (float)ctx->off2;
-    g.scale2 = (float)(ctx->scale * ctx->scale);
+    if (int rc = check_range_and_output(ctx, d_iq, nbytes, first_sample, n_samples, d_out)) return rc;
+    const ExciseGeom g = excise_geom(ctx, first_sample, n_samples, nfft);
     stft_dispatch(nfft, [&](auto n) { excise_chirp_launch<decltype(n)::value>(ctx, d_iq, g, d_rate, d_threshold, d_out, d_frames); });
     GJ_LAUNCH_CHECK(ctx);
-    const unsigned long long h2 = (unsigned long long)nfft;   // bytes of half a frame
-    const unsigned long long tail_first = g.n_frames * h2, n_bytes = 2ull * n_samples;
-    const unsigned long long edge = h2 + (n_bytes - tail_first);   // < 3 nfft bytes
-    hipLaunchKernelGGL(excise_chirp_edges_kernel, dim3((unsigned)((edge + 255) / 256)), dim3(256), 0, ctx->stream,
-                       d_iq + 2 * first_sample, d_out, h2, tail_first, n_bytes);
-    GJ_LAUNCH_CHECK(ctx);
-    return GJ_OK;
+    return excise_copy_edges(ctx, d_iq, g, n_samples, nfft, d_out);
 }
 
 int gj_chirp_rates_dev(gj_ctx* ctx, const gj_chirp_frame* d_scan, size_t n_frames, int rate_first, int rate_step,

@@ -15,6 +15,7 @@ raises ``GpsJamLibraryError``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import NamedTuple, Optional, Sequence
 
@@ -387,6 +388,12 @@ class DevBuf:
             self.dev._lib.gj_free(self.dev._ctx, self.ptr)
             self.ptr = 0
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
     def __del__(self):
         try:
             self.free()
@@ -643,6 +650,39 @@ class Device:
         arr = as_u8(raw)
         return (arr.ctypes.data if arr.size else None), int(arr.size), arr
 
+    @contextlib.contextmanager
+    def _resident(self, raw):
+        """A live ``Capture`` for the length of a ``with``: ``raw`` itself when it is one (it is left alone on the way out),
+        else host bytes, uploaded once and freed on the way out."""
+        if isinstance(raw, Capture):
+            if not raw.ptr and raw.nbytes:
+                raise ValueError("the capture has been freed")
+            yield raw
+        else:
+            with Capture(self, raw) as cap:
+                yield cap
+
+    def _on_device(self, temps, values, dtype, count: int, name: str, expected: str):
+        """``values`` on the device: a device buffer (DevBuf, address, torch tensor) as it is, whatever it holds, or a host
+        array of exactly ``count`` values, uploaded as ``dtype`` into a buffer that the ExitStack ``temps`` frees."""
+        if isinstance(values, (DevBuf, int)) or hasattr(values, "data_ptr"):
+            return values
+        host, dtype = np.asarray(values).reshape(-1), np.dtype(dtype)
+        if host.size != count:
+            raise ValueError(f"{name} holds {host.size} values, {expected}")
+        if host.size and dtype.kind == "i" and not np.issubdtype(host.dtype, np.integer):
+            raise TypeError(f"{name} must be integers")
+        return temps.enter_context(DevBuf(self, max(count, 1) * dtype.itemsize)).upload(host.astype(dtype))
+
+    def _cleaned(self, n_samples: int, n_records: int, dtype, launch):
+        """The tail the cleaners share: 2 * n_samples output bytes and n_records records of ``dtype`` (neither buffer is
+        ever empty), ``launch(d_out, d_rec)``, the records brought back and the output handed over to a ``Capture`` of
+        its own, which empties ``d_out``: ``(cleaned, records)``.  Whatever fails, both buffers are freed."""
+        with DevBuf(self, max(2 * n_samples, 1)) as d_out, DevBuf(self, max(n_records, 1) * dtype.itemsize) as d_rec:
+            launch(d_out, d_rec)
+            rec = d_rec.download(dtype, n_records)
+            return Capture.from_device(self, d_out, 2 * n_samples), rec
+
     def probe_busy_dev(self, milliseconds: float):
         """Keep this context's stream (and its hardware queue) busy for a while with one spinning wave (gj_probe_busy_dev):
         the stream-overlap probe of gpsjam/streams.py."""
@@ -819,12 +859,9 @@ class Device:
                        stride: int = 100) -> np.ndarray:
         """256-bin histogram of raw_chunk[::stride] over the chunks the waterfall keeps
         (widmo_plot.py:35,85)."""
-        d = DevBuf(self, 8 * 256)          # a buffer of this call's own: several threads may histogram at once
-        try:
+        with DevBuf(self, 8 * 256) as d:   # a buffer of this call's own: several threads may histogram at once
             self.byte_histogram_dev(cap, cap.nbytes, chunk_samples, nperseg, stride, d)
             return d.download(np.uint64, 256)
-        finally:
-            d.free()
 
     def xcorr_lags(self, slices: Sequence, pairs: Sequence[Sequence[int]], want_margins: bool = False):
         """lags[p], peaks[p] (, margins[p]) for pairs (i, j): lag of slice j relative to slice i
@@ -895,25 +932,15 @@ class Device:
         where the spectral peak is and how much of the frame's power it holds; n_frames defaults to all that fit.
         ``raw``: host bytes (uploaded once, like a ``Capture``) or a resident ``Capture``.  16 bytes per frame come back."""
         hop = int(nfft) // 2 if hop is None else int(hop)
-        own = None if isinstance(raw, Capture) else Capture(self, raw)
-        cap = raw if own is None else own
-        try:
-            if not cap.ptr and cap.nbytes:
-                raise ValueError("the capture has been freed")
+        with self._resident(raw) as cap:
             if n_frames is None:
                 n_frames = ridge_frames(cap.nbytes, first_sample, nfft, hop)
                 if n_frames == 0 and 16 <= int(nfft) <= 4096 and hop >= 1:
                     return Ridge(np.empty(0, RIDGE_DTYPE), nfft, hop, first_sample, guard)
             self._count("ridge")
-            out = DevBuf(self, max(int(n_frames), 1) * RIDGE_DTYPE.itemsize)
-            try:
+            with DevBuf(self, max(int(n_frames), 1) * RIDGE_DTYPE.itemsize) as out:
                 self.ridge_dev(cap, cap.nbytes, first_sample, nfft, hop, n_frames, guard, out)
                 rec = out.download(RIDGE_DTYPE, int(n_frames))
-            finally:
-                out.free()
-        finally:
-            if own is not None:
-                own.free()
         return Ridge(rec, nfft, hop, first_sample, guard)
 
     def chirp(self, raw, nfft: int = 256, hop: Optional[int] = None, rates=(0, 1, 1), first_sample: int = 0,
@@ -925,12 +952,7 @@ class Device:
         nfft, first_sample, guard = int(nfft), int(first_sample), int(guard)
         hop = nfft // 2 if hop is None else int(hop)
         first, step, n = (int(v) for v in rates)
-        own = None if isinstance(raw, Capture) else Capture(self, raw)
-        cap = raw if own is None else own
-        out = pk = None
-        try:
-            if not cap.ptr and cap.nbytes:
-                raise ValueError("the capture has been freed")
+        with self._resident(raw) as cap:
             if n_frames is None:
                 n_frames = ridge_frames(cap.nbytes, first_sample, nfft, hop)
                 if n_frames == 0 and 16 <= nfft <= 4096 and hop >= 1 and 1 <= n <= _ffi.GJ_CHIRP_MAX_RATES:
@@ -938,16 +960,11 @@ class Device:
                                      np.empty((0, n), np.float32) if want_peaks else None)
             n_frames = int(n_frames)
             self._count("chirp")
-            out = DevBuf(self, max(n_frames, 1) * CHIRP_DTYPE.itemsize)
-            if want_peaks:
-                pk = DevBuf(self, max(n_frames, 1) * max(n, 1) * 4)
-            self.chirp_dev(cap, cap.nbytes, first_sample, nfft, hop, n_frames, guard, first, step, n, out, pk)
-            rec = out.download(CHIRP_DTYPE, n_frames)
-            peaks = pk.download(np.float32, n_frames * n).reshape(n_frames, n) if want_peaks else None
-        finally:
-            for buf in (out, pk, own):
-                if buf is not None:
-                    buf.free()
+            with DevBuf(self, max(n_frames, 1) * CHIRP_DTYPE.itemsize) as out, \
+                    (DevBuf(self, max(n_frames, 1) * max(n, 1) * 4) if want_peaks else contextlib.nullcontext()) as pk:
+                self.chirp_dev(cap, cap.nbytes, first_sample, nfft, hop, n_frames, guard, first, step, n, out, pk)
+                rec = out.download(CHIRP_DTYPE, n_frames)
+                peaks = pk.download(np.float32, n_frames * n).reshape(n_frames, n) if want_peaks else None
         return ChirpScan(rec, nfft, hop, (first, step, n), first_sample, guard, peaks)
 
     def spectral_kurtosis(self, capture, nfft: int = 256, hop: Optional[int] = None, frames_per_row: int = 256,
@@ -957,12 +974,7 @@ class Device:
         ``capture``: host bytes (uploaded once, like a ``Capture``) or a resident ``Capture``."""
         nfft, frames_per_row, first_sample = int(nfft), int(frames_per_row), int(first_sample)
         hop = nfft if hop is None else int(hop)
-        own = None if isinstance(capture, Capture) else Capture(self, capture)
-        cap = capture if own is None else own
-        out = None
-        try:
-            if not cap.ptr and cap.nbytes:
-                raise ValueError("the capture has been freed")
+        with self._resident(capture) as cap:
             if n_rows is None:
                 n_rows = sk_rows(cap.nbytes, first_sample, nfft, hop, frames_per_row)
                 if n_rows == 0 and 16 <= nfft <= 4096 and hop >= 1 and 2 <= frames_per_row <= 65536:
@@ -971,15 +983,10 @@ class Device:
             n_rows = int(n_rows)
             self._count("spectral_kurtosis")
             cells = max(n_rows, 1) * max(nfft, 1)
-            out = DevBuf(self, 3 * 4 * cells)
-            self.spectral_kurtosis_dev(cap, cap.nbytes, first_sample, nfft, hop, frames_per_row, n_rows, out.ptr,
-                                       out.ptr + 4 * cells, out.ptr + 8 * cells)
-            got = out.download(np.float32, 3 * cells).reshape(3, cells)[:, :n_rows * nfft]
-        finally:
-            if out is not None:
-                out.free()
-            if own is not None:
-                own.free()
+            with DevBuf(self, 3 * 4 * cells) as out:
+                self.spectral_kurtosis_dev(cap, cap.nbytes, first_sample, nfft, hop, frames_per_row, n_rows, out.ptr,
+                                           out.ptr + 4 * cells, out.ptr + 8 * cells)
+                got = out.download(np.float32, 3 * cells).reshape(3, cells)[:, :n_rows * nfft]
         return SpectralKurtosis(got[0], got[1], got[2], nfft, hop, frames_per_row, first_sample)
 
     def excise(self, raw, threshold, nfft: int = 1024, first_sample: int = 0, n_samples: Optional[int] = None):
@@ -990,34 +997,14 @@ class Device:
         ``(cleaned, records)``: the cleaned range as a resident ``Capture`` of its own (the caller frees it) and one
         EXCISE_DTYPE record per frame."""
         nfft, first_sample = int(nfft), int(first_sample)
-        own = None if isinstance(raw, Capture) else Capture(self, raw)
-        cap = raw if own is None else own
-        d_thr = d_out = d_rec = None
-        try:
-            if not cap.ptr and cap.nbytes:
-                raise ValueError("the capture has been freed")
-            if n_samples is None:
-                n_samples = max(0, cap.nsamples - first_sample)
-            n_samples = int(n_samples)
+        with contextlib.ExitStack() as temps:
+            cap = temps.enter_context(self._resident(raw))
+            n_samples = max(0, cap.nsamples - first_sample) if n_samples is None else int(n_samples)
             frames = excise_frames(n_samples, nfft)
-            if isinstance(threshold, (DevBuf, int)) or hasattr(threshold, "data_ptr"):
-                thr = threshold
-            else:
-                host = np.ascontiguousarray(threshold, dtype=np.float32).reshape(-1)
-                if host.size != nfft:
-                    raise ValueError(f"threshold holds {host.size} values, nfft is {nfft}")
-                thr = d_thr = DevBuf(self, 4 * nfft).upload(host)
+            thr = self._on_device(temps, threshold, np.float32, nfft, "threshold", f"nfft is {nfft}")
             self._count("excise")
-            d_out = DevBuf(self, max(2 * n_samples, 1))
-            d_rec = DevBuf(self, max(frames, 1) * EXCISE_DTYPE.itemsize)
-            self.excise_dev(cap, cap.nbytes, first_sample, n_samples, nfft, thr, d_out, d_rec)
-            rec = d_rec.download(EXCISE_DTYPE, frames)
-            cleaned, d_out = Capture.from_device(self, d_out, 2 * n_samples), None
-        finally:
-            for b in (d_thr, d_rec, d_out, own):
-                if b is not None:
-                    b.free()
-        return cleaned, rec
+            return self._cleaned(n_samples, frames, EXCISE_DTYPE, lambda d_out, d_rec: self.excise_dev(
+                cap, cap.nbytes, first_sample, n_samples, nfft, thr, d_out, d_rec))
 
     def excise_chirp(self, raw, threshold, rates, nfft: int = 1024, first_sample: int = 0, n_samples: Optional[int] = None):
         """Chirp-domain excision (gj_excise_chirp_dev): ``excise`` with every frame de-chirped by its own rate in front
@@ -1027,43 +1014,15 @@ class Device:
         of int32.  ``raw``, ``threshold`` and the result ``(cleaned, records)`` as ``excise``; the records are taken
         behind the de-chirp."""
         nfft, first_sample = int(nfft), int(first_sample)
-        own = None if isinstance(raw, Capture) else Capture(self, raw)
-        cap = raw if own is None else own
-        d_thr = d_rate = d_out = d_rec = None
-        try:
-            if not cap.ptr and cap.nbytes:
-                raise ValueError("the capture has been freed")
-            if n_samples is None:
-                n_samples = max(0, cap.nsamples - first_sample)
-            n_samples = int(n_samples)
+        with contextlib.ExitStack() as temps:
+            cap = temps.enter_context(self._resident(raw))
+            n_samples = max(0, cap.nsamples - first_sample) if n_samples is None else int(n_samples)
             frames = excise_frames(n_samples, nfft)
-            if isinstance(threshold, (DevBuf, int)) or hasattr(threshold, "data_ptr"):
-                thr = threshold
-            else:
-                host = np.ascontiguousarray(threshold, dtype=np.float32).reshape(-1)
-                if host.size != nfft:
-                    raise ValueError(f"threshold holds {host.size} values, nfft is {nfft}")
-                thr = d_thr = DevBuf(self, 4 * nfft).upload(host)
-            if isinstance(rates, (DevBuf, int)) or hasattr(rates, "data_ptr"):
-                rate = rates
-            else:
-                host = np.asarray(rates).reshape(-1)
-                if host.size != frames:
-                    raise ValueError(f"rates holds {host.size} values, the range has {frames} frames of {nfft} points")
-                if host.size and not np.issubdtype(host.dtype, np.integer):
-                    raise TypeError("rates must be integers")
-                rate = d_rate = DevBuf(self, max(4 * frames, 4)).upload(host.astype(np.int32))
+            thr = self._on_device(temps, threshold, np.float32, nfft, "threshold", f"nfft is {nfft}")
+            rate = self._on_device(temps, rates, np.int32, frames, "rates", f"the range has {frames} frames of {nfft} points")
             self._count("excise_chirp")
-            d_out = DevBuf(self, max(2 * n_samples, 1))
-            d_rec = DevBuf(self, max(frames, 1) * EXCISE_DTYPE.itemsize)
-            self.excise_chirp_dev(cap, cap.nbytes, first_sample, n_samples, nfft, rate, thr, d_out, d_rec)
-            rec = d_rec.download(EXCISE_DTYPE, frames)
-            cleaned, d_out = Capture.from_device(self, d_out, 2 * n_samples), None
-        finally:
-            for b in (d_thr, d_rate, d_rec, d_out, own):
-                if b is not None:
-                    b.free()
-        return cleaned, rec
+            return self._cleaned(n_samples, frames, EXCISE_DTYPE, lambda d_out, d_rec: self.excise_chirp_dev(
+                cap, cap.nbytes, first_sample, n_samples, nfft, rate, thr, d_out, d_rec))
 
     def blank(self, raw, threshold: float, window: int = 16, guard: int = 8, first_sample: int = 0,
               n_samples: Optional[int] = None):
@@ -1074,27 +1033,12 @@ class Device:
         cleaned range as a resident ``Capture`` of its own (the caller frees it) and one BLANK_DTYPE record per
         BLANK_BLOCK samples."""
         first_sample = int(first_sample)
-        own = None if isinstance(raw, Capture) else Capture(self, raw)
-        cap = raw if own is None else own
-        d_out = d_rec = None
-        try:
-            if not cap.ptr and cap.nbytes:
-                raise ValueError("the capture has been freed")
-            if n_samples is None:
-                n_samples = max(0, cap.nsamples - first_sample)
-            n_samples = int(n_samples)
+        with self._resident(raw) as cap:
+            n_samples = max(0, cap.nsamples - first_sample) if n_samples is None else int(n_samples)
             blocks = blank_blocks(n_samples)
             self._count("blank")
-            d_out = DevBuf(self, max(2 * n_samples, 1))
-            d_rec = DevBuf(self, max(blocks, 1) * BLANK_DTYPE.itemsize)
-            self.blank_dev(cap, cap.nbytes, first_sample, n_samples, window, guard, threshold, d_out, d_rec)
-            rec = d_rec.download(BLANK_DTYPE, blocks)
-            cleaned, d_out = Capture.from_device(self, d_out, 2 * n_samples), None
-        finally:
-            for b in (d_rec, d_out, own):
-                if b is not None:
-                    b.free()
-        return cleaned, rec
+            return self._cleaned(n_samples, blocks, BLANK_DTYPE, lambda d_out, d_rec: self.blank_dev(
+                cap, cap.nbytes, first_sample, n_samples, window, guard, threshold, d_out, d_rec))
 
     # ------------------------------------------------------------------ device pointers
     def blank_dev(self, d_iq, nbytes, first_sample, n_samples, window, guard, threshold, d_out, d_blocks=None):

@@ -20,6 +20,7 @@ Nothing here is a CPU fallback for the kernels: without the HIP library ``AcqSea
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from dataclasses import dataclass
 from typing import Iterator, List, Sequence
@@ -232,17 +233,14 @@ class AcqSearch:
         nbytes = getattr(capture, "nbytes", None)
         if nbytes is None:
             nbytes = capture.numel() * capture.element_size()
-        d_power = None
-        if want_power:
-            d_power = self.dev.alloc(8 * len(self.prns) * len(self.freqs) * self.nsamp)
-        self.dev.timer_start()
-        self.search_dev(capture, nbytes, first_sample, d_power)
-        self.dev.last_kernel_ms = self.dev.timer_stop()
-        res = self.results()
-        if want_power:
-            p = d_power.download(np.float64).reshape(len(self.prns), len(self.freqs), self.nsamp)
-            d_power.free()
-            return res, p
+        cells = len(self.prns) * len(self.freqs) * self.nsamp
+        with (self.dev.alloc(8 * cells) if want_power else contextlib.nullcontext()) as d_power:
+            self.dev.timer_start()
+            self.search_dev(capture, nbytes, first_sample, d_power)
+            self.dev.last_kernel_ms = self.dev.timer_stop()
+            res = self.results()
+            if want_power:
+                return res, d_power.download(np.float64).reshape(len(self.prns), len(self.freqs), self.nsamp)
         return res
 
     def series_workspace(self, n_epochs: int, epochs_per_launch: int = 0) -> int:
@@ -277,14 +275,11 @@ class AcqSearch:
         if n_epochs >= 1:
             self.dev.reserve(self.series_workspace(n_epochs, epochs_per_launch))
         rec = C.sizeof(_AcqStruct)
-        d_out = self.dev.alloc(rec * max(n_epochs, 1) * len(self.prns))
-        try:
+        with self.dev.alloc(rec * max(n_epochs, 1) * len(self.prns)) as d_out:
             self.dev.timer_start()
             self.series_dev(capture, nbytes, first_sample, stride_samples, n_epochs, d_out, epochs_per_launch)
             self.dev.last_kernel_ms = self.dev.timer_stop()
             raw = d_out.download(np.uint8, rec * n_epochs * len(self.prns))
-        finally:
-            d_out.free()
         r = np.frombuffer(raw.tobytes(), dtype=np.dtype([(n, np.float64 if t is C.c_double else np.int32)
                                                          for n, t in _AcqStruct._fields_]))
         r = r.reshape(n_epochs, len(self.prns))

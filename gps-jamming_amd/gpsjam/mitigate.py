@@ -71,12 +71,9 @@ def _psd_rows(dev, cap: Capture, n_samples: int, nfft: int, fs: float) -> np.nda
     chunk = min(int(n_samples), WELCH_CHUNK)
     rows = dev.welch_rows(nbytes, chunk, nfft)
     dev.reserve(dev.welch_workspace(nbytes, chunk, nfft))
-    d_psd = dev.alloc(4 * max(rows, 1) * nfft)
-    try:
+    with dev.alloc(4 * max(rows, 1) * nfft) as d_psd:
         dev.welch_dev(cap.ptr, nbytes, chunk, nfft, fs, d_psd, None, shift=False)
         return d_psd.download(np.float32, rows * nfft).reshape(rows, nfft)
-    finally:
-        d_psd.free()
 
 
 def thresholds(dev, capture, nfft: int = 1024, rise_db: float = 12.0, fs: float = 2.048e6, **onset_args):
@@ -85,27 +82,26 @@ def thresholds(dev, capture, nfft: int = 1024, rise_db: float = 12.0, fs: float 
     them, when at least 8 nfft samples lie there ("quiet part"); otherwise it is flat, the median over bins of the
     whole capture's floor ("flat median").  A bin of Gaussian noise exceeds a 12-dB threshold with probability e^-16."""
     nfft = int(nfft)
-    own = None if isinstance(capture, Capture) else Capture(dev, capture)
-    cap = capture if own is None else own
-    try:
+    with dev._resident(capture) as cap:
         k = int(dev.onset(cap, **onset_args).start_index)
         if k >= QUIET_FRAMES_MIN * nfft:
             floor, floor_from = floor_from_psd(_psd_rows(dev, cap, k, nfft, fs), fs, nfft), "quiet part"
         else:
             whole = floor_from_psd(_psd_rows(dev, cap, cap.nsamples, nfft, fs), fs, nfft)
             floor, floor_from = np.full(nfft, np.median(whole)), "flat median"
-    finally:
-        if own is not None:
-            own.free()
     return (floor * 10.0 ** (float(rise_db) / 10.0)).astype(np.float32), floor_from
+
+
+def _removed_share(rec) -> float:
+    """The share of the frames' power that the excisor's records say was removed (0 for frames without power)."""
+    total = float(rec["total"].astype(np.float64).sum())
+    return float(rec["removed"].astype(np.float64).sum()) / total if total > 0 else 0.0
 
 
 def clean(dev, capture, nfft: int = 1024, rise_db: float = 12.0, fs: float = 2.048e6, threshold=None, **onset_args) -> Cleaned:
     """The whole capture excised at ``nfft`` points against ``thresholds(...)`` (or a given ``threshold``).
     ``capture``: a resident ``Capture`` or host bytes (uploaded once)."""
-    own = None if isinstance(capture, Capture) else Capture(dev, capture)
-    cap = capture if own is None else own
-    try:
+    with dev._resident(capture) as cap:
         if threshold is None:
             threshold, floor_from = thresholds(dev, cap, nfft, rise_db, fs, **onset_args)
         else:
@@ -113,12 +109,7 @@ def clean(dev, capture, nfft: int = 1024, rise_db: float = 12.0, fs: float = 2.0
         if excise_frames(cap.nsamples, nfft) == 0:
             raise ValueError(f"the capture holds {cap.nsamples} samples, fewer than one frame of {int(nfft)}")
         cleaned, rec = dev.excise(cap, threshold, nfft=nfft)
-    finally:
-        if own is not None:
-            own.free()
-    total = float(rec["total"].astype(np.float64).sum())
-    share = float(rec["removed"].astype(np.float64).sum()) / total if total > 0 else 0.0
-    return Cleaned(cleaned, rec, threshold, floor_from, share)
+    return Cleaned(cleaned, rec, threshold, floor_from, _removed_share(rec))
 
 
 class CleanedSwept(NamedTuple):
@@ -159,10 +150,7 @@ def clean_swept(dev, capture, nfft: int = 1024, rise_db: float = 12.0, fs: float
     from . import CHIRP_DTYPE, DevBuf, classify
     nfft, rate_span = int(nfft), int(rate_span)
     onset_only = {k: v for k, v in onset_args.items() if k != "max_sweep_hz_per_s"}
-    own = None if isinstance(capture, Capture) else Capture(dev, capture)
-    cap = capture if own is None else own
-    d_scan = d_rate = None
-    try:
+    with dev._resident(capture) as cap:
         if sweep_hz_per_s is None:
             found = classify.characterise_swept(dev, cap, fs=fs, **onset_args)
             if found.kind != "chirp":
@@ -181,19 +169,12 @@ def clean_swept(dev, capture, nfft: int = 1024, rise_db: float = 12.0, fs: float
             raise ValueError(f"the capture holds {cap.nsamples} samples, fewer than one frame of {nfft}")
         q0 = sweep_rate_units(sweep_hz_per_s, nfft, fs)
         first, n_rates = q0 - rate_span, 2 * rate_span + 1
-        d_scan = DevBuf(dev, frames * CHIRP_DTYPE.itemsize)
-        d_rate = DevBuf(dev, 4 * frames)
-        dev.chirp_dev(cap, cap.nbytes, 0, nfft, nfft // 2, frames, 2, first, 1, n_rates, d_scan)
-        dev.chirp_rates_dev(d_scan, frames, first, 1, min_concentration, d_rate)
-        cleaned, rec = dev.excise_chirp(cap, threshold, d_rate, nfft=nfft)
-        rates = d_rate.download(np.int32, frames)
-    finally:
-        for b in (d_scan, d_rate, own):
-            if b is not None:
-                b.free()
-    total = float(rec["total"].astype(np.float64).sum())
-    share = float(rec["removed"].astype(np.float64).sum()) / total if total > 0 else 0.0
-    return CleanedSwept(cleaned, rec, threshold, floor_from, share, rates, sweep_hz_per_s, True)
+        with DevBuf(dev, frames * CHIRP_DTYPE.itemsize) as d_scan, DevBuf(dev, 4 * frames) as d_rate:
+            dev.chirp_dev(cap, cap.nbytes, 0, nfft, nfft // 2, frames, 2, first, 1, n_rates, d_scan)
+            dev.chirp_rates_dev(d_scan, frames, first, 1, min_concentration, d_rate)
+            cleaned, rec = dev.excise_chirp(cap, threshold, d_rate, nfft=nfft)
+            rates = d_rate.download(np.int32, frames)
+    return CleanedSwept(cleaned, rec, threshold, floor_from, _removed_share(rec), rates, sweep_hz_per_s, True)
 
 
 class CleanedPulsed(NamedTuple):
@@ -217,16 +198,10 @@ def _floor_low_percentile(dev, cap: Capture, floor_pct: float) -> float:
     n = dev.chunk_count(nbytes, FLOOR_CHUNK_BYTES)
     if n == 0:
         raise ValueError("the capture holds no sample")
-    d_power = d_stats = None
-    try:
-        d_power, d_stats = DevBuf(dev, 4 * n), DevBuf(dev, 12)
+    with DevBuf(dev, 4 * n) as d_power, DevBuf(dev, 12) as d_stats:
         dev.chunk_power_dev(cap, nbytes, FLOOR_CHUNK_BYTES, d_power, eps=0.0)
         dev.power_threshold_dev(d_power, n, d_stats, None, pct=float(floor_pct), rise_db=0.0)
         return float(d_stats.download(np.float32, 3)[0])
-    finally:
-        for b in (d_power, d_stats):
-            if b is not None:
-                b.free()
 
 
 def clean_pulsed(dev, capture, window: int = 16, guard: int = 8, rise_db: float = 6.0, threshold=None,
@@ -244,9 +219,7 @@ def clean_pulsed(dev, capture, window: int = 16, guard: int = 8, rise_db: float 
     percentile of a chunk mean of noise reads the floor a few tenths of a dB low (215.75 against 227 LSB^2, -0.22 dB, at the 25th
     percentile on a 30 % train): the blanker then triggers slightly early, never late.  A given ``threshold`` is used as
     it is ("given")."""
-    own = None if isinstance(capture, Capture) else Capture(dev, capture)
-    cap = capture if own is None else own
-    try:
+    with dev._resident(capture) as cap:
         if threshold is not None:
             floor_from = "given"
         else:
@@ -258,9 +231,6 @@ def clean_pulsed(dev, capture, window: int = 16, guard: int = 8, rise_db: float 
             threshold = floor * 10.0 ** (float(rise_db) / 10.0)
         threshold = float(np.float32(threshold))
         cleaned, rec = dev.blank(cap, threshold, window=window, guard=guard)
-    finally:
-        if own is not None:
-            own.free()
     total = int(rec["total"].sum(dtype=np.uint64))
     removed = int(rec["removed"].sum(dtype=np.uint64))
     blanked = int(rec["n_blanked"].sum(dtype=np.int64))

@@ -15,6 +15,7 @@ import pytest
 import blank_restatement as br
 import excise_restatement as er
 import gpsjam
+import host_lib
 from gpsjam import _ffi, mitigate
 
 
@@ -184,44 +185,13 @@ def restated_onset(raw, noise_samples, window, factor):
     return (int(hit[0]) + window // 2 if hit.size else -1), noise, noise * factor
 
 
-class HostLib:
+class HostLib(host_lib.HostLib):
     """The library's entry points that Device.blank and mitigate.clean_pulsed reach, computed by the restatements on host
-    memory: a "device address" is the address of a numpy buffer this object keeps alive."""
+    memory (tests/host_lib.py)."""
 
     def __init__(self):
-        self.mem, self.calls, self.offset = {}, [], 127.5
-
-    def _new(self, nbytes):
-        buf = np.zeros(max(int(nbytes), 1), np.uint8)
-        self.mem[buf.ctypes.data] = buf
-        return buf.ctypes.data
-
-    @staticmethod
-    def view(addr, count, dtype=np.uint8):
-        addr = addr.value if isinstance(addr, C.c_void_p) else int(addr)
-        dt = np.dtype(dtype)
-        return np.frombuffer((C.c_uint8 * (count * dt.itemsize)).from_address(addr), dt)
-
-    def gj_malloc(self, ctx, nbytes, ref):
-        self.calls.append(("malloc", int(nbytes)))
-        ref._obj.value = self._new(nbytes)
-        return 0
-
-    def gj_upload(self, ctx, data, nbytes, ref):
-        ref._obj.value = self._new(nbytes)
-        if nbytes:
-            C.memmove(ref._obj.value, data, nbytes)
-        return 0
-
-    def gj_free(self, ctx, ptr):
-        self.mem.pop(int(ptr), None)
-        return 0
-
-    def gj_memcpy_h2d(self, ctx, dst, src, nbytes):
-        C.memmove(dst, src, nbytes)
-        return 0
-
-    gj_memcpy_d2h = gj_memcpy_h2d
+        super().__init__()
+        self.offset = 127.5
 
     def gj_blank_dev(self, ctx, d_iq, nbytes, first, n_samples, window, guard, threshold, d_out, d_blocks):
         self.calls.append(("blank", first, n_samples, window, guard, threshold))
@@ -258,8 +228,7 @@ class HostLib:
 
 @pytest.fixture
 def host_dev():
-    dev = object.__new__(gpsjam.Device)
-    dev._lib, dev._ctx, dev.kernel_calls, dev.cache_hits, dev.last_kernel_ms = HostLib(), C.c_void_p(1), {}, 0, 0.0
+    dev = host_lib.host_device(HostLib())
     yield dev
     dev._ctx = None            # a Capture that outlives the test frees nothing
 
@@ -295,6 +264,21 @@ def test_device_blank_on_the_host_double(host_dev):
     with pytest.raises(ValueError, match="freed"):
         host_dev.blank(freed, 1.0)
     assert host_dev.kernel_calls == {"blank": 3}, "a refused call counts nothing"
+
+
+def test_device_blank_refusals(host_dev):
+    raw, lib = br.parity_capture(), host_dev._lib
+    host_lib.check_freed(host_dev, raw, lambda cap: host_dev.blank(cap, br.PARITY_THRESHOLD))
+    # what the library refuses (a negative threshold, an empty range): the output and the records are allocated, never
+    # empty, and freed
+    lib.refuse("gj_blank_dev")
+    host_lib.check_refused(host_dev, raw, lambda s: host_dev.blank(s, -1.0, first_sample=br.PARITY_FIRST, n_samples=br.PARITY_SAMPLES),
+                           gpsjam.GpsJamError, host_lib.REFUSED_TEXT, counted="blank")
+    assert host_lib.mallocs(lib) == [2 * br.PARITY_SAMPLES, 24 * 4] * 2
+    lib.calls.clear()
+    host_lib.check_refused(host_dev, raw, lambda s: host_dev.blank(s, 1.0, first_sample=raw.size // 2), gpsjam.GpsJamError,
+                           host_lib.REFUSED_TEXT, counted="blank")
+    assert host_lib.mallocs(lib) == [1, 24] * 2 and host_dev.kernel_calls == {"blank": 4}
 
 
 def shares(res):

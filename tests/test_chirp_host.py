@@ -9,6 +9,7 @@ import pytest
 
 import chirp_restatement as cr
 import gpsjam
+import host_lib
 import ridge_restatement as rr
 from gpsjam import _ffi, classify
 
@@ -205,3 +206,77 @@ def test_the_ridge_alone_reads_the_fast_chirp_as_broadband():
           f"line needs {max(0.5 * res.evidence['line_min'], 2 * res.evidence['noise_concentration']):.4f}")
     assert res.kind == "broadband", res
     assert res.sweep_hz_per_s is None
+
+
+# ------------------------------------------------------------------------------------------------ the Python layer
+class HostLib(host_lib.HostLib):
+    """gj_chirp_dev, which Device.chirp reaches, computed by the restatement on host memory (tests/host_lib.py)."""
+
+    def gj_chirp_dev(self, ctx, d_iq, nbytes, first, nfft, hop, n_frames, guard, rate_first, rate_step, n_rates, d_out, d_peaks):
+        self.calls.append(("chirp", first, nfft, hop, n_frames, guard, rate_first, rate_step, n_rates, bool(d_peaks)))
+        scan = cr.chirp_scan(self.view(d_iq, nbytes), nfft, hop, (rate_first, rate_step, n_rates), first, n_frames, guard)
+        rec = self.view(d_out, n_frames, gpsjam.CHIRP_DTYPE)
+        for key in ("total", "peak", "second", "peak_bin", "rate_index"):
+            rec[key] = scan.records[key]
+        if d_peaks:
+            self.view(d_peaks, n_frames * n_rates, np.float32)[:] = scan.peaks.reshape(-1)
+        return 0
+
+
+@pytest.fixture
+def host_dev():
+    dev = host_lib.host_device(HostLib())
+    yield dev
+    dev._ctx = None            # a Capture that outlives the test frees nothing
+
+
+W_NFFT, W_HOP, W_FIRST, W_FRAMES, W_RATES = 16, 5, 1, 10, (-2, 1, 5)
+W_RAW = rr.parity_capture()[:2 * (W_FIRST + (W_FRAMES - 1) * W_HOP + W_NFFT + 3)]      # two samples short of an 11th frame
+
+
+def test_device_chirp_on_the_host_double(host_dev):
+    lib = host_dev._lib
+    ref = cr.chirp_scan(W_RAW, W_NFFT, W_HOP, W_RATES, W_FIRST, guard=1)
+    want = as_scan(ref, W_RATES, W_NFFT, W_HOP, W_FIRST)
+    assert len(want) == W_FRAMES == gpsjam.ridge_frames(W_RAW.size, W_FIRST, W_NFFT, W_HOP) and want.rate_index.any()
+    for n, (source, held) in enumerate(host_lib.sources(host_dev, W_RAW), 1):
+        lib.calls.clear()
+        uploads = gpsjam.Capture.uploads
+        got = host_dev.chirp(source, W_NFFT, W_HOP, W_RATES, first_sample=W_FIRST, guard=1, want_peaks=True)
+        assert gpsjam.Capture.uploads == uploads + (source is W_RAW), "host bytes are uploaded once, a resident capture never"
+        assert isinstance(got, gpsjam.ChirpScan) and got.records.tobytes() == want.records.tobytes()
+        assert (got.nfft, got.hop, got.first_sample, got.guard, got.rates) == (W_NFFT, W_HOP, W_FIRST, 1, W_RATES)
+        assert got.peaks.shape == (W_FRAMES, 5) and got.peaks.tobytes() == want.peaks.tobytes()
+        assert host_lib.mallocs(lib) == [24 * W_FRAMES, 4 * W_FRAMES * 5], "the records, then the peaks"
+        assert lib.calls[-1] == ("chirp", W_FIRST, W_NFFT, W_HOP, W_FRAMES, 1, -2, 1, 5, True) and host_dev.kernel_calls == {"chirp": n}
+        assert set(lib.mem) == held, "every buffer of the call's own is freed"
+    # the defaults: hop nfft / 2, the one rate 0, guard 2, no peaks; a given frame count is taken as it is
+    lib.calls.clear()
+    part = host_dev.chirp(W_RAW, W_NFFT, n_frames=6)
+    assert lib.calls == [("malloc", 24 * 6), ("chirp", 0, W_NFFT, W_NFFT // 2, 6, 2, 0, 1, 1, False)]
+    assert part.peaks is None and (part.hop, part.guard, part.rates, len(part)) == (8, 2, (0, 1, 1), 6)
+    assert part.records.tobytes() == as_scan(cr.chirp_scan(W_RAW, W_NFFT, 8, (0, 1, 1), 0, 6), (0, 1, 1)).records.tobytes()
+    assert not lib.mem and host_dev.kernel_calls == {"chirp": 3}
+
+
+def test_device_chirp_refusals_and_the_empty_result(host_dev):
+    lib = host_dev._lib
+    host_lib.check_freed(host_dev, W_RAW, lambda cap: host_dev.chirp(cap, W_NFFT))
+    # no frame fits: an empty ChirpScan with the call's geometry, and the library is not reached
+    for source, held in host_lib.sources(host_dev, W_RAW[:2 * (W_NFFT - 1)]):
+        for want_peaks in (False, True):
+            empty = host_dev.chirp(source, W_NFFT, W_HOP, W_RATES, guard=3, want_peaks=want_peaks)
+            assert len(empty) == 0 and empty.records.dtype == gpsjam.CHIRP_DTYPE
+            assert (empty.nfft, empty.hop, empty.guard, empty.rates) == (W_NFFT, W_HOP, 3, W_RATES)
+            assert (empty.peaks.shape == (0, 5) and empty.peaks.dtype == np.float32) if want_peaks else empty.peaks is None
+            assert set(lib.mem) == held and host_dev.kernel_calls == {} and not host_lib.mallocs(lib)
+    # ... unless the geometry or the rate grid is one the library refuses: that is left to the library
+    lib.refuse("gj_chirp_dev")
+    host_lib.check_refused(host_dev, W_RAW[:2 * (W_NFFT - 1)], lambda s: host_dev.chirp(s, W_NFFT, rates=(0, 1, 257)),
+                           gpsjam.GpsJamError, host_lib.REFUSED_TEXT, counted="chirp")
+    assert host_lib.mallocs(lib) == [24] * 2, "a record buffer is never empty"
+    lib.calls.clear()
+    host_lib.check_refused(host_dev, W_RAW, lambda s: host_dev.chirp(s, W_NFFT, W_HOP, W_RATES, want_peaks=True), gpsjam.GpsJamError,
+                           host_lib.REFUSED_TEXT, counted="chirp")
+    assert host_lib.mallocs(lib) == [24 * W_FRAMES, 4 * W_FRAMES * 5] * 2
+    assert host_dev.kernel_calls == {"chirp": 4}

@@ -16,6 +16,7 @@ import chirp_restatement as cr
 import excise_chirp_restatement as xr
 import excise_restatement as er
 import gpsjam
+import host_lib
 from gpsjam import _ffi, classify, mitigate
 
 
@@ -154,43 +155,11 @@ def test_restated_removal_is_complete_in_the_chirp_domain_only(nfft):
 
 
 # ------------------------------------------------------------------------------------------------ the Python layers
-class HostLib:
+class HostLib(host_lib.HostLib):
     """The library's entry points that Device.excise_chirp and mitigate.clean_swept reach, computed by the restatements
-    on host memory: a "device address" is the address of a numpy buffer this object keeps alive."""
+    on host memory (tests/host_lib.py)."""
 
-    def __init__(self):
-        self.mem, self.calls = {}, []
-
-    def _new(self, nbytes):
-        buf = np.zeros(max(int(nbytes), 1), np.uint8)
-        self.mem[buf.ctypes.data] = buf
-        return buf.ctypes.data
-
-    @staticmethod
-    def view(addr, count, dtype=np.uint8):
-        addr = addr.value if isinstance(addr, C.c_void_p) else int(addr)
-        dt = np.dtype(dtype)
-        return np.frombuffer((C.c_uint8 * (count * dt.itemsize)).from_address(addr), dt)
-
-    def gj_malloc(self, ctx, nbytes, ref):
-        ref._obj.value = self._new(nbytes)
-        return 0
-
-    def gj_upload(self, ctx, data, nbytes, ref):
-        ref._obj.value = self._new(nbytes)
-        if nbytes:
-            C.memmove(ref._obj.value, data, nbytes)
-        return 0
-
-    def gj_free(self, ctx, ptr):
-        self.mem.pop(int(ptr), None)
-        return 0
-
-    def gj_memcpy_h2d(self, ctx, dst, src, nbytes):
-        C.memmove(dst, src, nbytes)
-        return 0
-
-    gj_memcpy_d2h = gj_memcpy_h2d
+    log_malloc = False       # ``calls`` holds the kernel calls alone
 
     def gj_chirp_dev(self, ctx, d_iq, nbytes, first, nfft, hop, n_frames, guard, rate_first, rate_step, n_rates, d_out, d_peaks):
         self.calls.append(("chirp", first, nfft, hop, n_frames, rate_first, rate_step, n_rates))
@@ -221,8 +190,7 @@ class HostLib:
 
 @pytest.fixture
 def host_dev():
-    dev = object.__new__(gpsjam.Device)
-    dev._lib, dev._ctx, dev.kernel_calls, dev.cache_hits, dev.last_kernel_ms = HostLib(), C.c_void_p(1), {}, 0, 0.0
+    dev = host_lib.host_device(HostLib())
     yield dev
     dev._ctx = None            # a Capture that outlives the test frees nothing
 
@@ -252,6 +220,44 @@ def test_device_excise_chirp_on_the_host_double(host_dev):
     with pytest.raises(ValueError, match="threshold holds"):
         host_dev.excise_chirp(raw, thr[:-1], rates, nfft=nfft, first_sample=1)
     assert host_dev.kernel_calls == {"excise_chirp": 2}, "a refused call counts nothing"
+
+
+def test_device_excise_chirp_refusals_and_buffers(host_dev):
+    nfft = 64
+    raw = xr.parity_capture(nfft)[:2 * (1 + 20 * nfft)]
+    n = raw.size // 2 - 1
+    nf = gpsjam.excise_frames(n, nfft)
+    rates, thr, lib = xr.parity_rates(nfft, nf), xr.parity_threshold(nfft), host_dev._lib
+    lib.log_malloc = True
+    call = lambda thr, rates: (lambda s: host_dev.excise_chirp(s, thr, rates, nfft=nfft, first_sample=1))
+    host_lib.check_freed(host_dev, raw, call(thr, rates))
+    host_lib.check_refused(host_dev, raw, call(thr[:-1], rates), ValueError, "threshold holds 63 values, nfft is 64")
+    assert not host_lib.mallocs(lib), "the thresholds are checked in front of their upload"
+    for bad in (rates[:-1], np.append(rates, 0)):
+        host_lib.check_refused(host_dev, raw, call(thr, bad), ValueError,
+                               f"rates holds {bad.size} values, the range has {nf} frames of 64 points")
+    host_lib.check_refused(host_dev, raw, call(thr, rates.astype(np.float64)), TypeError, "rates must be integers")
+    assert host_lib.mallocs(lib) == [4 * nfft] * 6, "the thresholds were on the device by then, and are freed"
+    assert host_dev.kernel_calls == {}
+    # the buffers of a call that goes through: thresholds, rates, output, records; all but the output are freed
+    for k, (source, held) in enumerate(host_lib.sources(host_dev, raw), 1):
+        lib.calls.clear()
+        uploads = gpsjam.Capture.uploads
+        cleaned, rec = call(thr, rates.tolist())(source)
+        assert gpsjam.Capture.uploads == uploads + (source is raw), "host bytes are uploaded once; the cleaned capture is no upload"
+        assert host_lib.mallocs(lib) == [4 * nfft, 4 * nf, 2 * n, 16 * nf] and rec.size == nf and cleaned.nbytes == 2 * n
+        assert set(lib.mem) == held | {cleaned.ptr} and host_dev.kernel_calls == {"excise_chirp": k}
+        cleaned.free()
+    # what the library refuses: everything is allocated by then, and freed
+    lib.calls.clear()
+    lib.refuse("gj_excise_chirp_dev")
+    host_lib.check_refused(host_dev, raw, call(thr, rates), gpsjam.GpsJamError, host_lib.REFUSED_TEXT, counted="excise_chirp")
+    assert host_lib.mallocs(lib) == [4 * nfft, 4 * nf, 2 * n, 16 * nf] * 2
+    # a range shorter than a frame has no frame: no rate is wanted, and the buffers are never empty
+    lib.calls.clear()
+    host_lib.check_refused(host_dev, raw, lambda s: host_dev.excise_chirp(s, thr, [], nfft=nfft, n_samples=nfft - 1), gpsjam.GpsJamError,
+                           host_lib.REFUSED_TEXT, counted="excise_chirp")
+    assert host_lib.mallocs(lib) == [4 * nfft, 4, 2 * (nfft - 1), 16] * 2 and host_dev.kernel_calls == {"excise_chirp": 6}
 
 
 def test_clean_swept_on_the_host_double(host_dev, monkeypatch):

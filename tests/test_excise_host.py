@@ -9,6 +9,7 @@ import pytest
 
 import excise_restatement as er
 import gpsjam
+import host_lib
 import ridge_restatement as rr
 from gpsjam import _ffi, mitigate
 
@@ -149,3 +150,102 @@ def test_gpu_inputs_keep_clear_of_rounding_ties_and_of_their_thresholds():
     assert e32 <= er.E32
     assert max(share.values()) <= 0.01, share
     assert min(margin.values()) >= er.NEAR_TIE, margin
+
+
+# ------------------------------------------------------------------------------------------------ the Python layers
+class HostLib(host_lib.HostLib):
+    """gj_excise_dev, which Device.excise and mitigate.clean reach, computed by the restatement on host memory
+    (tests/host_lib.py)."""
+
+    def gj_excise_dev(self, ctx, d_iq, nbytes, first, n_samples, nfft, d_thr, d_out, d_frames):
+        self.calls.append(("excise", first, n_samples, nfft))
+        ex = er.excise(self.view(d_iq, nbytes), self.view(d_thr, nfft, np.float32), nfft, first, n_samples)
+        self.view(d_out, 2 * n_samples)[:] = ex.out
+        if d_frames:
+            rec = self.view(d_frames, ex.records.size, gpsjam.EXCISE_DTYPE)
+            for key in ("total", "removed", "n_excised"):
+                rec[key] = ex.records[key]
+        return 0
+
+
+@pytest.fixture
+def host_dev():
+    dev = host_lib.host_device(HostLib())
+    yield dev
+    dev._ctx = None            # a Capture that outlives the test frees nothing
+
+
+W_NFFT, W_FIRST, W_SAMPLES = 16, 1, 10 * 16 + 5
+W_FRAMES = er.frames_loop(W_SAMPLES, W_NFFT)                   # 19, and a tail of 13 samples
+W_RAW = er.parity_capture()[:2 * (W_FIRST + W_SAMPLES)]
+
+
+def w_threshold():
+    thr = er.parity_threshold(W_NFFT)
+    thr[3] = -1.0              # one bin goes whatever the frame holds
+    return thr
+
+
+def as_records(rec):
+    out = np.zeros(rec.size, gpsjam.EXCISE_DTYPE)
+    for key in ("total", "removed", "n_excised"):
+        out[key] = rec[key]
+    return out
+
+
+def test_device_excise_on_the_host_double(host_dev):
+    lib, thr = host_dev._lib, w_threshold()
+    want = er.excise(W_RAW, thr, W_NFFT, W_FIRST)
+    assert want.records.size == W_FRAMES == 19 == gpsjam.excise_frames(W_SAMPLES, W_NFFT) and np.all(want.records["n_excised"] >= 1)
+    for n, (source, held) in enumerate(host_lib.sources(host_dev, W_RAW), 1):
+        lib.calls.clear()
+        uploads = gpsjam.Capture.uploads
+        cleaned, rec = host_dev.excise(source, thr, nfft=W_NFFT, first_sample=W_FIRST)
+        assert gpsjam.Capture.uploads == uploads + (source is W_RAW), "host bytes are uploaded once; the cleaned capture is no upload"
+        assert isinstance(cleaned, gpsjam.Capture) and cleaned.nbytes == 2 * W_SAMPLES and rec.dtype == gpsjam.EXCISE_DTYPE
+        assert np.array_equal(HostLib.view(cleaned.ptr, cleaned.nbytes), want.out) and rec.tobytes() == as_records(want.records).tobytes()
+        assert host_lib.mallocs(lib) == [4 * W_NFFT, 2 * W_SAMPLES, 16 * W_FRAMES], "the thresholds, the output, the records"
+        assert lib.calls[-1] == ("excise", W_FIRST, W_SAMPLES, W_NFFT) and host_dev.kernel_calls == {"excise": n}
+        assert set(lib.mem) == held | {cleaned.ptr}, "every buffer but the result is freed"
+        cleaned.free()
+    # thresholds that are on the device already are taken as they are; a given range
+    d_thr = gpsjam.DevBuf(host_dev, 4 * W_NFFT).upload(thr)
+    lib.calls.clear()
+    part, rec = host_dev.excise(W_RAW, d_thr, nfft=W_NFFT, n_samples=64)
+    assert lib.calls == [("malloc", 128), ("malloc", 16 * 7), ("excise", 0, 64, W_NFFT)] and part.nbytes == 128 and rec.size == 7
+    assert np.array_equal(HostLib.view(part.ptr, 128), er.excise(W_RAW, thr, W_NFFT, 0, 64).out)
+    assert set(lib.mem) == {d_thr.ptr, part.ptr} and host_dev.kernel_calls == {"excise": 3}
+    part.free()
+    d_thr.free()
+    assert not lib.mem
+
+
+def test_device_excise_refusals(host_dev):
+    lib, thr = host_dev._lib, w_threshold()
+    host_lib.check_freed(host_dev, W_RAW, lambda cap: host_dev.excise(cap, thr, nfft=W_NFFT))
+    for bad in (thr[:-1], np.append(thr, 0.0)):
+        host_lib.check_refused(host_dev, W_RAW, lambda s: host_dev.excise(s, bad, nfft=W_NFFT), ValueError,
+                               f"threshold holds {bad.size} values, nfft is 16")
+    assert not host_lib.mallocs(lib) and host_dev.kernel_calls == {}
+    # a range shorter than a frame is the library's to refuse: the output and the records are allocated, never empty, and freed
+    lib.refuse("gj_excise_dev")
+    host_lib.check_refused(host_dev, W_RAW, lambda s: host_dev.excise(s, thr, nfft=W_NFFT, first_sample=W_FIRST + W_SAMPLES),
+                           gpsjam.GpsJamError, host_lib.REFUSED_TEXT, counted="excise")
+    assert host_lib.mallocs(lib) == [4 * W_NFFT, 1, 16] * 2 and host_dev.kernel_calls == {"excise": 2}
+
+
+def test_clean_with_a_given_threshold_on_the_host_double(host_dev):
+    lib, thr = host_dev._lib, w_threshold()
+    want = er.excise(W_RAW, thr, W_NFFT)
+    for source, held in host_lib.sources(host_dev, W_RAW):
+        res = mitigate.clean(host_dev, source, nfft=W_NFFT, threshold=thr.astype(np.float64))
+        assert isinstance(res, mitigate.Cleaned) and res.floor_from == "given" and res.threshold.dtype == np.float32
+        assert np.array_equal(res.threshold, thr) and res.records.tobytes() == as_records(want.records).tobytes()
+        assert np.array_equal(HostLib.view(res.capture.ptr, res.capture.nbytes), want.out)
+        total = float(res.records["total"].astype(np.float64).sum())
+        assert res.removed_share == float(res.records["removed"].astype(np.float64).sum()) / total and 0.0 < res.removed_share < 1.0
+        assert set(lib.mem) == held | {res.capture.ptr}
+        res.capture.free()
+    assert host_dev.kernel_calls == {"excise": 2}
+    host_lib.check_refused(host_dev, W_RAW[:2 * (W_NFFT - 1)], lambda s: mitigate.clean(host_dev, s, nfft=W_NFFT, threshold=thr),
+                           ValueError, "the capture holds 15 samples, fewer than one frame of 16")

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import gpsjam
+import host_lib
 import ridge_restatement as rr
 from gpsjam import _ffi, classify
 
@@ -184,3 +185,68 @@ def test_no_gpu_input_has_a_nearly_tied_peak():
         worst[case] = float(margin.min())
     bad = {k: v for k, v in worst.items() if v < rr.NEAR_TIE}
     assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------ the Python layer
+class HostLib(host_lib.HostLib):
+    """gj_ridge_dev, which Device.ridge reaches, computed by the restatement on host memory (tests/host_lib.py)."""
+
+    def gj_ridge_dev(self, ctx, d_iq, nbytes, first, nfft, hop, n_frames, guard, d_out):
+        self.calls.append(("ridge", first, nfft, hop, n_frames, guard))
+        rec, _ = rr.ridge(self.view(d_iq, nbytes), nfft, hop, first, n_frames, guard)
+        out = self.view(d_out, n_frames, gpsjam.RIDGE_DTYPE)
+        for key in gpsjam.RIDGE_DTYPE.names:
+            out[key] = rec[key]
+        return 0
+
+
+@pytest.fixture
+def host_dev():
+    dev = host_lib.host_device(HostLib())
+    yield dev
+    dev._ctx = None            # a Capture that outlives the test frees nothing
+
+
+W_NFFT, W_HOP, W_FIRST, W_FRAMES = 16, 5, 3, 12
+W_RAW = rr.parity_capture()[:2 * (W_FIRST + (W_FRAMES - 1) * W_HOP + W_NFFT + 2)]      # two samples short of a 13th frame
+
+
+def test_device_ridge_on_the_host_double(host_dev):
+    lib = host_dev._lib
+    want = rr.ridge(W_RAW, W_NFFT, W_HOP, W_FIRST)[0].astype(gpsjam.RIDGE_DTYPE)
+    assert want.size == W_FRAMES == gpsjam.ridge_frames(W_RAW.size, W_FIRST, W_NFFT, W_HOP)
+    for n, (source, held) in enumerate(host_lib.sources(host_dev, W_RAW), 1):
+        lib.calls.clear()
+        uploads = gpsjam.Capture.uploads
+        got = host_dev.ridge(source, W_NFFT, W_HOP, first_sample=W_FIRST, guard=1)
+        assert gpsjam.Capture.uploads == uploads + (source is W_RAW), "host bytes are uploaded once, a resident capture never"
+        assert isinstance(got, gpsjam.Ridge) and (got.nfft, got.hop, got.first_sample, got.guard) == (W_NFFT, W_HOP, W_FIRST, 1)
+        assert got.records.tobytes() == rr.ridge(W_RAW, W_NFFT, W_HOP, W_FIRST, guard=1)[0].astype(gpsjam.RIDGE_DTYPE).tobytes()
+        assert got.total.tobytes() == want["total"].tobytes() and np.array_equal(got.peak_bin, want["peak_bin"])
+        assert host_lib.mallocs(lib) == [16 * W_FRAMES], "one record buffer"
+        assert lib.calls[-1] == ("ridge", W_FIRST, W_NFFT, W_HOP, W_FRAMES, 1) and host_dev.kernel_calls == {"ridge": n}
+        assert set(lib.mem) == held, "every buffer of the call's own is freed"
+    # the defaults: hop nfft / 2, guard 2, the range from sample 0; a given frame count is taken as it is
+    lib.calls.clear()
+    part = host_dev.ridge(W_RAW, W_NFFT, n_frames=7)
+    assert lib.calls == [("malloc", 16 * 7), ("ridge", 0, W_NFFT, W_NFFT // 2, 7, 2)] and (part.hop, part.guard, len(part)) == (8, 2, 7)
+    assert part.records.tobytes() == rr.ridge(W_RAW, W_NFFT, 8, 0, 7)[0].astype(gpsjam.RIDGE_DTYPE).tobytes()
+    assert not lib.mem and host_dev.kernel_calls == {"ridge": 3}
+
+
+def test_device_ridge_refusals_and_the_empty_result(host_dev):
+    lib = host_dev._lib
+    host_lib.check_freed(host_dev, W_RAW, lambda cap: host_dev.ridge(cap, W_NFFT))
+    # no frame fits: an empty Ridge with the call's geometry, and the library is not reached
+    for source, held in host_lib.sources(host_dev, W_RAW[:2 * (W_NFFT - 1)]):
+        empty = host_dev.ridge(source, W_NFFT, W_HOP, guard=3)
+        assert len(empty) == 0 and empty.records.dtype == gpsjam.RIDGE_DTYPE and (empty.nfft, empty.hop, empty.guard) == (W_NFFT, W_HOP, 3)
+        assert set(lib.mem) == held and host_dev.kernel_calls == {} and not host_lib.mallocs(lib)
+    # ... unless the geometry is one the library refuses: that is left to the library
+    lib.refuse("gj_ridge_dev")
+    host_lib.check_refused(host_dev, W_RAW[:2 * 7], lambda s: host_dev.ridge(s, 8), gpsjam.GpsJamError,
+                           host_lib.REFUSED_TEXT, counted="ridge")
+    host_lib.check_refused(host_dev, W_RAW, lambda s: host_dev.ridge(s, W_NFFT, n_frames=0), gpsjam.GpsJamError,
+                           host_lib.REFUSED_TEXT, counted="ridge")
+    assert host_lib.mallocs(lib) == [16] * 4, "a record buffer is never empty"
+    assert host_dev.kernel_calls == {"ridge": 4}

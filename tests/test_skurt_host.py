@@ -9,6 +9,7 @@ import pytest
 
 import excise_restatement as er
 import gpsjam
+import host_lib
 import ridge_restatement as rr
 import skurt_restatement as sr
 from gpsjam import _ffi, kurtosis
@@ -233,3 +234,72 @@ def test_no_gpu_input_has_a_cell_near_a_band_edge():
     print("smallest distance of a cell's SK to a band edge:", {k: f"{v:.2e}" for k, v in worst.items()})
     bad = {k: v for k, v in worst.items() if v < sr.EDGE}
     assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------ the Python layer
+class HostLib(host_lib.HostLib):
+    """gj_sk_dev, which Device.spectral_kurtosis reaches, computed by the restatement on host memory (tests/host_lib.py)."""
+
+    def gj_sk_dev(self, ctx, d_iq, nbytes, first, nfft, hop, frames_per_row, n_rows, d_s1, d_s2, d_sk):
+        self.calls.append(("sk", first, nfft, hop, frames_per_row, n_rows))
+        for addr, a in zip((d_s1, d_s2, d_sk), sr.sk(self.view(d_iq, nbytes), nfft, hop, frames_per_row, first, n_rows)):
+            if addr:
+                self.view(addr, n_rows * nfft, np.float32)[:] = a.reshape(-1)
+        return 0
+
+
+@pytest.fixture
+def host_dev():
+    dev = host_lib.host_device(HostLib())
+    yield dev
+    dev._ctx = None            # a Capture that outlives the test frees nothing
+
+
+W_NFFT, W_HOP, W_M, W_FIRST, W_ROWS = 16, 5, 3, 2, 4
+W_RAW = rr.parity_capture()[:2 * (W_FIRST + (W_ROWS * W_M - 1) * W_HOP + W_NFFT + 2 * W_HOP)]      # two frames short of a 5th row
+
+
+def test_device_spectral_kurtosis_on_the_host_double(host_dev):
+    lib = host_dev._lib
+    want = [a.astype(np.float32) for a in sr.sk(W_RAW, W_NFFT, W_HOP, W_M, W_FIRST)]
+    assert want[0].shape == (W_ROWS, W_NFFT) and gpsjam.sk_rows(W_RAW.size, W_FIRST, W_NFFT, W_HOP, W_M) == W_ROWS
+    for n, (source, held) in enumerate(host_lib.sources(host_dev, W_RAW), 1):
+        lib.calls.clear()
+        uploads = gpsjam.Capture.uploads
+        got = host_dev.spectral_kurtosis(source, W_NFFT, W_HOP, W_M, first_sample=W_FIRST)
+        assert gpsjam.Capture.uploads == uploads + (source is W_RAW), "host bytes are uploaded once, a resident capture never"
+        assert isinstance(got, gpsjam.SpectralKurtosis) and (got.nfft, got.hop, got.frames_per_row, got.first_sample) == (W_NFFT, W_HOP, W_M, W_FIRST)
+        for have, ref in zip((got.s1, got.s2, got.sk), want):
+            assert have.shape == (W_ROWS, W_NFFT) and have.tobytes() == ref.tobytes()
+        assert host_lib.mallocs(lib) == [3 * 4 * W_ROWS * W_NFFT], "one buffer holds the three arrays"
+        assert lib.calls[-1] == ("sk", W_FIRST, W_NFFT, W_HOP, W_M, W_ROWS) and host_dev.kernel_calls == {"spectral_kurtosis": n}
+        assert set(lib.mem) == held, "every buffer of the call's own is freed"
+    # the defaults: hop nfft, the range from sample 0; a given row count is taken as it is
+    lib.calls.clear()
+    part = host_dev.spectral_kurtosis(W_RAW, W_NFFT, frames_per_row=2, n_rows=2)
+    assert lib.calls == [("malloc", 3 * 4 * 2 * W_NFFT), ("sk", 0, W_NFFT, W_NFFT, 2, 2)] and (part.hop, len(part)) == (W_NFFT, 2)
+    for have, ref in zip((part.s1, part.s2, part.sk), sr.sk(W_RAW, W_NFFT, W_NFFT, 2, 0, 2)):
+        assert have.tobytes() == ref.astype(np.float32).tobytes()
+    assert not lib.mem and host_dev.kernel_calls == {"spectral_kurtosis": 3}
+
+
+def test_device_spectral_kurtosis_refusals_and_the_empty_result(host_dev):
+    lib = host_dev._lib
+    host_lib.check_freed(host_dev, W_RAW, lambda cap: host_dev.spectral_kurtosis(cap, W_NFFT))
+    # no row fits: an empty result with the call's geometry, and the library is not reached
+    short = W_RAW[:2 * (W_FIRST + (W_M - 1) * W_HOP + W_NFFT - 1)]                     # one sample short of the first row
+    for source, held in host_lib.sources(host_dev, short):
+        empty = host_dev.spectral_kurtosis(source, W_NFFT, W_HOP, W_M, first_sample=W_FIRST)
+        assert len(empty) == 0 and empty.s1.shape == empty.s2.shape == empty.sk.shape == (0, W_NFFT) and empty.sk.dtype == np.float32
+        assert (empty.nfft, empty.hop, empty.frames_per_row, empty.first_sample) == (W_NFFT, W_HOP, W_M, W_FIRST)
+        assert set(lib.mem) == held and host_dev.kernel_calls == {} and not host_lib.mallocs(lib)
+    # ... unless the geometry is one the library refuses: that is left to the library
+    lib.refuse("gj_sk_dev")
+    host_lib.check_refused(host_dev, short, lambda s: host_dev.spectral_kurtosis(s, W_NFFT, W_HOP, 1, first_sample=40),
+                           gpsjam.GpsJamError, host_lib.REFUSED_TEXT, counted="spectral_kurtosis")
+    assert host_lib.mallocs(lib) == [3 * 4 * W_NFFT] * 2, "the buffer is never empty"
+    lib.calls.clear()
+    host_lib.check_refused(host_dev, W_RAW, lambda s: host_dev.spectral_kurtosis(s, W_NFFT, W_HOP, W_M), gpsjam.GpsJamError,
+                           host_lib.REFUSED_TEXT, counted="spectral_kurtosis")
+    assert host_lib.mallocs(lib) == [3 * 4 * W_ROWS * W_NFFT] * 2
+    assert host_dev.kernel_calls == {"spectral_kurtosis": 4}
