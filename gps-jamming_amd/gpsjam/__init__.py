@@ -29,7 +29,7 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "library_path", "as_u8", "default_device", "read_capture", "resident_capture",
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
            "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE",
-           "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks"]
+           "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks", "FINE_BLOCK", "FINE_MAX_HALF", "fine_blocks", "FineCorr"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -193,6 +193,28 @@ def blank_blocks(n_samples: int) -> int:
     if not 0 <= int(n_samples) < 2 ** 64:
         return 0
     return int(_ffi.load().gj_blank_blocks(int(n_samples)))
+
+
+FINE_BLOCK = _ffi.GJ_FINE_BLOCK
+FINE_MAX_HALF = _ffi.GJ_FINE_MAX_HALF
+
+
+def fine_blocks(n_samples: int) -> int:
+    """Block records of the lag-window correlation over n_samples: one per FINE_BLOCK samples, the last one ragged
+    (gj_fine_blocks)."""
+    if not 0 <= int(n_samples) < 2 ** 64:
+        return 0
+    return int(_ffi.load().gj_fine_blocks(int(n_samples)))
+
+
+class FineCorr(NamedTuple):
+    """``Device.xcorr_fine``: correlate(x_b, x_a, 'full') at the lags ``lags`` in K5's unpacking, from the exact integers
+    of gj_xcorr_fine_dev (c = C4 / 4: exact in complex128 up to 2^53 / 4 per part).  ``blocks[m]`` is the same over the
+    m-th FINE_BLOCK samples of a alone (None unless asked for); the rows sum to ``c``."""
+    lags: np.ndarray        # int64[2R+1]
+    c: np.ndarray           # complex128[2R+1]
+    blocks: Optional[np.ndarray]   # complex128[blocks][2R+1] or None
+    n_samples: int
 
 
 class Ridge:
@@ -1040,7 +1062,41 @@ class Device:
             return self._cleaned(n_samples, blocks, BLANK_DTYPE, lambda d_out, d_rec: self.blank_dev(
                 cap, cap.nbytes, first_sample, n_samples, window, guard, threshold, d_out, d_rec))
 
+    def xcorr_fine(self, a, b, lag_center: int = 0, half_width: int = 16, first_a: int = 0, first_b: int = 0,
+                   n_samples: Optional[int] = None, want_blocks: bool = False) -> FineCorr:
+        """The exact correlation of two ranges at the 2 * half_width + 1 lags around ``lag_center``
+        (gj_xcorr_fine_dev): ``c[k] = correlate(x_b, x_a, 'full')`` at lag ``lags[k]``, positive lags when b is delayed,
+        over ``n_samples`` samples from ``first_a`` of a and ``first_b`` of b (default: as many as both hold).  ``a``
+        and ``b``: host bytes (uploaded once each) or resident ``Capture``s; ``want_blocks``: also the sum of every
+        FINE_BLOCK samples alone.  What a sub-sample delay is estimated from: ``gpsjam.tdoa.fine_lag``."""
+        lag_center, half_width, first_a, first_b = int(lag_center), int(half_width), int(first_a), int(first_b)
+        with contextlib.ExitStack() as temps:
+            cap_a = temps.enter_context(self._resident(a))
+            cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
+            if n_samples is None:
+                n_samples = max(0, min(cap_a.nsamples - first_a, cap_b.nsamples - first_b))
+            n_samples, n_lags = int(n_samples), 2 * max(half_width, 0) + 1
+            blocks = fine_blocks(n_samples) if want_blocks else 0
+            d_total = temps.enter_context(DevBuf(self, 16 * n_lags))
+            d_blocks = temps.enter_context(DevBuf(self, 8 * n_lags * max(blocks, 1))) if want_blocks else None
+            self._count("xcorr_fine")
+            self.xcorr_fine_dev(cap_a, cap_a.nbytes, first_a, cap_b, cap_b.nbytes, first_b, n_samples, lag_center,
+                                half_width, d_total, d_blocks)
+            total = d_total.download(np.int64, 2 * n_lags).reshape(n_lags, 2)
+            rec = d_blocks.download(np.int32, 2 * n_lags * blocks).reshape(blocks, n_lags, 2) if want_blocks else None
+        lags = lag_center - half_width + np.arange(n_lags, dtype=np.int64)
+        c = (total[:, 0] + 1j * total[:, 1]) / 4.0
+        return FineCorr(lags, c, None if rec is None else (rec[..., 0] + 1j * rec[..., 1]) / 4.0, n_samples)
+
     # ------------------------------------------------------------------ device pointers
+    def xcorr_fine_dev(self, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, lag_center, half_width, d_total,
+                       d_blocks=None):
+        """gj_xcorr_fine_dev: int64 (re, im) of the 2 * half_width + 1 lags into d_total and, if asked for, the int32
+        (re, im) of every FINE_BLOCK samples into d_blocks, on the context's stream."""
+        self._check(self._lib.gj_xcorr_fine_dev(self._ctx, _ptr(d_a), int(nbytes_a), int(first_a), _ptr(d_b), int(nbytes_b),
+                                                int(first_b), int(n_samples), int(lag_center), int(half_width),
+                                                _ptr(d_total), _ptr(d_blocks) or None))
+
     def blank_dev(self, d_iq, nbytes, first_sample, n_samples, window, guard, threshold, d_out, d_blocks=None):
         """gj_blank_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 24-byte record (BLANK_DTYPE) per
         BLANK_BLOCK samples into d_blocks, on the context's stream."""

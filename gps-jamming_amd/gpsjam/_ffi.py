@@ -161,6 +161,8 @@ GJ_VERSION = 150
 GJ_CAF_MAX_BINS = 4096
 GJ_CHIRP_MAX_RATES = 256
 GJ_BLANK_BLOCK = 4096
+GJ_FINE_BLOCK = 4096
+GJ_FINE_MAX_HALF = 32
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
 _pf, _psz = C.POINTER(C.c_float), C.POINTER(C.c_size_t)
@@ -271,6 +273,8 @@ SIGNATURES = {
     "gj_xcorr_caf_u8": (_i, [_vp, C.POINTER(_vp), _i, _sz, C.POINTER(C.c_int32), _i, _i, _i, C.POINTER(CafResult),
                              C.POINTER(C.c_int32), _pf, _pf]),
     "gj_xcorr_caf_workspace": (_sz, [_vp, _i, _sz, _i, _i, _i]),
+    "gj_fine_blocks": (_sz, [_sz]),
+    "gj_xcorr_fine_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, C.c_int32, _i, _vp, _vp]),
     "gj_pack_result_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gj_synth_u8_dev": (_i, [_vp, C.POINTER(SynthParams), C.c_int64, _sz, _vp]),
 }

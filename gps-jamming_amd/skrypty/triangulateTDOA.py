@@ -188,6 +188,18 @@ def correlation_lag(signal1_slice, signal0_slice):
     return k - (len(signal0_slice) - 1), float(np.abs(corr[k]))
 
 
+def correlation_lag_fine(signal1_slice, signal0_slice):
+    """correlation_lag with a sub-sample lag: the exact correlation at the 33 lags around correlation_lag's integer
+    answer, and the delay from the slope of its cross-spectrum's phase (gpsjam.tdoa.fine_lag).  Returns
+    (float lag, peak); the lag is the integer one, as a float, where the estimate does not hold (a carrier, an empty
+    slice).  Not in the reference, whose lag is an integer: bearing_from_lag takes either."""
+    from gpsjam import tdoa
+    lag, peak = correlation_lag(signal1_slice, signal0_slice)
+    corr = gpsjam.default_device().xcorr_fine(_raw_of(signal0_slice), _raw_of(signal1_slice), lag_center=lag)
+    fine = tdoa.fine_lag(corr, fs=SAMPLE_RATE)
+    return (fine.lag if fine.ok else float(lag)), peak
+
+
 def correlation_lag_offset(signal1_slice, signal0_slice, max_offset_hz):
     """correlation_lag for receivers that do not share a clock: the lag is searched together with the frequency offset
     of antenna 1 against antenna 0 within +-max_offset_hz, in steps of SAMPLE_RATE / L (L: the correlation's FFT

@@ -678,6 +678,43 @@ int gj_xcorr_caf_u8(gj_ctx* ctx, const uint8_t* const* slices, int n_ant, size_t
 size_t gj_xcorr_caf_workspace(gj_ctx* ctx, int n_ant, size_t n_samples, int n_pairs, int n_bins,
                               int bins_per_launch);
 
+/* ------------------------------------------------- fine TDOA: exact lag-window correlation ---- */
+/* The correlation of two captures' ranges at the 2R + 1 lags around an integer lag (K5's answer), as a direct
+ * time-domain sum over ANY number of samples, up to a whole capture: what a sub-sample delay estimate is made from
+ * (gpsjam/tdoa.py does the float part, 65 complex numbers, on the host).  With R = half_width, n = n_samples,
+ * o2 = 2*offset of gj_set_unpack (an integer) and u = 2*byte - o2 for I and Q:
+ *
+ *   xa[t] = sample first_a + t of capture a,  xb[t] = sample first_b + t of capture b,   t = 0 .. n-1;
+ *           both are ZERO outside 0 .. n-1, even where the capture has bytes there
+ *   for k = lag_center - R .. lag_center + R, in that order in the output:
+ *   C4[k].re = sum_t  uI_b[t+k] uI_a[t] + uQ_b[t+k] uQ_a[t]
+ *   C4[k].im = sum_t  uQ_b[t+k] uI_a[t] - uI_b[t+k] uQ_a[t]          t = 0 .. n-1,  0 <= t+k < n
+ *
+ * C4[k] = 4 * correlate(x_b, x_a, 'full')[k + n - 1] in K5's unpacking x = (I - offset) + j(Q - offset)
+ * (skrypty/triangulateTDOA.py:86), K5's sign convention: the peak sits at a positive k when b is delayed.  Every value
+ * is an exact integer.
+ * d_total: int64[2R+1][2] (re, im).  d_blocks (optional, may be NULL): int32[gj_fine_blocks(n)][2R+1][2]; record m is
+ * the same sum over t in [m*GJ_FINE_BLOCK, (m+1)*GJ_FINE_BLOCK) alone, the last block ragged.  A block sum is at most
+ * 4096 * 2 * 510^2 = 2 130 739 200 < 2^31 in magnitude (offsets 0 and 255), so it fits; d_total is the sum of the block
+ * records in 64 bits.  d_blocks = NULL changes no bit of d_total.
+ * Determinism: integer addition, so the result does not depend on tiling or order; two calls give identical bits, and
+ * the result depends on the bytes of the two ranges alone.
+ * Allowed: d_a == d_b and overlapping ranges (the inputs are only read); odd first_a / first_b; a lag_center with no
+ * overlap (|k| >= n gives zeros); n shorter than R.
+ * GJ_ERR_INVALID: n_samples == 0, a range that runs past its capture, a null or odd d_a or d_b, a null d_total, a
+ * d_total that is not 8-byte aligned, a d_blocks that is not 4-byte aligned, |lag_center| + R overflowing int32.
+ * GJ_ERR_UNSUPPORTED: half_width outside 0 .. GJ_FINE_MAX_HALF.  A refused call enqueues nothing.
+ * Enqueues on the context's stream (a memset of d_total and one launch, whose workgroups add their 64-bit sums to
+ * d_total with atomic adds) and returns.  Needs no workspace: 0 bytes to gj_reserve, the call never allocates. */
+#define GJ_FINE_BLOCK 4096          /* samples of a per block record */
+#define GJ_FINE_MAX_HALF 32         /* half_width R: 0..32, 2R+1 <= 65 lags */
+/* block records over n_samples: ceil(n_samples / GJ_FINE_BLOCK); pure host arithmetic, no context */
+size_t gj_fine_blocks(size_t n_samples);
+int gj_xcorr_fine_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t first_a, const uint8_t* d_b,
+                      size_t nbytes_b, size_t first_b, size_t n_samples, int32_t lag_center, int half_width,
+                      int64_t* d_total /* [2R+1][2]  re, im */,
+                      int32_t* d_blocks /* [gj_fine_blocks(n_samples)][2R+1][2] or NULL */);
+
 /* ------------------------------------------------- per-stream result vector ---------- */
 /* What one rank sends to rank 0 (gpsjam/sharded.py):
  * double[40 + n_chunks + nperseg + 5*pair_capacity] =
