@@ -273,12 +273,19 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
                 dst[s] = (*reinterpret_cast<const uint16_t*>(chunk8 + (byte0 + 2u * TF * s)));
         }
     };
-    // samples s0 .. s0+7 of segment seg_idx (one half segment)
+    // samples s0 .. s0+7 of segment seg_idx (one half segment).
+    // The loads are relaxed atomics of wavefront scope: the same global_load_ushort, no cache-policy bits and no wait
+    // of their own, but -- unlike a plain load from a const __restrict__ pointer, which the compiler may issue anywhere
+    // up to its first use -- they keep their place among the LDS instructions, barriers and fences around them.  The
+    // compiler still counts them in vmcnt and waits where the data is first used.
     auto load_half = [&](unsigned (&dst)[8], unsigned seg_idx, int s0) {
-        const unsigned byte0 = (seg_idx * (unsigned)(N / 2) + (unsigned)jl0) * 2u;
+        // one 32-bit offset for the half; the eight strides (at most 7 * 512 bytes) are added to the POINTER and so
+        // become the loads' immediates: one address register, no adds between the loads
+        const uint8_t* half8 = chunk8 + ((seg_idx * (unsigned)(N / 2) + (unsigned)jl0) * 2u + 2u * TF * (unsigned)s0);
 #pragma unroll
         for (int s = 0; s < 8; ++s)
-            dst[s] = (*reinterpret_cast<const uint16_t*>(chunk8 + (byte0 + 2u * TF * (s0 + s))));
+            dst[s] = __hip_atomic_load(reinterpret_cast<const uint16_t*>(half8 + 2 * TF * s), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WAVEFRONT);
     };
     const unsigned nsteps = (seg_hi - seg_lo + B - 1) / B;
     // this transform group's segments: [my_lo, my_hi) one per step (RUNS), or seg_lo + b, + B, ... (interleaved)
@@ -291,12 +298,15 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
     c2 carry[CARRY ? 8 : 1];           // CARRY: 2u - off2 of the previous step's second half = this step's first half
     [[maybe_unused]] unsigned ws_cur = 0, ws_prv = 2;   // HS: slot of this step's half-sum / of the previous step's
     if constexpr (CARRY) {
-        // first step of the group's run: the first half has no predecessor -- unpack it here, once
-        load_half(rawh, seg_idle, 0);
+        // first step of the group's run: the first half has no predecessor -- unpack it here, once.  Both halves are
+        // asked for before the first is waited for: one exposed round trip per workgroup, not two.
+        unsigned raw0[8];
+        load_half(raw0, seg_idle, 0);
+        load_half(rawh, seg_idle, 8);
         c2 flo = make_c2(0.f, 0.f);
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
-            const c2 f = make_c2((float)(rawh[s] & 255u), (float)((rawh[s] >> 8) & 255u));
+            const c2 f = make_c2((float)(raw0[s] & 255u), (float)((raw0[s] >> 8) & 255u));
             flo = cadd(flo, f);
             carry[s] = twice_plus_k(f, kmoff);
         }
@@ -306,7 +316,6 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
             wsum[ws_prv][b][(tid >> 6) % WPF][0] = li;
             wsum[ws_prv][b][(tid >> 6) % WPF][1] = lq;
         }
-        load_half(rawh, seg_idle, 8);
     } else {
         load_step(raw, RUNS ? seg_idle : ((seg_lo + b < seg_hi) ? seg_lo + b : seg_lo));
     }
@@ -369,10 +378,18 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
             sq = group_sum_dpp_f<TF>(fsum.y);
         }
 
-        // CARRY: the next step's new half, asked for while this step's points sit in LDS (about two thirds of a step
-        // = 2 us ahead of their use, and where the fewest registers are live)
+        // CARRY: the next step's new half, asked for while this step's points sit in LDS: about two thirds of a step
+        // = 2 us ahead of their use, and where the fewest registers are live.  That holds for the generated code only
+        // because load_half's loads are ordered (see there): as plain loads the compiler moved all eight behind the
+        // last butterfly of the step, some 70 vector instructions ahead of the next step's wait, and every wave sat out
+        // most of a memory round trip once per step (profiles/NOTES_k2_prefetch.md; tools/k2_isa_report.py shows
+        // where they stand).  The scheduling barrier keeps the eight together in front of the exchange's barrier or
+        // fence, as in K5 (k_xcorr.hip, xc_passes_tw).
         auto prefetch_half = [&] {
-            if constexpr (CARRY) load_half(rawh, seg_next, 8);
+            if constexpr (CARRY) {
+                load_half(rawh, seg_next, 8);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         };
         if constexpr (XP) welch_passes_x4096(v, lds0, tid, tw, ktw, prefetch_half);
         else welch_passes<N, 0>(v, lds0, lds1, it, b * lds_span(N), jl, tw, ktw, prefetch_half);
