@@ -29,7 +29,8 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "library_path", "as_u8", "default_device", "read_capture", "resident_capture",
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
            "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE",
-           "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks", "FINE_BLOCK", "FINE_MAX_HALF", "fine_blocks", "FineCorr"]
+           "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks", "FINE_BLOCK", "FINE_MAX_HALF", "fine_blocks", "FineCorr",
+           "CrossSpectrum", "csd_rows"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -350,6 +351,56 @@ class SpectralKurtosis:
         if len(self) == 0:
             return np.full(self.nfft, np.nan)
         return _sk_estimate(self.s1.astype(np.float64).sum(axis=0), self.s2.astype(np.float64).sum(axis=0), self.frames_per_row * len(self))
+
+    def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
+        """Signed frequency of every bin in FFT order: bins from nfft/2 on are negative frequencies."""
+        k = np.arange(self.nfft)
+        return np.where(k >= self.nfft // 2, k - self.nfft, k) * (float(fs) / self.nfft)
+
+
+def csd_rows(nbytes_a: int, first_a: int, nbytes_b: int, first_b: int, nfft: int, hop: int, frames_per_row: int) -> int:
+    """Whole rows of frames_per_row frame pairs of nfft points that fit BOTH captures from first_a / first_b at the given
+    hop (gj_csd_rows); 0 when none do."""
+    if min(int(nbytes_a), int(first_a), int(nbytes_b), int(first_b), int(hop)) < 0 \
+            or not -2 ** 31 <= int(nfft) < 2 ** 31 or not -2 ** 31 <= int(frames_per_row) < 2 ** 31:
+        return 0
+    return int(_ffi.load().gj_csd_rows(int(nbytes_a), int(first_a), int(nbytes_b), int(first_b), int(nfft), int(hop),
+                                       int(frames_per_row)))
+
+
+def _msc(saa, sbb, sab) -> np.ndarray:
+    """|Sab|^2 / (Saa Sbb) in float64; NaN where Saa Sbb == 0 (include/gpsjam.h)."""
+    saa, sbb, sab = np.asarray(saa, np.float64), np.asarray(sbb, np.float64), np.asarray(sab, np.complex128)
+    den = saa * sbb
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = (sab.real * sab.real + sab.imag * sab.imag) / den
+    return np.where(den == 0, np.nan, v)
+
+
+class CrossSpectrum:
+    """Cross-spectral density of a capture pair (``Device.cross_spectrum``; gj_csd_dev, include/gpsjam.h): per row of
+    ``frames_per_row`` frame pairs and per bin the auto-spectra ``saa`` and ``sbb`` (float32), the cross-spectrum ``sab``
+    (complex64, sum of B conj(A): its phase falls with frequency when b is delayed) and the magnitude-squared coherence
+    ``msc`` (float32), each [rows, nfft] in FFT order, plus the geometry they were computed with.  Row r starts at
+    samples ``first_a + r * frames_per_row * hop`` of a and ``first_b + ...`` of b."""
+
+    def __init__(self, saa, sbb, sab, msc, nfft: int, hop: int, frames_per_row: int, first_a: int = 0, first_b: int = 0):
+        self.nfft, self.hop, self.frames_per_row = int(nfft), int(hop), int(frames_per_row)
+        self.first_a, self.first_b = int(first_a), int(first_b)
+        self.saa = np.ascontiguousarray(saa, dtype=np.float32).reshape(-1, self.nfft)
+        self.sbb = np.ascontiguousarray(sbb, dtype=np.float32).reshape(-1, self.nfft)
+        self.sab = np.ascontiguousarray(sab, dtype=np.complex64).reshape(-1, self.nfft)
+        self.msc = np.ascontiguousarray(msc, dtype=np.float32).reshape(-1, self.nfft)
+
+    def __len__(self) -> int:
+        return self.saa.shape[0]
+
+    def merged(self) -> np.ndarray:
+        """MSC of all rows together, float64[nfft]: the formula on the summed sums (M = frames_per_row * rows)."""
+        if len(self) == 0:
+            return np.full(self.nfft, np.nan)
+        return _msc(self.saa.astype(np.float64).sum(axis=0), self.sbb.astype(np.float64).sum(axis=0),
+                    self.sab.astype(np.complex128).sum(axis=0))
 
     def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
         """Signed frequency of every bin in FFT order: bins from nfft/2 on are negative frequencies."""
@@ -1011,6 +1062,36 @@ class Device:
                 got = out.download(np.float32, 3 * cells).reshape(3, cells)[:, :n_rows * nfft]
         return SpectralKurtosis(got[0], got[1], got[2], nfft, hop, frames_per_row, first_sample)
 
+    def cross_spectrum(self, a, b, nfft: int = 256, hop: Optional[int] = None, frames_per_row: int = 1024,
+                       first_a: int = 0, first_b: int = 0, n_rows: Optional[int] = None) -> CrossSpectrum:
+        """Cross-spectral density and coherence of a capture pair (gj_csd_dev): per row of frames_per_row frame pairs of
+        nfft points, hop samples apart (default nfft: independent frames), the per-bin sums of |A|^2, |B|^2 and
+        B conj(A) and the magnitude-squared coherence; n_rows defaults to all that fit both.  ``a`` and ``b``: host bytes
+        (uploaded once each) or resident ``Capture``s.  ``last_kernel_ms`` is the time of the two launches."""
+        nfft, frames_per_row, first_a, first_b = int(nfft), int(frames_per_row), int(first_a), int(first_b)
+        hop = nfft if hop is None else int(hop)
+        with contextlib.ExitStack() as temps:
+            cap_a = temps.enter_context(self._resident(a))
+            cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
+            if n_rows is None:
+                n_rows = csd_rows(cap_a.nbytes, first_a, cap_b.nbytes, first_b, nfft, hop, frames_per_row)
+                if n_rows == 0 and 16 <= nfft <= 4096 and hop >= 1 and 2 <= frames_per_row <= 65536:
+                    empty = np.empty((0, nfft), np.float32)
+                    return CrossSpectrum(empty, empty, empty.astype(np.complex64), empty, nfft, hop, frames_per_row, first_a, first_b)
+            n_rows = int(n_rows)
+            self._count("cross_spectrum")
+            cells = max(n_rows, 1) * max(nfft, 1)
+            out = temps.enter_context(DevBuf(self, 5 * 4 * cells))       # sab (8-byte aligned) in front, then saa, sbb, msc
+            self.timer_start()
+            self.cross_spectrum_dev(cap_a, cap_a.nbytes, first_a, cap_b, cap_b.nbytes, first_b, nfft, hop, frames_per_row,
+                                    n_rows, out.ptr + 8 * cells, out.ptr + 12 * cells, out.ptr, out.ptr + 16 * cells)
+            self.last_kernel_ms = self.timer_stop()
+            got = out.download(np.float32, 5 * cells)
+        n = n_rows * nfft
+        sab = got[:2 * cells][:2 * n].view(np.complex64)
+        saa, sbb, msc = (got[k * cells:k * cells + n] for k in (2, 3, 4))
+        return CrossSpectrum(saa, sbb, sab, msc, nfft, hop, frames_per_row, first_a, first_b)
+
     def excise(self, raw, threshold, nfft: int = 1024, first_sample: int = 0, n_samples: Optional[int] = None):
         """Frequency-domain excision (gj_excise_dev): samples first_sample .. + n_samples of ``raw`` (default: to the
         end) with every bin of every nfft-point frame whose power exceeds ``threshold[k]`` taken out.  ``raw``: host
@@ -1129,6 +1210,17 @@ class Device:
 
     def sk_workspace(self, nfft: int, frames_per_row: int, n_rows: int) -> int:
         return self._lib.gj_sk_workspace(self._ctx, int(nfft), int(frames_per_row), int(n_rows))
+
+    def cross_spectrum_dev(self, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, nfft, hop, frames_per_row, n_rows, d_saa,
+                           d_sbb, d_sab, d_msc=None):
+        """gj_csd_dev: float32[n_rows][nfft] sums of |A|^2 into d_saa and of |B|^2 into d_sbb, float32[n_rows][nfft][2]
+        (re, im) sums of B conj(A) into d_sab and, if asked for, the coherence into d_msc, on the context's stream."""
+        self._check(self._lib.gj_csd_dev(self._ctx, _ptr(d_a), int(nbytes_a), int(first_a), _ptr(d_b), int(nbytes_b),
+                                         int(first_b), int(nfft), int(hop), int(frames_per_row), int(n_rows), _ptr(d_saa),
+                                         _ptr(d_sbb), _ptr(d_sab), _ptr(d_msc) or None))
+
+    def csd_workspace(self, nfft: int, frames_per_row: int, n_rows: int) -> int:
+        return self._lib.gj_csd_workspace(self._ctx, int(nfft), int(frames_per_row), int(n_rows))
 
     def ridge_dev(self, d_iq, nbytes, first_sample, nfft, hop, n_frames, guard, d_out):
         """gj_ridge_dev: n_frames records of 16 bytes (RIDGE_DTYPE) into d_out, on the context's stream."""

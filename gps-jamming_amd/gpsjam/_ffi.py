@@ -216,6 +216,9 @@ SIGNATURES = {
     "gj_sk_rows": (_sz, [_sz, _sz, _i, _sz, _i]),
     "gj_sk_workspace": (_sz, [_vp, _i, _i, _sz]),
     "gj_sk_dev": (_i, [_vp, _vp, _sz, _sz, _i, _sz, _i, _sz, _vp, _vp, _vp]),
+    "gj_csd_rows": (_sz, [_sz, _sz, _sz, _sz, _i, _sz, _i]),
+    "gj_csd_workspace": (_sz, [_vp, _i, _i, _sz]),
+    "gj_csd_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _sz, _i, _sz, _vp, _vp, _vp, _vp]),
     "gj_excise_frames": (_sz, [_sz, _i]),
     "gj_excise_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp]),
     "gj_excise_chirp_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,186 @@
+"""Which bins do two antennas share, and with what delay in each band: decisions on the cross-spectral density of a
+capture pair (``Device.cross_spectrum``, gj_csd_dev).
+
+Two receivers see the same jammer under independent noise.  Per bin the magnitude-squared coherence
+
+    MSC = |Sab|^2 / (Saa Sbb),   Saa, Sbb, Sab summed over M frame pairs
+
+is about 1 / M under noise alone and (rho / (1 + rho))^2 in a bin of jammer-to-noise ratio rho.  For Gaussian noise and
+independent frames P(MSC > g) = (1 - g)^(M - 1) exactly (Carter), so the threshold for a per-bin false-alarm
+probability needs no noise floor and no calibration -- floor-free as the spectral kurtosis is (``gpsjam.kurtosis``), and
+sighted exactly where that one is blind: a Gaussian broadband jammer has SK = 1 but is coherent between the antennas,
+also when it lies below each receiver's own noise.  Inside a coherent band the slope of Sab's phase is that band's own
+delay, so two jammers at once give two delays where a full-band correlation (K5, ``gj_xcorr_fine_dev``) gives the
+stronger one's.
+
+Limits:
+  * the receivers share a clock.  A frequency offset between them rotates Sab from frame to frame and averages it
+    away; feeding a cross-ambiguity bin in is a later change;
+  * the residual misalignment of the pair must be small against nfft (``scan`` takes an integer ``lag`` to align by);
+  * both dongles have a DC spur, and two constants are perfectly coherent: bins within ``dc_guard`` of bin 0 are never
+    flagged.
+
+    python -m gpsjam.coherence A.bin B.bin [--nfft N] [--frames-per-row M] [--p-fa P] [--lag L|k5]
+
+prints the coherent bands and their delays.
+
+Nothing here computes on the CPU but the decisions on the rows x nfft numbers.
+"""
+from __future__ import annotations
+
+import contextlib
+from typing import List, NamedTuple, Optional
+
+import numpy as np
+
+from . import CrossSpectrum
+
+K5_SAMPLES = 65536          # the slice ``scan(lag="k5")`` hands to K5
+
+
+class Detection(NamedTuple):
+    """Per-bin flags in FFT order and the threshold they were decided with."""
+    flagged: np.ndarray         # bool[nfft]: more than half of the rows exceed the threshold
+    threshold: float
+    p_fa: float
+
+
+class Band(NamedTuple):
+    """A contiguous run of flagged bins.  first_bin .. last_bin are FFT-order indices of the run's ends in ascending
+    frequency; the frequencies are the outer edges of those bins.  ``delay``: samples by which b lags a in this band
+    (``band_delay``), None where it was not estimated."""
+    first_bin: int
+    last_bin: int
+    n_bins: int
+    freq_lo_hz: float
+    freq_hi_hz: float
+    median_msc: float
+    delay: Optional[float] = None
+
+
+class Scan(NamedTuple):
+    result: CrossSpectrum
+    detection: Detection
+    bands: List[Band]
+    lag: int                    # the integer lag the pair was aligned by
+
+
+def threshold(frames_per_row: int, p_fa: float = 1e-6) -> float:
+    """The MSC that noise exceeds with probability p_fa in one cell: 1 - p_fa^(1 / (M - 1)).  Exact for Gaussian noise
+    and INDEPENDENT frames, that is hop >= nfft; overlapping frames are correlated and exceed it more often."""
+    m = int(frames_per_row)
+    if m < 2:
+        raise ValueError("frames_per_row must be >= 2")
+    if not 0.0 < float(p_fa) < 1.0:
+        raise ValueError("p_fa must lie in (0, 1)")
+    return 1.0 - float(p_fa) ** (1.0 / (m - 1))
+
+
+def _signed(nfft: int) -> np.ndarray:
+    k = np.arange(nfft)
+    return np.where(k >= nfft // 2, k - nfft, k)
+
+
+def detect(result: CrossSpectrum, p_fa: float = 1e-6, dc_guard: int = 1) -> Detection:
+    """A bin is flagged when more than half of the rows exceed ``threshold(M, p_fa)``.  A NaN cell (a bin without
+    power) never votes.  Bins within ``dc_guard`` of bin 0 are never flagged (negative: none is exempt)."""
+    thr = threshold(result.frames_per_row, p_fa)
+    msc = result.msc.astype(np.float64)
+    rows = msc.shape[0]
+    with np.errstate(invalid="ignore"):
+        above = np.sum(msc > thr, axis=0)
+    flagged = 2 * above > rows
+    flagged &= np.abs(_signed(result.nfft)) > int(dc_guard)
+    return Detection(flagged, thr, float(p_fa))
+
+
+def bands(result: CrossSpectrum, detection: Detection, fs: float = 2.048e6) -> List[Band]:
+    """Contiguous flagged runs in ascending frequency (fftshift order), with the median MSC of their cells."""
+    n = result.nfft
+    order = np.fft.fftshift(np.arange(n))                      # FFT-order bin at every shifted position
+    hit = np.asarray(detection.flagged, bool)[order]
+    width = float(fs) / n
+    out, at = [], 0
+    while at < n:
+        if not hit[at]:
+            at += 1
+            continue
+        end = at
+        while end + 1 < n and hit[end + 1]:
+            end += 1
+        cells = result.msc[:, order[at:end + 1]].astype(np.float64)
+        med = float(np.nanmedian(cells)) if np.isfinite(cells).any() else float("nan")
+        out.append(Band(int(order[at]), int(order[end]), end - at + 1, (at - n // 2 - 0.5) * width, (end - n // 2 + 0.5) * width, med))
+        at = end + 1
+    return out
+
+
+def band_delay(result: CrossSpectrum, band: Band, coarse_lag: int = 0) -> Optional[float]:
+    """Samples by which b lags a inside ``band``, plus ``coarse_lag``: the |Sab|-weighted least-squares slope of the
+    unwrapped phase of the row-summed Sab over the band's bins, D = -(nfft / 2 pi) d(arg Sab) / dk.  None for a band
+    of fewer than 3 bins (a line through two points has no residual to average)."""
+    if band.n_bins < 3:
+        return None
+    n = result.nfft
+    order = np.fft.fftshift(np.arange(n))
+    at = int(np.flatnonzero(order == band.first_bin)[0])
+    bins = order[at:at + band.n_bins]
+    s = result.sab[:, bins].astype(np.complex128).sum(axis=0)
+    w = np.abs(s)
+    if not np.all(np.isfinite(w)) or w.sum() == 0:
+        return None
+    k = _signed(n)[bins].astype(np.float64)
+    phase = np.unwrap(np.angle(s))
+    km, pm = np.sum(w * k) / w.sum(), np.sum(w * phase) / w.sum()
+    slope = np.sum(w * (k - km) * (phase - pm)) / np.sum(w * (k - km) ** 2)
+    return float(-slope * n / (2.0 * np.pi) + coarse_lag)
+
+
+def _k5_lag(dev, cap_a, cap_b) -> int:
+    n = min(K5_SAMPLES, cap_a.nsamples, cap_b.nsamples)
+    lags, _ = dev.xcorr_lags_at([cap_a, cap_b], [0, 0], n, [(0, 1)])
+    return int(lags[0])
+
+
+def scan(dev, a, b, lag=0, fs: float = 2.048e6, nfft: int = 256, frames_per_row: int = 1024, p_fa: float = 1e-6,
+         dc_guard: int = 1, hop: Optional[int] = None) -> Scan:
+    """``dev.cross_spectrum`` over the whole pair, ``detect``, ``bands``, and each band's delay.  The pair is aligned
+    by the integer ``lag`` first (samples by which b lags a): a positive lag advances first_b, a negative one first_a.
+    ``lag="k5"`` takes K5's integer lag of the first K5_SAMPLES samples."""
+    with dev._resident(a) as cap_a, (dev._resident(b) if b is not a else contextlib.nullcontext(cap_a)) as cap_b:
+        lag = _k5_lag(dev, cap_a, cap_b) if lag == "k5" else int(lag)
+        result = dev.cross_spectrum(cap_a, cap_b, nfft=nfft, hop=hop, frames_per_row=frames_per_row,
+                                    first_a=max(-lag, 0), first_b=max(lag, 0))
+    detection = detect(result, p_fa, dc_guard)
+    found = [bd._replace(delay=band_delay(result, bd, lag)) for bd in bands(result, detection, fs)]
+    return Scan(result, detection, found, lag)
+
+
+def main(argv=None) -> int:
+    import argparse
+    from . import Device
+    ap = argparse.ArgumentParser(prog="python -m gpsjam.coherence", description="print the bands two captures share and their delays")
+    ap.add_argument("a")
+    ap.add_argument("b")
+    ap.add_argument("--nfft", type=int, default=256)
+    ap.add_argument("--frames-per-row", type=int, default=1024)
+    ap.add_argument("--p-fa", type=float, default=1e-6)
+    ap.add_argument("--lag", default="0", help="integer samples by which b lags a, or k5")
+    ap.add_argument("--fs", type=float, default=2.048e6)
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    lag = "k5" if args.lag == "k5" else int(args.lag)
+    with Device(args.device) as dev:
+        with dev.capture(args.a) as cap_a, dev.capture(args.b) as cap_b:
+            res = scan(dev, cap_a, cap_b, lag=lag, fs=args.fs, nfft=args.nfft, frames_per_row=args.frames_per_row, p_fa=args.p_fa)
+    print(f"{args.a} / {args.b}: {len(res.result)} rows of {args.frames_per_row} frame pairs of {args.nfft} points, aligned by {res.lag}, "
+          f"threshold {res.detection.threshold:.5f} (p_fa {args.p_fa:g}), {len(res.bands)} coherent band(s)")
+    for bd in res.bands:
+        delay = "       -" if bd.delay is None else f"{bd.delay:+8.3f}"
+        print(f"  {bd.freq_lo_hz / 1e3:9.1f} .. {bd.freq_hi_hz / 1e3:9.1f} kHz  bins {bd.first_bin}..{bd.last_bin} ({bd.n_bins})  "
+              f"median MSC {bd.median_msc:.3f}  delay {delay} samples")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

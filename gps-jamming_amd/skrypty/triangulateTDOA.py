@@ -222,6 +222,22 @@ def correlation_lag_offset(signal1_slice, signal0_slice, max_offset_hz):
     return k - (n - 1), float(np.abs(corr[k])), res.offset_hz
 
 
+def correlation_lag_bands(file_b, file_a, lag="k5", nfft=256, frames_per_row=1024, p_fa=1e-6):
+    """One lag per coherent band instead of one per pair: ``[(freq_lo_hz, freq_hi_hz, lag)]`` in ascending frequency, the
+    lag in samples (a float), positive when antenna b receives that band later.  Two jammers at once give two rows
+    where correlation_lag names the stronger one's lag.  ``file_b``, ``file_a``: capture files or load_iq_data handles;
+    the pair is aligned by ``lag`` first ("k5": correlation_lag's integer answer on the captures' heads).  Not in the
+    reference.  The receivers must share a clock (gpsjam.coherence states the limits); bands of fewer than 3 bins carry
+    no lag and are left out."""
+    from gpsjam import coherence
+
+    def source(x):
+        return x.raw if isinstance(x, IQCapture) else gpsjam.read_capture(x)
+    res = coherence.scan(gpsjam.default_device(), source(file_a), source(file_b), lag=lag, fs=SAMPLE_RATE, nfft=nfft,
+                         frames_per_row=frames_per_row, p_fa=p_fa)
+    return [(b.freq_lo_hz, b.freq_hi_hz, b.delay) for b in res.bands if b.delay is not None]
+
+
 def bearing_from_lag(lag_samples, ant0_pos=ANT0_POS, ant1_pos=ANT1_POS, sample_rate=SAMPLE_RATE):
     """Scalar geometry of reference :92-119 (including its baseline-angle expression, :114).
     Returns a dict, or a dict with 'error' when the geometry is impossible."""

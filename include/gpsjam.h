@@ -321,6 +321,48 @@ int gj_sk_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_samp
               int frames_per_row, size_t n_rows, float* d_s1 /* [n_rows*nfft] */, float* d_s2 /* [n_rows*nfft] */,
               float* d_sk /* [n_rows*nfft] or NULL */);
 
+/* ------------------------------------------------- cross-spectral density ----------- */
+/* The frequency-resolved question about a PAIR of captures (gpsjam/coherence.py reads it): which bins carry the same
+ * source in both, and with what delay in each band.  Two antennas see the same jammer under independent receiver noise:
+ * the magnitude-squared coherence is about 1/M under noise alone and (rho / (1 + rho))^2 in a bin of jammer-to-noise
+ * ratio rho, also where the jammer lies below each receiver's noise floor and is Gaussian (the kurtosis's blind spot).
+ * For Gaussian noise and independent frames P(MSC > g) = (1 - g)^(M-1) exactly (Carter): the detector needs no floor.
+ * With N = nfft, M = frames_per_row, row r = 0 .. n_rows-1 holds the frames f = r*M + m, m = 0 .. M-1, at s_f = f*hop:
+ *
+ *   x_a[t]    = (I - offset) + j(Q - offset) of capture a at sample first_a + t     gj_set_unpack's offset; likewise x_b
+ *   w[n]      = 0.5 - 0.5 cos(2 pi n / N)                          periodic Hann, K2's table; no mean removal
+ *   A_f[k]    = sum_{n<N} w[n] x_a[s_f + n] exp(-2 pi i k n / N)   B_f[k] likewise from capture b at first_b
+ *   Saa[r][k] = scale^2 sum_m |A_f[k]|^2     Sbb[r][k] = scale^2 sum_m |B_f[k]|^2      the units of gj_sk_dev's S1
+ *   Sab[r][k] = scale^2 sum_m B_f[k] conj(A_f[k])
+ *   MSC[r][k] = (re^2 + im^2) / (Saa Sbb)                          NaN where Saa Sbb == 0; not clamped
+ *
+ * Sign: if b is a delayed by D samples, arg Sab[k] = -2 pi k D / N with k signed, so D = -(N / 2 pi) d(arg)/dk, positive
+ * when b is delayed: the convention of gj_xcorr_lags and gj_xcorr_fine_dev.
+ * d_saa, d_sbb: float32[n_rows][nfft] in FFT order; d_sab: float32[n_rows][nfft][2], (re, im); d_msc: float32[n_rows][nfft]
+ * or NULL.  MSC is evaluated in double from the float32 values written to the other three and rounded once; rounding may
+ * carry it past 1.  The sums run in LSB units, scale^2 is applied once at the end.
+ * nfft: a power of two, 16..4096 (GJ_ERR_UNSUPPORTED otherwise).  hop >= 1, otherwise arbitrary (hop >= nfft gives
+ * independent frames); first_a and first_b may be odd and may differ; d_a == d_b and overlapping ranges are allowed.
+ * 2 <= frames_per_row <= 65536 (below 2: GJ_ERR_INVALID, MSC is identically 1 at M = 1; above: GJ_ERR_UNSUPPORTED).
+ * n_rows == 0 or more rows than gj_csd_rows, a null or odd d_a or d_b, a null d_saa, d_sbb or d_sab, a d_saa, d_sbb or
+ * d_msc that is not 4-byte aligned, a d_sab that is not 8-byte aligned: GJ_ERR_INVALID.  A refused call enqueues
+ * nothing.  Enqueues on the context's stream (two launches) and returns; allocates nothing when gj_csd_workspace bytes
+ * were reserved.
+ * Determinism: a row is cut into blocks by gj_sk_dev's rule -- ceil(M / 16) blocks of ceil(M / blocks) frames, the last
+ * one shorter; one transform group sums a block frame by frame in float32, and the blocks of a row are added in order.
+ * So row r of a call is bit-identical to row r-k of the call started k*M*hop samples later in both captures and to row r
+ * of a call with fewer rows, two identical calls give identical bytes, d_msc == NULL changes no other bit, and Saa
+ * depends on capture a's bytes alone (the same call against another b writes the same Saa), likewise Sbb on b's. */
+/* whole rows that fit both captures: pure host arithmetic, no context; 0 for an impossible geometry */
+size_t gj_csd_rows(size_t nbytes_a, size_t first_a, size_t nbytes_b, size_t first_b, int nfft, size_t hop,
+                   int frames_per_row);
+/* workspace bytes gj_csd_dev needs for the partial sums (for gj_reserve); 0 for parameters gj_csd_dev refuses and when
+ * the product does not fit a size_t */
+size_t gj_csd_workspace(gj_ctx* ctx, int nfft, int frames_per_row, size_t n_rows);
+int gj_csd_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t first_a, const uint8_t* d_b, size_t nbytes_b,
+               size_t first_b, int nfft, size_t hop, int frames_per_row, size_t n_rows, float* d_saa /* [n_rows*nfft] */,
+               float* d_sbb /* [n_rows*nfft] */, float* d_sab /* [n_rows*nfft*2] */, float* d_msc /* [n_rows*nfft] or NULL */);
+
 /* ------------------------------------------------- frequency-domain excision -------- */
 /* The windowed 50 %-overlap FFT excisor of GPS receivers: a cleaned capture, uint8 I/Q again, with every bin above its
  * threshold taken out (the interferers of simulate/frontend/jammers/; gpsjam/mitigate.py builds the thresholds).  For a
