@@ -76,9 +76,7 @@ hipStream_t current_stream(gj_ctx* ctx) {
     return ctx->stream;
 }
 
-static float* g_window_dummy = nullptr;
 const float* window_table(gj_ctx* ctx, int n) {
-    (void)g_window_dummy;
     return reinterpret_cast<const float*>(ctx->d_twiddle + kTwiddleTable) + (n - 16);
 }
 

@@ -7,36 +7,22 @@
 // (gpsjam/coherence.py reads both).
 //
 // This is sk_kernel (k_skurt.hip) with two captures and four accumulators per bin, on the front end of stft_group.h:
-//   * a transform group takes one BLOCK of a row, a run of up to kCsdMaxRun consecutive frame PAIRS.  Per pair it
+//   * a transform group takes one BLOCK of a row, a run of up to kRowMaxRun consecutive frame PAIRS.  Per pair it
 //     transforms a's frame and keeps its 16 bins in registers, transforms b's frame through the same LDS buffer (the
 //     front end's exchange ends with a barrier behind the gather, so the buffer is free again), and accumulates.  A bin
 //     belongs to the same thread in both transforms: nothing is reduced across lanes;
 //   * the sums run in LSB units (scale^2 is applied at the end);
 //   * a block ends with one partial, float32[4][N] (Saa, Sbb, re, im), in the workspace; a second small launch adds a
 //     row's partials in block order, scales, and evaluates MSC in double from the rounded float32 values.
-// The partition is gj_sk_dev's: a function of M alone (csd_blocks below).  Determinism as there: a block's partial is
-// computed by ONE group from that block's bytes alone, pair by pair in order; Saa's accumulator sees a's bins only and
-// Sbb's b's only, so each depends on its own capture's bytes alone.
+// Rows, blocks, the partition rule and the determinism that rests on it are stft_rows.h, shared with k_skurt.hip.  Here
+// Saa's accumulator sees a's bins only and Sbb's b's only, so each depends on its own capture's bytes alone.
 //
 // A translation unit of its own with its own extern "C" entry points; no other source refers to it.
-#include "stft_group.h"
+#include "stft_rows.h"
 
 #include <cmath>
 
 namespace gj {
-
-constexpr int kCsdMaxRun = 16;       // frame pairs per block at most (k_skurt.hip kSkMaxRun: the same rule)
-constexpr int kCsdMaxFrames = 65536; // frames per row at most
-
-// blocks of a row and frame pairs per block (the last block may be shorter, never empty)
-struct CsdBlocks {
-    unsigned nb, run;
-};
-inline CsdBlocks csd_blocks(int frames_per_row) {
-    const unsigned M = (unsigned)frames_per_row;
-    const unsigned nb = (M + kCsdMaxRun - 1) / kCsdMaxRun;
-    return CsdBlocks{nb, (M + nb - 1) / nb};
-}
 
 // Im(B conj(A)) as the difference of two ROUNDED products, never contracted into a fused multiply-add: the form is
 // antisymmetric in (a, b), so swapping the captures conjugates Sab bit for bit and a capture against itself has no
@@ -60,9 +46,8 @@ struct CsdCfg {
 };
 
 struct CsdGeom {
-    unsigned long long first_a, first_b, hop, n_units, nsteps, last_frame;
-    unsigned frames_per_row, nb, run;
-    float neg_off;   // -offset of the unpack convention
+    unsigned long long first_a, first_b;
+    RowGeom rows;
 };
 
 template <int N>
@@ -88,25 +73,10 @@ __global__ __launch_bounds__(kBlockThreads, CsdCfg<N>::min_waves) void csd_kerne
     c2 wp[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) wp[s] = stft_window_pair<N>(wintab, jl0, s);
-    const c2 koff = make_c2(g.neg_off, g.neg_off);
+    const c2 koff = make_c2(g.rows.neg_off, g.rows.neg_off);
 
-    // This group's block in workgroup step `step`, as sk_kernel's: its first frame and how many pairs it holds.  A group
-    // behind the last block holds none; it walks the call's last block again so that every load stays inside both
-    // captures, and every group of the grid makes g.run iterations per step (the barriers of the large sizes are
-    // workgroup-wide).
-    auto block_of = [&](unsigned long long step, unsigned& count) {
-        unsigned long long u = step * B + (unsigned)b;
-        const bool valid = u < g.n_units;
-        if (!valid) u = g.n_units - 1;
-        const unsigned long long r = u / g.nb;
-        const unsigned j = (unsigned)(u - r * g.nb);
-        const unsigned rest = g.frames_per_row - j * g.run;
-        count = valid ? (rest < g.run ? rest : g.run) : 0u;
-        return r * g.frames_per_row + (unsigned long long)j * g.run;
-    };
-    auto frame_at = [&](unsigned long long f) {   // a short block's spare iterations read the call's last frame
-        return (f > g.last_frame ? g.last_frame : f) * g.hop;
-    };
+    auto block_of = [&](unsigned long long step, unsigned& count) { return row_block_of<B>(g.rows, step, b, count); };
+    auto frame_at = [&](unsigned long long f) { return row_clamp_frame(g.rows, f) * g.rows.hop; };
     auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, Cfg::wide_load>(dst, base, jl0); };
     auto transform = [&](c2 (&v)[16]) {
         if constexpr (XP) stft_passes_x4096(v, lds0, tid, tw, ktw);
@@ -121,16 +91,16 @@ __global__ __launch_bounds__(kBlockThreads, CsdCfg<N>::min_waves) void csd_kerne
     unsigned long long f0 = block_of(step, count);
     load_frame(raw_a, base_a + 2ull * frame_at(f0));
     load_frame(raw_b, base_b + 2ull * frame_at(f0));
-    for (; step < g.nsteps; step += gridDim.x) {
-        const bool more = step + gridDim.x < g.nsteps;   // workgroup-uniform
+    for (; step < g.rows.nsteps; step += gridDim.x) {
+        const bool more = step + gridDim.x < g.rows.nsteps;   // workgroup-uniform
         unsigned next_count = 0;
         const unsigned long long next_f0 = more ? block_of(step + gridDim.x, next_count) : 0ull;
         float saa[16], sbb[16], sre[16], sim[16];
 #pragma unroll
         for (int s = 0; s < 16; ++s) saa[s] = sbb[s] = sre[s] = sim[s] = 0.f;
 
-        for (unsigned i = 0; i < g.run; ++i) {
-            const bool within = i + 1 < g.run;
+        for (unsigned i = 0; i < g.rows.run; ++i) {
+            const bool within = i + 1 < g.rows.run;
             const unsigned long long next_at = frame_at(within ? f0 + i + 1 : next_f0);
 
             c2 a[16];
@@ -203,30 +173,6 @@ __global__ __launch_bounds__(256) void csd_finalize_kernel(const float* __restri
     }
 }
 
-// bytes of partial sums for n_rows rows; 0 when the product does not fit a size_t
-static size_t csd_workspace_bytes(int nfft, int frames_per_row, size_t n_rows) {
-    size_t units = 0, bytes = 0;
-    if (__builtin_mul_overflow(n_rows, (size_t)csd_blocks(frames_per_row).nb, &units)) return 0;
-    if (__builtin_mul_overflow(units, (size_t)nfft * 4 * sizeof(float), &bytes)) return 0;
-    return bytes;
-}
-
-// whole rows of one capture (gj_sk_rows' arithmetic)
-static size_t csd_rows_of(size_t nbytes, size_t first, int nfft, size_t hop, int frames_per_row) {
-    const size_t total = nbytes / 2;
-    if (nfft < 1 || hop < 1 || frames_per_row < 1 || first > total || total - first < (size_t)nfft) return 0;
-    return ((total - first - (size_t)nfft) / hop + 1) / (size_t)frames_per_row;
-}
-
-template <int N>
-static void csd_launch(gj_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, CsdGeom g, float* partial) {
-    constexpr unsigned long long B = kBlockPoints / N;
-    g.nsteps = (g.n_units + B - 1) / B;
-    const unsigned grid = stft_one_round_grid(ctx, CsdCfg<N>::min_waves, g.nsteps);
-    hipLaunchKernelGGL(csd_kernel<N>, dim3(grid), dim3(kBlockThreads), 0, ctx->stream, d_a, d_b, g, ctx->d_twiddle, window_table(ctx, N),
-                       partial);
-}
-
 }   // namespace gj
 
 using namespace gj;
@@ -234,24 +180,21 @@ using namespace gj;
 extern "C" {
 
 size_t gj_csd_rows(size_t nbytes_a, size_t first_a, size_t nbytes_b, size_t first_b, int nfft, size_t hop, int frames_per_row) {
-    const size_t ra = csd_rows_of(nbytes_a, first_a, nfft, hop, frames_per_row);
-    const size_t rb = csd_rows_of(nbytes_b, first_b, nfft, hop, frames_per_row);
+    const size_t ra = row_fit(nbytes_a, first_a, nfft, hop, frames_per_row);
+    const size_t rb = row_fit(nbytes_b, first_b, nfft, hop, frames_per_row);
     return ra < rb ? ra : rb;
 }
 
 size_t gj_csd_workspace(gj_ctx* ctx, int nfft, int frames_per_row, size_t n_rows) {
     (void)ctx;
-    if (!stft_nfft_ok(nfft) || frames_per_row < 2 || frames_per_row > kCsdMaxFrames) return 0;
-    return csd_workspace_bytes(nfft, frames_per_row, n_rows);
+    return row_workspace_bytes(4, nfft, frames_per_row, n_rows);
 }
 
 int gj_csd_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t first_a, const uint8_t* d_b, size_t nbytes_b, size_t first_b,
                int nfft, size_t hop, int frames_per_row, size_t n_rows, float* d_saa, float* d_sbb, float* d_sab, float* d_msc) {
     if (!ctx) return GJ_ERR_INVALID;
     Guard lock(ctx);
-    if (int rc = stft_check_nfft(ctx, nfft)) return rc;
-    if (frames_per_row < 2) return fail(ctx, GJ_ERR_INVALID, "frames_per_row must be >= 2");
-    if (frames_per_row > kCsdMaxFrames) return fail(ctx, GJ_ERR_UNSUPPORTED, "frames_per_row must be <= %d", kCsdMaxFrames);
+    if (int rc = row_check_shape(ctx, nfft, frames_per_row)) return rc;
     if (!d_a || !d_b || !d_saa || !d_sbb || !d_sab) return fail(ctx, GJ_ERR_INVALID, "null buffer");
     if (int rc = stft_check_capture(ctx, d_a)) return rc;
     if (int rc = stft_check_capture(ctx, d_b)) return rc;
@@ -263,28 +206,16 @@ int gj_csd_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t first_a,
     if (n_rows == 0 || n_rows > fit)
         return fail(ctx, GJ_ERR_INVALID, "n_rows %zu: 1..%zu rows of %d frames of %d points fit both captures from samples %zu and %zu at hop %zu",
                     n_rows, fit, frames_per_row, nfft, first_a, first_b, hop);
-    const size_t need = csd_workspace_bytes(nfft, frames_per_row, n_rows);
-    if (!need) return fail(ctx, GJ_ERR_NOMEM, "the partial sums of %zu rows do not fit the address space", n_rows);
-    int rc = ensure_workspace(ctx, need);
-    if (rc) return rc;
-    float* partial = reinterpret_cast<float*>(ctx->ws);
-    const CsdBlocks blk = csd_blocks(frames_per_row);
-    CsdGeom g;
-    g.first_a = first_a;
-    g.first_b = first_b;
-    g.hop = hop;
-    g.n_units = (unsigned long long)n_rows * blk.nb;
-    g.nsteps = 0;
-    g.last_frame = (unsigned long long)n_rows * (unsigned)frames_per_row - 1;
-    g.frames_per_row = (unsigned)frames_per_row;
-    g.nb = blk.nb;
-    g.run = blk.run;
-    g.neg_off = -0.5f * (float)ctx->off2;
-    stft_dispatch(nfft, [&](auto n) { csd_launch<decltype(n)::value>(ctx, d_a, d_b, g, partial); });
+    float* partial = nullptr;
+    if (int rc = row_workspace(ctx, 4, nfft, frames_per_row, n_rows, &partial)) return rc;
+    const CsdGeom g{first_a, first_b, row_geom(ctx, hop, frames_per_row, n_rows)};
+    stft_dispatch(nfft, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        row_launch<N>(ctx, csd_kernel<N>, CsdCfg<N>::min_waves, g, partial, d_a, d_b);
+    });
     GJ_LAUNCH_CHECK(ctx);
     const unsigned long long n_out = (unsigned long long)n_rows * (unsigned)nfft;
-    const unsigned long long want = (n_out + 255) / 256, cap = (unsigned long long)ctx->num_cus * 32;
-    hipLaunchKernelGGL(csd_finalize_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, ctx->stream, partial, n_out, nfft, blk.nb,
+    hipLaunchKernelGGL(csd_finalize_kernel, dim3(row_finalize_grid(ctx, n_out)), dim3(256), 0, ctx->stream, partial, n_out, nfft, g.rows.nb,
                        ctx->scale * ctx->scale, d_saa, d_sbb, reinterpret_cast<float2*>(d_sab), d_msc);
     GJ_LAUNCH_CHECK(ctx);
     return GJ_OK;

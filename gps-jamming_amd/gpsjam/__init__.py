@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from . import _ffi
+from . import _bands, _ffi
 from ._ffi import (AmpStats, GpsJamError, GpsJamLibraryError, Onset, SynthParams,  # noqa: F401
                    GJ_LAG_INVALID, GJ_MAX_ANTENNAS)
 
@@ -252,8 +252,7 @@ class Ridge:
 
     def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
         """Signed frequency of peak_bin: bins from nfft/2 on are negative frequencies."""
-        k = self.peak_bin.astype(np.int64)
-        return np.where(k >= self.nfft // 2, k - self.nfft, k) * (float(fs) / self.nfft)
+        return _bands.signed_bins(self.nfft, self.peak_bin.astype(np.int64)) * (float(fs) / self.nfft)
 
 
 CHIRP_DTYPE = np.dtype([("total", np.float32), ("peak", np.float32), ("second", np.float32), ("peak_bin", np.int32),
@@ -315,12 +314,45 @@ class ChirpScan:
         return ((k + self.nfft / 2.0) % self.nfft - self.nfft / 2.0) * (float(fs) / self.nfft)
 
 
+def _row_args_fit(nfft: int, frames_per_row: int, *sizes: int) -> bool:
+    """Whether gj_sk_rows / gj_csd_rows can be asked at all: ``sizes`` go into size_t, the other two into int."""
+    return min(int(v) for v in sizes) >= 0 and all(-2 ** 31 <= int(v) < 2 ** 31 for v in (nfft, frames_per_row))
+
+
 def sk_rows(nbytes: int, first_sample: int, nfft: int, hop: int, frames_per_row: int) -> int:
     """Whole rows of frames_per_row frames of nfft points that fit from first_sample at the given hop (gj_sk_rows);
     0 when none do."""
-    if min(int(nbytes), int(first_sample), int(hop)) < 0 or not -2 ** 31 <= int(nfft) < 2 ** 31 or not -2 ** 31 <= int(frames_per_row) < 2 ** 31:
+    if not _row_args_fit(nfft, frames_per_row, nbytes, first_sample, hop):
         return 0
     return int(_ffi.load().gj_sk_rows(int(nbytes), int(first_sample), int(nfft), int(hop), int(frames_per_row)))
+
+
+def _rows_to_compute(n_rows: Optional[int], fit, ranges, nfft: int, hop: int, frames_per_row: int):
+    """(n_rows, empty): a given row count as it is, None means all that fit (``sk_rows`` / ``csd_rows`` on ``ranges``).
+    ``empty``: the float32[0, nfft] to answer with when none does although the library takes the geometry, else None."""
+    if n_rows is not None:
+        return int(n_rows), None
+    n_rows = fit(*ranges, nfft, hop, frames_per_row)
+    legal = 16 <= nfft <= 4096 and hop >= 1 and 2 <= frames_per_row <= 65536
+    return n_rows, np.empty((0, nfft), np.float32) if n_rows == 0 and legal else None
+
+
+class _RowSums:
+    """What ``SpectralKurtosis`` and ``CrossSpectrum`` share: arrays [rows, nfft] in FFT order and the rows' geometry."""
+
+    def __init__(self, lead, nfft: int, hop: int, frames_per_row: int):
+        self.nfft, self.hop, self.frames_per_row = int(nfft), int(hop), int(frames_per_row)
+        self._lead = self._rows(lead)
+
+    def _rows(self, values, dtype=np.float32) -> np.ndarray:
+        return np.ascontiguousarray(values, dtype=dtype).reshape(-1, self.nfft)
+
+    def __len__(self) -> int:
+        return self._lead.shape[0]
+
+    def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
+        """Signed frequency of every bin in FFT order: bins from nfft/2 on are negative frequencies."""
+        return _bands.signed_bins(self.nfft) * (float(fs) / self.nfft)
 
 
 def _sk_estimate(s1, s2, frames: int) -> np.ndarray:
@@ -331,20 +363,16 @@ def _sk_estimate(s1, s2, frames: int) -> np.ndarray:
     return np.where(s1 == 0, np.nan, sk)
 
 
-class SpectralKurtosis:
+class SpectralKurtosis(_RowSums):
     """Spectral kurtosis of a capture (``Device.spectral_kurtosis``; gj_sk_dev, include/gpsjam.h): per row of
     ``frames_per_row`` frames and per bin the sums ``s1`` of P and ``s2`` of P^2 and the estimator ``sk``, each
     float32[rows, nfft] in FFT order, plus the geometry they were computed with.  Row r starts at sample
     ``first_sample + r * frames_per_row * hop``.  Noise gives sk = 1 with standard deviation 2 / sqrt(frames_per_row)."""
 
     def __init__(self, s1, s2, sk, nfft: int, hop: int, frames_per_row: int, first_sample: int = 0):
-        self.nfft, self.hop, self.frames_per_row, self.first_sample = int(nfft), int(hop), int(frames_per_row), int(first_sample)
-        self.s1 = np.ascontiguousarray(s1, dtype=np.float32).reshape(-1, self.nfft)
-        self.s2 = np.ascontiguousarray(s2, dtype=np.float32).reshape(-1, self.nfft)
-        self.sk = np.ascontiguousarray(sk, dtype=np.float32).reshape(-1, self.nfft)
-
-    def __len__(self) -> int:
-        return self.s1.shape[0]
+        super().__init__(s1, nfft, hop, frames_per_row)
+        self.first_sample = int(first_sample)
+        self.s1, self.s2, self.sk = self._lead, self._rows(s2), self._rows(sk)
 
     def merged(self) -> np.ndarray:
         """SK of all rows together, float64[nfft]: the estimator on the summed sums with M = frames_per_row * rows."""
@@ -352,17 +380,11 @@ class SpectralKurtosis:
             return np.full(self.nfft, np.nan)
         return _sk_estimate(self.s1.astype(np.float64).sum(axis=0), self.s2.astype(np.float64).sum(axis=0), self.frames_per_row * len(self))
 
-    def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
-        """Signed frequency of every bin in FFT order: bins from nfft/2 on are negative frequencies."""
-        k = np.arange(self.nfft)
-        return np.where(k >= self.nfft // 2, k - self.nfft, k) * (float(fs) / self.nfft)
-
 
 def csd_rows(nbytes_a: int, first_a: int, nbytes_b: int, first_b: int, nfft: int, hop: int, frames_per_row: int) -> int:
     """Whole rows of frames_per_row frame pairs of nfft points that fit BOTH captures from first_a / first_b at the given
     hop (gj_csd_rows); 0 when none do."""
-    if min(int(nbytes_a), int(first_a), int(nbytes_b), int(first_b), int(hop)) < 0 \
-            or not -2 ** 31 <= int(nfft) < 2 ** 31 or not -2 ** 31 <= int(frames_per_row) < 2 ** 31:
+    if not _row_args_fit(nfft, frames_per_row, nbytes_a, first_a, nbytes_b, first_b, hop):
         return 0
     return int(_ffi.load().gj_csd_rows(int(nbytes_a), int(first_a), int(nbytes_b), int(first_b), int(nfft), int(hop),
                                        int(frames_per_row)))
@@ -377,7 +399,7 @@ def _msc(saa, sbb, sab) -> np.ndarray:
     return np.where(den == 0, np.nan, v)
 
 
-class CrossSpectrum:
+class CrossSpectrum(_RowSums):
     """Cross-spectral density of a capture pair (``Device.cross_spectrum``; gj_csd_dev, include/gpsjam.h): per row of
     ``frames_per_row`` frame pairs and per bin the auto-spectra ``saa`` and ``sbb`` (float32), the cross-spectrum ``sab``
     (complex64, sum of B conj(A): its phase falls with frequency when b is delayed) and the magnitude-squared coherence
@@ -385,15 +407,9 @@ class CrossSpectrum:
     samples ``first_a + r * frames_per_row * hop`` of a and ``first_b + ...`` of b."""
 
     def __init__(self, saa, sbb, sab, msc, nfft: int, hop: int, frames_per_row: int, first_a: int = 0, first_b: int = 0):
-        self.nfft, self.hop, self.frames_per_row = int(nfft), int(hop), int(frames_per_row)
+        super().__init__(saa, nfft, hop, frames_per_row)
         self.first_a, self.first_b = int(first_a), int(first_b)
-        self.saa = np.ascontiguousarray(saa, dtype=np.float32).reshape(-1, self.nfft)
-        self.sbb = np.ascontiguousarray(sbb, dtype=np.float32).reshape(-1, self.nfft)
-        self.sab = np.ascontiguousarray(sab, dtype=np.complex64).reshape(-1, self.nfft)
-        self.msc = np.ascontiguousarray(msc, dtype=np.float32).reshape(-1, self.nfft)
-
-    def __len__(self) -> int:
-        return self.saa.shape[0]
+        self.saa, self.sbb, self.sab, self.msc = self._lead, self._rows(sbb), self._rows(sab, np.complex64), self._rows(msc)
 
     def merged(self) -> np.ndarray:
         """MSC of all rows together, float64[nfft]: the formula on the summed sums (M = frames_per_row * rows)."""
@@ -401,11 +417,6 @@ class CrossSpectrum:
             return np.full(self.nfft, np.nan)
         return _msc(self.saa.astype(np.float64).sum(axis=0), self.sbb.astype(np.float64).sum(axis=0),
                     self.sab.astype(np.complex128).sum(axis=0))
-
-    def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
-        """Signed frequency of every bin in FFT order: bins from nfft/2 on are negative frequencies."""
-        k = np.arange(self.nfft)
-        return np.where(k >= self.nfft // 2, k - self.nfft, k) * (float(fs) / self.nfft)
 
 
 def as_u8(raw) -> np.ndarray:
@@ -1048,12 +1059,9 @@ class Device:
         nfft, frames_per_row, first_sample = int(nfft), int(frames_per_row), int(first_sample)
         hop = nfft if hop is None else int(hop)
         with self._resident(capture) as cap:
-            if n_rows is None:
-                n_rows = sk_rows(cap.nbytes, first_sample, nfft, hop, frames_per_row)
-                if n_rows == 0 and 16 <= nfft <= 4096 and hop >= 1 and 2 <= frames_per_row <= 65536:
-                    empty = np.empty((0, nfft), np.float32)
-                    return SpectralKurtosis(empty, empty, empty, nfft, hop, frames_per_row, first_sample)
-            n_rows = int(n_rows)
+            n_rows, empty = _rows_to_compute(n_rows, sk_rows, (cap.nbytes, first_sample), nfft, hop, frames_per_row)
+            if empty is not None:
+                return SpectralKurtosis(empty, empty, empty, nfft, hop, frames_per_row, first_sample)
             self._count("spectral_kurtosis")
             cells = max(n_rows, 1) * max(nfft, 1)
             with DevBuf(self, 3 * 4 * cells) as out:
@@ -1073,12 +1081,9 @@ class Device:
         with contextlib.ExitStack() as temps:
             cap_a = temps.enter_context(self._resident(a))
             cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
-            if n_rows is None:
-                n_rows = csd_rows(cap_a.nbytes, first_a, cap_b.nbytes, first_b, nfft, hop, frames_per_row)
-                if n_rows == 0 and 16 <= nfft <= 4096 and hop >= 1 and 2 <= frames_per_row <= 65536:
-                    empty = np.empty((0, nfft), np.float32)
-                    return CrossSpectrum(empty, empty, empty.astype(np.complex64), empty, nfft, hop, frames_per_row, first_a, first_b)
-            n_rows = int(n_rows)
+            n_rows, empty = _rows_to_compute(n_rows, csd_rows, (cap_a.nbytes, first_a, cap_b.nbytes, first_b), nfft, hop, frames_per_row)
+            if empty is not None:
+                return CrossSpectrum(empty, empty, empty, empty, nfft, hop, frames_per_row, first_a, first_b)
             self._count("cross_spectrum")
             cells = max(n_rows, 1) * max(nfft, 1)
             out = temps.enter_context(DevBuf(self, 5 * 4 * cells))       # sab (8-byte aligned) in front, then saa, sbb, msc

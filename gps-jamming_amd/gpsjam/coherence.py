@@ -33,7 +33,7 @@ from typing import List, NamedTuple, Optional
 
 import numpy as np
 
-from . import CrossSpectrum
+from . import CrossSpectrum, _bands
 
 K5_SAMPLES = 65536          # the slice ``scan(lag="k5")`` hands to K5
 
@@ -76,11 +76,6 @@ def threshold(frames_per_row: int, p_fa: float = 1e-6) -> float:
     return 1.0 - float(p_fa) ** (1.0 / (m - 1))
 
 
-def _signed(nfft: int) -> np.ndarray:
-    k = np.arange(nfft)
-    return np.where(k >= nfft // 2, k - nfft, k)
-
-
 def detect(result: CrossSpectrum, p_fa: float = 1e-6, dc_guard: int = 1) -> Detection:
     """A bin is flagged when more than half of the rows exceed ``threshold(M, p_fa)``.  A NaN cell (a bin without
     power) never votes.  Bins within ``dc_guard`` of bin 0 are never flagged (negative: none is exempt)."""
@@ -90,29 +85,13 @@ def detect(result: CrossSpectrum, p_fa: float = 1e-6, dc_guard: int = 1) -> Dete
     with np.errstate(invalid="ignore"):
         above = np.sum(msc > thr, axis=0)
     flagged = 2 * above > rows
-    flagged &= np.abs(_signed(result.nfft)) > int(dc_guard)
+    flagged &= np.abs(_bands.signed_bins(result.nfft)) > int(dc_guard)
     return Detection(flagged, thr, float(p_fa))
 
 
 def bands(result: CrossSpectrum, detection: Detection, fs: float = 2.048e6) -> List[Band]:
     """Contiguous flagged runs in ascending frequency (fftshift order), with the median MSC of their cells."""
-    n = result.nfft
-    order = np.fft.fftshift(np.arange(n))                      # FFT-order bin at every shifted position
-    hit = np.asarray(detection.flagged, bool)[order]
-    width = float(fs) / n
-    out, at = [], 0
-    while at < n:
-        if not hit[at]:
-            at += 1
-            continue
-        end = at
-        while end + 1 < n and hit[end + 1]:
-            end += 1
-        cells = result.msc[:, order[at:end + 1]].astype(np.float64)
-        med = float(np.nanmedian(cells)) if np.isfinite(cells).any() else float("nan")
-        out.append(Band(int(order[at]), int(order[end]), end - at + 1, (at - n // 2 - 0.5) * width, (end - n // 2 + 0.5) * width, med))
-        at = end + 1
-    return out
+    return [Band(*run) for _, *run in _bands.runs(np.asarray(detection.flagged, bool), result.msc, fs)]
 
 
 def band_delay(result: CrossSpectrum, band: Band, coarse_lag: int = 0) -> Optional[float]:
@@ -121,15 +100,14 @@ def band_delay(result: CrossSpectrum, band: Band, coarse_lag: int = 0) -> Option
     of fewer than 3 bins (a line through two points has no residual to average)."""
     if band.n_bins < 3:
         return None
-    n = result.nfft
-    order = np.fft.fftshift(np.arange(n))
-    at = int(np.flatnonzero(order == band.first_bin)[0])
-    bins = order[at:at + band.n_bins]
+    n, signed = result.nfft, _bands.signed_bins(result.nfft)
+    at = int(signed[band.first_bin]) + n // 2                  # the band's place in ascending frequency
+    bins = _bands.shifted_order(n)[at:at + band.n_bins]
     s = result.sab[:, bins].astype(np.complex128).sum(axis=0)
     w = np.abs(s)
     if not np.all(np.isfinite(w)) or w.sum() == 0:
         return None
-    k = _signed(n)[bins].astype(np.float64)
+    k = signed[bins].astype(np.float64)
     phase = np.unwrap(np.angle(s))
     km, pm = np.sum(w * k) / w.sum(), np.sum(w * phase) / w.sum()
     slope = np.sum(w * (k - km) * (phase - pm)) / np.sum(w * (k - km) ** 2)

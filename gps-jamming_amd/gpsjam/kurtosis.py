@@ -24,7 +24,7 @@ from typing import List, NamedTuple
 
 import numpy as np
 
-from . import SpectralKurtosis
+from . import SpectralKurtosis, _bands
 
 
 class Detection(NamedTuple):
@@ -41,7 +41,8 @@ class Detection(NamedTuple):
 
 class Band(NamedTuple):
     """A contiguous run of flagged bins of one kind.  first_bin .. last_bin are FFT-order indices of the run's ends in
-    ascending frequency (the run may pass from nfft - 1 to 0); the frequencies are the outer edges of those bins."""
+    ascending frequency (across DC a run passes from nfft - 1 to 0; the band's two ends, nfft/2 - 1 and nfft/2, are never
+    joined: a run through them comes back as two); the frequencies are the outer edges of those bins."""
     kind: str                   # "steady" or "intermittent"
     first_bin: int
     last_bin: int
@@ -79,24 +80,8 @@ def detect(result: SpectralKurtosis, sigmas: float = 4.0) -> Detection:
 
 def bands(result: SpectralKurtosis, detection: Detection, fs: float = 2.048e6) -> List[Band]:
     """Contiguous flagged runs of one kind, in ascending frequency (fftshift order), with the median SK of their cells."""
-    n = result.nfft
-    order = np.fft.fftshift(np.arange(n))                      # FFT-order bin at every shifted position
-    kind = np.where(detection.steady, 1, np.where(detection.intermittent, 2, 0))[order]
-    width = float(fs) / n
-    out, at = [], 0
-    while at < n:
-        if kind[at] == 0:
-            at += 1
-            continue
-        end = at
-        while end + 1 < n and kind[end + 1] == kind[at]:
-            end += 1
-        cells = result.sk[:, order[at:end + 1]].astype(np.float64)
-        med = float(np.nanmedian(cells)) if np.isfinite(cells).any() else float("nan")
-        out.append(Band("steady" if kind[at] == 1 else "intermittent", int(order[at]), int(order[end]), end - at + 1,
-                        (at - n // 2 - 0.5) * width, (end - n // 2 + 0.5) * width, med))
-        at = end + 1
-    return out
+    kinds = np.where(detection.steady, 1, np.where(detection.intermittent, 2, 0))
+    return [Band("steady" if kind == 1 else "intermittent", *run) for kind, *run in _bands.runs(kinds, result.sk, fs)]
 
 
 def excision_threshold(result: SpectralKurtosis, detection: Detection, rise_db: float = 12.0) -> np.ndarray:

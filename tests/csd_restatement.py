@@ -23,7 +23,7 @@ import skurt_restatement as sr
 
 FS = rr.FS
 NFFT = rr.PARITY_NFFT                       # 16 .. 4096
-MAX_RUN = sr.MAX_RUN                        # frame pairs per block of the kernel (k_csd.hip kCsdMaxRun)
+MAX_RUN = sr.MAX_RUN                        # frame pairs per block of the kernel (stft_rows.h kRowMaxRun)
 S1_TOL = sr.S1_TOL                          # the project's tolerance for these very sums
 
 
@@ -112,15 +112,9 @@ def detect_pair(case, with_interferer=True):
 
 # ---------------------------------------------------------------------------------------------------- the definition
 def rows_that_fit(nbytes_a, first_a, nbytes_b, first_b, nfft, hop, frames_per_row):
-    """gj_csd_rows as the loop it abbreviates: rows whose last frame still ends inside BOTH captures."""
-    if nfft < 1 or hop < 1 or frames_per_row < 1:
-        return 0
-    rows, ta, tb = 0, nbytes_a // 2, nbytes_b // 2
-    while True:
-        end = ((rows + 1) * frames_per_row - 1) * hop + nfft
-        if first_a + end > ta or first_b + end > tb:
-            return rows
-        rows += 1
+    """gj_csd_rows: rows whose last frame still ends inside BOTH captures, the fewer of what each holds on its own."""
+    return min(sr.rows_that_fit(nbytes_a, first_a, nfft, hop, frames_per_row),
+               sr.rows_that_fit(nbytes_b, first_b, nfft, hop, frames_per_row))
 
 
 def frame_spectra(raw, nfft, hop, first, f0, n_frames, offset=127.5):
@@ -206,8 +200,7 @@ def full_band_lag(a, b, n=TWO_CORR_SAMPLES):
     return k if k < size // 2 else k - size
 
 
-def power_db(raw, against):
-    return sr.power_db(raw, against)
+power_db = sr.power_db
 
 
 # ---------------------------------------------------------------------------------------------------- GPU parity
@@ -215,10 +208,7 @@ PARITY_M = sr.PARITY_M                      # (2, 5, 17)
 BOUNDARY_NFFT = sr.BOUNDARY_NFFT
 BOUNDARY_HOP = sr.BOUNDARY_HOP
 BOUNDARY_M = sr.BOUNDARY_M
-
-
-def parity_hops(nfft):
-    return sr.parity_hops(nfft)             # nfft and nfft / 2 + 37
+parity_hops = sr.parity_hops                # nfft and nfft / 2 + 37
 
 
 @functools.lru_cache(maxsize=None)

@@ -19,7 +19,7 @@ import ridge_restatement as rr
 
 FS = rr.FS
 NFFT = rr.PARITY_NFFT                       # 16 .. 4096
-MAX_RUN = 16                                # frames per block of the kernel (k_skurt.hip kSkMaxRun)
+MAX_RUN = 16                                # frames per block of the kernel (stft_rows.h kRowMaxRun)
 
 # ---------------------------------------------------------------------------------------------------- detection cases
 DETECT_SAMPLES = 1 << 19

@@ -33,7 +33,7 @@ SCALE_SWEEP_SEED = 1
 CHIRP_NFFT = (16, 32, 64, 256, 1024, 2048, 4096)
 CHIRP_RIDGE_NFFT = (64, 1024, 4096)         # the single rate 0 against gj_ridge_dev
 SK_NFFT = (256, 1024, 4096)                 # a group inside a wave, a whole wave, the whole workgroup
-SK_M = 37                                   # sk_blocks: 3 blocks of 13, 13 and 11 frames
+SK_M = 37                                   # row_blocks: 3 blocks of 13, 13 and 11 frames
 SK_BLOCKS = (13, 13, 11)
 SK_HOP = 1
 

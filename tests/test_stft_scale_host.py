@@ -35,7 +35,7 @@ def test_frames_rows_and_runs_fit_the_captures():
         assert gpsjam.sk_rows(tone.size, si.FIRST, nfft, si.SK_HOP, si.SK_M) >= rows == sr.rows_that_fit(
             2 * (si.FIRST + (rows * si.SK_M - 1) * si.SK_HOP + nfft), si.FIRST, nfft, si.SK_HOP, si.SK_M)
         assert len(si.SK_BLOCKS) * rows >= si.STEPS * b > len(si.SK_BLOCKS) * (rows - 1)
-    # the kernel's partition of a row (k_skurt.hip sk_blocks): ceil(M / 16) blocks of ceil(M / blocks) frames, a short last one
+    # the kernel's partition of a row (stft_rows.h row_blocks): ceil(M / 16) blocks of ceil(M / blocks) frames, a short last one
     nb = -(-si.SK_M // sr.MAX_RUN)
     run = -(-si.SK_M // nb)
     assert (nb, run) == (3, 13) and si.SK_BLOCKS == (run, run, si.SK_M - 2 * run) and 0 < si.SK_BLOCKS[-1] < run
