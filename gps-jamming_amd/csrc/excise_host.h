@@ -1,6 +1,7 @@
-// What the two excisors, k_excise.hip and k_excise_chirp.hip, share besides the transform front end (stft_group.h; those
-// two include this, nothing else does): the geometry their kernels take, the run arithmetic of their launches and the
-// copy of the edges no frame pair covers.  The transform kernels themselves stay apart, each in its own file.
+// What the two excisors, k_excise.hip and k_excise_chirp.hip, and the canceller, k_cancel.hip, share besides the transform
+// front end (stft_group.h; those three include this, nothing else does): the geometry their kernels take, the run
+// arithmetic of their launches and the copy of the edges no frame pair covers.  The transform kernels themselves stay
+// apart, each in its own file.
 #pragma once
 #include "stft_group.h"
 

@@ -30,7 +30,7 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
            "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE",
            "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks", "FINE_BLOCK", "FINE_MAX_HALF", "fine_blocks", "FineCorr",
-           "CrossSpectrum", "csd_rows"]
+           "CrossSpectrum", "csd_rows", "CANCEL_DTYPE"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -176,6 +176,9 @@ def ridge_frames(nbytes: int, first_sample: int, nfft: int, hop: int) -> int:
 
 
 EXCISE_DTYPE = np.dtype([("total", np.float32), ("removed", np.float32), ("n_excised", np.int32), ("reserved", np.int32)])
+
+# gj_cancel_frame: one frame of the two-antenna canceller
+CANCEL_DTYPE = np.dtype([("total_in", np.float32), ("total", np.float32), ("removed", np.float32), ("n_excised", np.int32)])
 
 
 def excise_frames(n_samples: int, nfft: int) -> int:
@@ -1132,6 +1135,41 @@ class Device:
             return self._cleaned(n_samples, frames, EXCISE_DTYPE, lambda d_out, d_rec: self.excise_chirp_dev(
                 cap, cap.nbytes, first_sample, n_samples, nfft, rate, thr, d_out, d_rec))
 
+    def cancel(self, a, b, weights, threshold=None, nfft: int = 1024, first_a: int = 0, first_b: int = 0,
+               n_samples: Optional[int] = None, frames_per_set: Optional[int] = None):
+        """Two-antenna per-bin cancellation (gj_cancel_dev): samples first_a .. + n_samples of ``a`` (default: as many as
+        both captures hold) with ``W[k] * B_f[k]`` subtracted from every bin of every nfft-point frame, B_f being the frame
+        of ``b`` at first_b, and every bin whose remaining power exceeds ``threshold[k]`` taken out.  ``a`` and ``b``:
+        host bytes (uploaded once each) or resident ``Capture``s.  ``weights``: complex64[nfft] (one set) or
+        complex64[n_sets][nfft] in FFT order (``gpsjam.coherence.cancel_weights`` builds them); frame f uses set
+        ``min(f // frames_per_set, n_sets - 1)``, and ``frames_per_set`` defaults to all frames (needed only with more
+        than one set).  ``threshold``: as ``excise``; None never excises.  Returns ``(cleaned, records)``: the cleaned
+        range as a resident ``Capture`` of its own (the caller frees it) and one CANCEL_DTYPE record per frame."""
+        nfft, first_a, first_b = int(nfft), int(first_a), int(first_b)
+        w = np.asarray(weights)
+        if w.ndim not in (1, 2) or w.shape[-1] != nfft or w.size == 0:
+            raise ValueError(f"weights must be complex64[{nfft}] or [n_sets][{nfft}], not {w.shape}")
+        w = np.ascontiguousarray(w.reshape(-1, nfft), np.complex64)
+        n_sets = w.shape[0]
+        with contextlib.ExitStack() as temps:
+            cap_a = temps.enter_context(self._resident(a))
+            cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
+            if n_samples is None:
+                n_samples = max(0, min(cap_a.nsamples - first_a, cap_b.nsamples - first_b))
+            n_samples = int(n_samples)
+            frames = excise_frames(n_samples, nfft)
+            if frames_per_set is None:
+                if n_sets > 1:
+                    raise ValueError(f"{n_sets} weight sets need frames_per_set")
+                frames_per_set = max(frames, 1)
+            thr = np.full(nfft, np.inf, np.float32) if threshold is None else threshold
+            thr = self._on_device(temps, thr, np.float32, nfft, "threshold", f"nfft is {nfft}")
+            d_w = self._on_device(temps, w.view(np.float32), np.float32, 2 * n_sets * nfft, "weights", "")
+            self._count("cancel")
+            return self._cleaned(n_samples, frames, CANCEL_DTYPE, lambda d_out, d_rec: self.cancel_dev(
+                cap_a, cap_a.nbytes, first_a, cap_b, cap_b.nbytes, first_b, n_samples, nfft, d_w, frames_per_set, n_sets,
+                thr, d_out, d_rec))
+
     def blank(self, raw, threshold: float, window: int = 16, guard: int = 8, first_sample: int = 0,
               n_samples: Optional[int] = None):
         """Time-domain pulse blanking (gj_blank_dev): samples first_sample .. + n_samples of ``raw`` (default: to the
@@ -1200,6 +1238,14 @@ class Device:
         total) into d_rate, on the context's stream."""
         self._check(self._lib.gj_chirp_rates_dev(self._ctx, _ptr(d_scan), int(n_frames), int(rate_first), int(rate_step),
                                                  float(min_concentration), _ptr(d_rate)))
+
+    def cancel_dev(self, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, nfft, d_weights, frames_per_set, n_sets,
+                   d_threshold, d_out, d_frames=None):
+        """gj_cancel_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 16-byte record (CANCEL_DTYPE) per
+        frame into d_frames, with the float32[n_sets][nfft][2] weights in d_weights, on the context's stream."""
+        self._check(self._lib.gj_cancel_dev(self._ctx, _ptr(d_a), int(nbytes_a), int(first_a), _ptr(d_b), int(nbytes_b),
+                                            int(first_b), int(n_samples), int(nfft), _ptr(d_weights), int(frames_per_set),
+                                            int(n_sets), _ptr(d_threshold), _ptr(d_out), _ptr(d_frames) or None))
 
     def excise_dev(self, d_iq, nbytes, first_sample, n_samples, nfft, d_threshold, d_out, d_frames=None):
         """gj_excise_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 16-byte record (EXCISE_DTYPE) per

@@ -146,6 +146,11 @@ class ExciseFrame(C.Structure):
     _fields_ = [("total", C.c_float), ("removed", C.c_float), ("n_excised", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CancelFrame(C.Structure):
+    """gj_cancel_frame: one frame of the two-antenna canceller (include/gpsjam.h)."""
+    _fields_ = [("total_in", C.c_float), ("total", C.c_float), ("removed", C.c_float), ("n_excised", C.c_int32)]
+
+
 class BlankBlock(C.Structure):
     """gj_blank_block: one GJ_BLANK_BLOCK-sample record of the pulse blanker (include/gpsjam.h)."""
     _fields_ = [("total", C.c_uint64), ("removed", C.c_uint64), ("n_blanked", C.c_int32), ("n_rising", C.c_int32)]
@@ -223,6 +228,7 @@ SIGNATURES = {
     "gj_excise_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp]),
     "gj_excise_chirp_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp]),
     "gj_chirp_rates_dev": (_i, [_vp, _vp, _sz, _i, _i, _f, _vp]),
+    "gj_cancel_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _vp, _vp, _vp]),
     "gj_blank_blocks": (_sz, [_sz]),
     "gj_blank_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _f, _vp, _vp]),
     "gj_byte_histogram_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

@@ -24,6 +24,9 @@ Limits:
 
 prints the coherent bands and their delays.
 
+What is found can be taken out: ``cancel_weights`` turns the sums into the per-bin weights of the two-antenna canceller
+(``Device.cancel``, gj_cancel_dev; ``gpsjam.mitigate.clean_spatial`` joins the two).
+
 Nothing here computes on the CPU but the decisions on the rows x nfft numbers.
 """
 from __future__ import annotations
@@ -87,6 +90,38 @@ def detect(result: CrossSpectrum, p_fa: float = 1e-6, dc_guard: int = 1) -> Dete
     flagged = 2 * above > rows
     flagged &= np.abs(_bands.signed_bins(result.nfft)) > int(dc_guard)
     return Detection(flagged, thr, float(p_fa))
+
+
+def detect_cells(result: CrossSpectrum, p_fa: float = 1e-6, dc_guard: int = 1) -> Detection:
+    """``detect`` without the vote: ``flagged`` is bool[n_rows][nfft], every cell decided on its own row's MSC.  What a
+    jammer that is on in a few rows only needs; the false-alarm probability is then ``p_fa`` per cell, not per bin."""
+    thr = threshold(result.frames_per_row, p_fa)
+    with np.errstate(invalid="ignore"):
+        flagged = result.msc.astype(np.float64) > thr
+    flagged &= (np.abs(_bands.signed_bins(result.nfft)) > int(dc_guard))[None, :]
+    return Detection(flagged, thr, float(p_fa))
+
+
+def cancel_weights(result: CrossSpectrum, detection: Detection, per_row: bool = True) -> np.ndarray:
+    """The per-bin MMSE weights of the two-antenna canceller, W = conj(Sab) / Sbb: the prediction of a's spectrum from
+    b's that leaves the least power (``Device.cancel`` subtracts W B from A).  In the flagged bins only, exactly 0
+    elsewhere -- the DC guard bins, which no detection flags, and cells with Sbb = 0 or a sum that is not finite.
+    ``detection.flagged``: bool[nfft] (``detect``) or bool[n_rows][nfft] (``detect_cells``).
+    per_row=True: complex64[n_rows][nfft], each row from its own sums.  per_row=False: complex64[nfft] from the
+    row-summed sums, in the bins flagged in any row.  |W|^2 <= Saa / Sbb (Cauchy-Schwarz on the sums)."""
+    flagged = np.asarray(detection.flagged, bool)
+    sab, sbb = result.sab.astype(np.complex128), result.sbb.astype(np.float64)
+    if flagged.shape not in ((result.nfft,), sab.shape):
+        raise ValueError(f"flags of shape {flagged.shape} do not fit {sab.shape[0]} rows of {result.nfft} bins")
+    if per_row:
+        flagged = np.broadcast_to(flagged, sab.shape)
+    else:
+        sab, sbb = sab.sum(axis=0), sbb.sum(axis=0)
+        flagged = flagged.any(axis=0) if flagged.ndim == 2 else flagged
+    use = flagged & (sbb > 0) & np.isfinite(sbb) & np.isfinite(sab)
+    w = np.zeros(sab.shape, np.complex128)
+    w[use] = np.conj(sab[use]) / sbb[use]
+    return w.astype(np.complex64)
 
 
 def bands(result: CrossSpectrum, detection: Detection, fs: float = 2.048e6) -> List[Band]:

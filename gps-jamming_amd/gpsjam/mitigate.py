@@ -7,6 +7,7 @@ measures its spectrum, the excisor cleans the whole capture.
 
     python -m gpsjam.mitigate IN.bin OUT.bin [--nfft N] [--rise-db D] [--swept]
     python -m gpsjam.mitigate IN.bin OUT.bin --pulsed [--window W] [--guard G] [--rise-db D]
+    python -m gpsjam.mitigate A.bin OUT.bin --spatial B.bin [--nfft N] [--frames-per-row M] [--p-fa P] [--lag L|k5]
 
 writes the cleaned file, byte for byte as long as the input, for gnssdec.
 
@@ -19,15 +20,24 @@ bin of every frame it touches; the per-bin mask wipes those frames or lets the p
 (``--pulsed``) blanks in the time domain instead (``Device.blank``, gj_blank_dev): every sample near a short window
 whose mean power exceeds the noise floor raised by ``rise_db`` goes to mid-level.
 
-Nothing here computes on the CPU but the threshold's arithmetic on one PSD row or one floor value.
+A Gaussian broadband jammer stands above the floor in every bin of its band, sweeps nowhere and has no pulses: none of
+the three sees anything to cut.  With a second antenna it can be cancelled: ``clean_spatial`` (``--spatial``) finds the
+bins the two captures share (``coherence.scan``, gj_csd_dev), builds the per-bin weights from the same sums
+(``coherence.cancel_weights``) and subtracts the auxiliary antenna's weighted spectrum from the main one's
+(``Device.cancel``, gj_cancel_dev).  One auxiliary antenna gives one null per bin: a satellite whose inter-antenna phase
+is near the jammer's is attenuated with it, and the main antenna's receiver noise rises by up to 1 + |W|^2.
+
+Nothing here computes on the CPU but the threshold's arithmetic on one PSD row or one floor value, and the weights'
+on the rows x nfft sums.
 """
 from __future__ import annotations
 
-from typing import NamedTuple, Optional
+import contextlib
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 
-from . import Capture, excise_frames
+from . import Capture, _bands, excise_frames
 
 FLOOR_CHUNK_BYTES = 128       # K1's chunk while clean_pulsed reads the floor off a capture without a quiet part: 64 samples
 QUIET_FRAMES_MIN = 8          # the quiet part must hold 8 nfft samples to supply the floor
@@ -238,6 +248,63 @@ def clean_pulsed(dev, capture, window: int = 16, guard: int = 8, rise_db: float 
                          blanked / cleaned.nsamples if cleaned.nsamples else 0.0)
 
 
+class CleanedSpatial(NamedTuple):
+    """Result of ``clean_spatial``: the cleaned range of ``main`` as a resident ``Capture`` (the caller frees it), one
+    CANCEL_DTYPE record per frame, the weights that were applied (complex64[n_sets][nfft], FFT order), the coherence
+    scan they came from, the bands that were cancelled (flagged in any row), per band the measured suppression in dB,
+    10 log10(sum total_in / sum total) over the frames whose weight set is not zero inside the band, and whether anything
+    was cancelled at all (False: nothing coherent was flagged, ``capture`` is a copy of ``main``; ``note`` says so)."""
+    capture: Capture
+    records: np.ndarray
+    weights: np.ndarray
+    scan: object
+    bands: List
+    suppression_db: List[float]
+    cancelled: bool
+    note: str
+
+
+def clean_spatial(dev, main, aux, nfft: int = 1024, frames_per_row: int = 256, p_fa: float = 1e-6, lag="k5",
+                  threshold=None, fs: float = 2.048e6) -> CleanedSpatial:
+    """``main`` with what it shares with ``aux`` cancelled bin by bin (gj_cancel_dev).  ``main`` and ``aux``: resident
+    ``Capture``s or host bytes (uploaded once each) of two antennas on one clock.
+
+    ``coherence.scan`` runs at hop = nfft over rows of ``frames_per_row`` frame pairs, aligned by ``lag`` (samples by
+    which aux lags main, or "k5").  A cell -- one bin of one row -- whose coherence exceeds the threshold of ``p_fa``
+    (``coherence.detect_cells``) gets the weight conj(Sab) / Sbb of its own row's sums, every other cell exactly 0, so a
+    row without the jammer goes through untouched.  Row r covers the excisor frames [2 r M, 2 (r + 1) M) with
+    M = frames_per_row: the canceller takes one weight set per row at ``frames_per_set`` = 2 M, and the frames behind
+    the last whole row use the last set.  ``threshold``: the excisor's mask behind the cancellation, None for none.
+    The result covers the aligned range: main from sample max(-lag, 0) on, as long as both captures hold samples.
+    With nothing flagged the result is a copy of the whole of ``main`` and ``cancelled`` is False."""
+    from . import coherence
+    nfft, m = int(nfft), int(frames_per_row)
+    with dev._resident(main) as cap_a, (dev._resident(aux) if aux is not main else contextlib.nullcontext(cap_a)) as cap_b:
+        if excise_frames(cap_a.nsamples, nfft) == 0:
+            raise ValueError(f"the capture holds {cap_a.nsamples} samples, fewer than one frame of {nfft}")
+        found = coherence.scan(dev, cap_a, cap_b, lag=lag, fs=fs, nfft=nfft, frames_per_row=m, p_fa=p_fa)
+        cells = coherence.detect_cells(found.result, p_fa)
+        if not cells.flagged.any():
+            zero = np.zeros((1, nfft), np.complex64)
+            cleaned, rec = dev.cancel(cap_a, cap_a, zero, threshold, nfft=nfft)
+            return CleanedSpatial(cleaned, rec, zero, found, [], [], False, "nothing coherent was flagged: a copy of main")
+        weights = coherence.cancel_weights(found.result, cells, per_row=True)
+        cleaned, rec = dev.cancel(cap_a, cap_b, weights, threshold, nfft=nfft, first_a=found.result.first_a,
+                                  first_b=found.result.first_b, frames_per_set=2 * m)
+    union = coherence.Detection(cells.flagged.any(axis=0), cells.threshold, cells.p_fa)
+    cancelled = coherence.bands(found.result, union, fs)
+    sets = np.minimum(np.arange(rec.size) // (2 * m), weights.shape[0] - 1)
+    t_in, t_out = rec["total_in"].astype(np.float64), rec["total"].astype(np.float64)
+    shifted = _bands.shifted_order(nfft)
+    suppression = []
+    for bd in cancelled:
+        at = int(np.flatnonzero(shifted == bd.first_bin)[0])
+        active = np.any(weights[:, shifted[at:at + bd.n_bins]] != 0, axis=1)[sets]
+        num, den = t_in[active].sum(), t_out[active].sum()
+        suppression.append(float(10.0 * np.log10(num / den)) if num > 0 and den > 0 else float("nan"))
+    return CleanedSpatial(cleaned, rec, weights, found, cancelled, suppression, True, "")
+
+
 def main(argv=None) -> int:
     import argparse
     from . import Device
@@ -252,9 +319,30 @@ def main(argv=None) -> int:
     ap.add_argument("--pulsed", action="store_true", help="time-domain blanking of a pulse train (clean_pulsed; --rise-db defaults to 6)")
     ap.add_argument("--window", type=int, default=16, help="--pulsed: samples of the power window")
     ap.add_argument("--guard", type=int, default=8, help="--pulsed: samples blanked on either side of a detection")
+    ap.add_argument("--spatial", metavar="B.bin", default=None,
+                    help="cancel what the input shares with this second antenna's capture (clean_spatial)")
+    ap.add_argument("--frames-per-row", type=int, default=256, help="--spatial: frame pairs per weight set")
+    ap.add_argument("--p-fa", type=float, default=1e-6, help="--spatial: false-alarm probability per cell")
+    ap.add_argument("--lag", default="k5", help="--spatial: integer samples by which B lags the input, or k5")
     args = ap.parse_args(argv)
-    if args.pulsed and args.swept:
-        ap.error("--pulsed and --swept exclude each other")
+    if sum(map(bool, (args.pulsed, args.swept, args.spatial))) > 1:
+        ap.error("--pulsed, --swept and --spatial exclude each other")
+    if args.spatial:
+        lag = "k5" if args.lag == "k5" else int(args.lag)
+        with Device(args.device) as dev:
+            with dev.capture(args.input) as cap, dev.capture(args.spatial) as aux:
+                res = clean_spatial(dev, cap, aux, nfft=args.nfft, frames_per_row=args.frames_per_row, p_fa=args.p_fa, lag=lag,
+                                    fs=args.fs)
+                try:
+                    res.capture.download().tofile(args.output)
+                finally:
+                    res.capture.free()
+        print(f"{args.output}: {res.records.size} frames of {args.nfft} points, aligned by {res.scan.lag}, "
+              + (f"{len(res.bands)} band(s) cancelled" if res.cancelled else res.note))
+        for bd, db in zip(res.bands, res.suppression_db):
+            print(f"  {bd.freq_lo_hz / 1e3:9.1f} .. {bd.freq_hi_hz / 1e3:9.1f} kHz  ({bd.n_bins} bins)  median MSC {bd.median_msc:.3f}  "
+                  f"suppression {db:.1f} dB")
+        return 0
     if args.pulsed:
         rise_db = 6.0 if args.rise_db is None else args.rise_db
         with Device(args.device) as dev:

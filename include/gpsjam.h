@@ -448,6 +448,51 @@ int gj_excise_chirp_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t 
 int gj_chirp_rates_dev(gj_ctx* ctx, const gj_chirp_frame* d_scan, size_t n_frames, int rate_first, int rate_step,
                        float min_concentration, int32_t* d_rate /* [n_frames] */);
 
+/* ------------------------------------------------- two-antenna per-bin canceller ---- */
+/* The frequency-domain sidelobe canceller (per-bin power inversion) of a receiver with two antennas: capture a's short
+ * spectrum is predicted from capture b's with one complex weight per bin, the prediction is subtracted, and the rest
+ * goes back to uint8 I/Q through the excisor's mask and overlap-add.  What is coherent between the antennas is removed,
+ * a broadband Gaussian jammer included, which no threshold, de-chirp or blanker can touch; satellites arrive from other
+ * directions with another inter-antenna phase and stay.  The MMSE weight is W[k] = conj(Sab[k]) / Sbb[k] of gj_csd_dev's
+ * sums (gpsjam/coherence.py builds it).  With F, h = N/2, w, x (per capture), scale, the output rule and the copied edges
+ * exactly gj_excise_dev's, F = gj_excise_frames(n_samples, nfft), and frames f = 0 .. F-1:
+ *
+ *   A_f[k]  = sum_n w[n] x_a[first_a + f*h + n] exp(-2 pi i k n / N)     B_f[k] likewise from capture b at first_b + f*h
+ *   set(f)  = min(f / frames_per_set, n_sets - 1)                         integer division
+ *   Y_f[k]  = A_f[k] - W[set(f)][k] * B_f[k]          every product of W * B rounded on its own, then the subtraction
+ *   P_f[k]  = |Y_f[k]|^2 * scale^2
+ *   M_f[k]  = 0 if P_f[k] > thr[k] else 1             strict; +inf never, negative always, NaN never, as gj_excise_dev
+ *   y_f     = IFFT_N(M_f * Y_f)                       with the 1/N
+ *   y[t]    = y_{f-1}[t - s_{f-1}] + y_f[t - s_f]     for t covered by two frames
+ *
+ * d_weights: DEVICE float32[n_sets][nfft][2], (re, im), FFT order; the host never reads it.  With every weight 0 the
+ * call writes exactly the bytes of gj_excise_dev on capture a, and its total, removed and n_excised.
+ * Output: d_out[2*n_samples], range-relative as gj_excise_dev's; the first half frame and everything from F*h on are
+ * copied from capture a.  The call writes exactly 2*n_samples bytes.  d_frames (optional) receives one record per frame.
+ * first_a and first_b may be odd and may differ; d_a == d_b is allowed.
+ * Refusals: those of gj_excise_dev for each capture (nfft, n_samples < nfft, a range past either capture, a null or odd
+ * d_a or d_b, a null d_out or d_threshold, a d_threshold or d_frames that is not 4-byte aligned, d_out overlapping either
+ * capture), frames_per_set == 0 or n_sets == 0, a null d_weights or one that is not 8-byte aligned (GJ_ERR_INVALID but
+ * for nfft: GJ_ERR_UNSUPPORTED).  A refused call enqueues nothing.  Needs no workspace; enqueues on the context's stream
+ * (two launches: the transform kernel and the edge copy) and returns.
+ * Determinism: an output sample depends only on the bytes of the two frame pairs that cover it and on their weight sets,
+ * and every sum runs in an order fixed by nfft.  So a call started k*h samples later in both captures, with the sets
+ * shifted alike, reproduces the overlapping interior bytes and the records of the shared frames bit for bit; two
+ * identical calls give identical bytes; and d_frames == NULL changes no byte.
+ * Limits: one auxiliary antenna gives one null per bin -- a signal whose inter-antenna phase is near the jammer's is
+ * attenuated with it -- and capture a's receiver noise rises by up to 1 + |W|^2.  The pair must share a clock and be
+ * aligned to well under nfft samples, as for gj_csd_dev. */
+typedef struct gj_cancel_frame {   /* 16 bytes */
+    float total_in;    /* sum_k |A_f[k]|^2 scale^2 */
+    float total;       /* sum_k P_f[k], behind the cancellation */
+    float removed;     /* sum of P_f[k] over the excised bins */
+    int32_t n_excised; /* bins with M_f[k] = 0 */
+} gj_cancel_frame;
+int gj_cancel_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t first_a, const uint8_t* d_b, size_t nbytes_b,
+                  size_t first_b, size_t n_samples, int nfft, const float* d_weights /* [n_sets][nfft][2] */,
+                  size_t frames_per_set, size_t n_sets, const float* d_threshold /* [nfft] */,
+                  uint8_t* d_out /* [2*n_samples] */, gj_cancel_frame* d_frames /* [F] or NULL */);
+
 /* ------------------------------------------------- time-domain pulse blanking ------- */
 /* The pulse blanker a receiver puts in front of its FFT excisor: a cleaned capture, uint8 I/Q again, with every sample
  * near a window of excess power put to mid-level (simulate/frontend/jammers/pulsedJammer.py and every sweep that crosses

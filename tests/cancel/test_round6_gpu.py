@@ -1,0 +1,413 @@
+"""The two-antenna per-bin canceller (gj_cancel_dev, Device.cancel, gpsjam.mitigate.clean_spatial) on the GPU.
+
+This file sits in a package of its own on purpose, as tests/csd/ does: the suite orders GPU files by basename
+(tests/conftest.py SUITE_ORDER, which tests/test_suite_order.py holds every GPU file to), and under the name
+test_round6_gpu.py it runs in stage 2, behind the parity tests of K2 whose transform it shares.
+
+Yardstick: the float64 restatement of the definition in include/gpsjam.h (tests/cancel_restatement.py).  The mask is
+equal on EVERY bin of every frame (tests/test_cancel_host.py shows that no input has a bin within 1e-4 of its
+threshold); total_in, total and removed within rtol 1e-5 of total_in; bytes equal wherever the float64 value is further
+than TIE_BAND from a rounding tie and within 1 elsewhere.  The anchors (W = 0 against gj_excise_dev, a capture against
+itself, every bin cut), translation, repetition and the run seams are bit-exact.  Every call writes into
+sentinel-filled buffers whose bytes behind 2 * n_samples and behind d_frames[F] must stay untouched."""
+import numpy as np
+import pytest
+
+import cancel_restatement as cr
+import excise_restatement as er
+import gpsjam
+import stft_scale_inputs as si
+from excise import test_round6_gpu as excise_t
+from gpsjam import gnss, mitigate
+
+pytestmark = pytest.mark.gpu
+
+GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
+REC = gpsjam.CANCEL_DTYPE.itemsize
+SENTINEL = 0xA5
+PAD = 256                                       # sentinel bytes behind d_out[2 n_samples] and behind d_frames[F]
+RTOL = 1e-5
+FA, FB, N = cr.PARITY_FIRST_A, cr.PARITY_FIRST_B, cr.PARITY_SAMPLES
+
+
+@pytest.fixture(scope="module")
+def pair(dev):
+    a, b = (dev.capture(r) for r in cr.parity_pair())
+    yield a, b
+    a.free()
+    b.free()
+
+
+class Resident:
+    """Arrays resident once per (dtype, values)."""
+
+    def __init__(self, dev):
+        self.dev, self.bufs = dev, {}
+
+    def __call__(self, values, dtype=np.float32):
+        values = np.ascontiguousarray(values, dtype)
+        key = (np.dtype(dtype).str, values.tobytes())
+        if key not in self.bufs:
+            self.bufs[key] = self.dev.alloc(max(values.nbytes, 1)).upload(values.reshape(-1).view(np.uint8))
+        return self.bufs[key]
+
+    def free(self):
+        for b in self.bufs.values():
+            b.free()
+
+
+@pytest.fixture(scope="module")
+def res(dev):
+    r = Resident(dev)
+    yield r
+    r.free()
+
+
+def run(dev, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, want_frames=True):
+    """(bytes[2 n_samples], records[F]) through gj_cancel_dev into sentinel-filled buffers."""
+    nf = gpsjam.excise_frames(n_samples, nfft)
+    out, rec = dev.alloc(2 * n_samples + PAD), dev.alloc(nf * REC + PAD)
+    try:
+        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
+        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
+        dev.cancel_dev(d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, out,
+                       rec if want_frames else None)
+        got, raw = out.download(np.uint8), rec.download(np.uint8)
+    finally:
+        out.free()
+        rec.free()
+    assert np.all(got[2 * n_samples:] == SENTINEL), "bytes were written behind d_out[2 n_samples]"
+    assert np.all(raw[(nf * REC if want_frames else 0):] == SENTINEL), "records were written behind d_frames[F]"
+    return got[:2 * n_samples], raw[:nf * REC].view(gpsjam.CANCEL_DTYPE)
+
+
+def run_pair(dev, pair, nfft, d_w, frames_per_set, n_sets, d_thr, first_a=FA, first_b=FB, n_samples=N, want_frames=True):
+    a, b = pair
+    return run(dev, a, a.nbytes, first_a, b, b.nbytes, first_b, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, want_frames)
+
+
+def compare(got, rec, want, what):
+    """GPU bytes and records against a cr.Cancelled."""
+    assert rec.size == want.records.size and got.size == want.out.size, what
+    # the mask on every bin: per frame the count is equal, and no bin of the restatement is near its threshold, so a
+    # differing bin would have to be matched by another differing the other way at a margin of 1e-4 each
+    np.testing.assert_array_equal(rec["n_excised"], want.records["n_excised"], err_msg=str(what))
+    tin = want.records["total_in"]
+    for key in ("total_in", "total", "removed"):
+        err = float(np.max(np.abs(rec[key] - want.records[key]) / tin))
+        print(f"{what} {key}: {err:.2e} of total_in")
+        assert err <= RTOL, (what, key, err)
+    assert np.array_equal(got[:want.lo], want.out[:want.lo]) and np.array_equal(got[want.hi:], want.out[want.hi:]), (what, "edges")
+    body, ref = got[want.lo:want.hi].astype(np.int16), want.out[want.lo:want.hi].astype(np.int16)
+    clear = er.tie_distance(want.value) > cr.TIE_BAND
+    diff = np.abs(body - ref)
+    print(f"{what}: {int(np.sum(diff != 0))} of {diff.size} bytes differ, {int(np.sum(~clear))} lie in the tie band")
+    assert not diff[clear].any(), (what, int(np.sum(diff[clear] != 0)), "bytes differ outside the tie band")
+    assert diff.max(initial=0) <= 1, (what, int(diff.max()))
+
+
+# ------------------------------------------------------------------------------------------------ 1. parity
+@pytest.mark.parametrize("nfft", cr.NFFT)
+def test_parity_with_the_restatement(dev, pair, res, nfft):
+    try:
+        for offset, scale in cr.CONVENTIONS:
+            dev.set_unpack(offset, scale)
+            want = cr.parity_reference(nfft, offset, scale)
+            w = cr.parity_weights(nfft, offset)
+            got, rec = run_pair(dev, pair, nfft, res(w.view(np.float32)), cr.PARITY_FRAMES_PER_SET, w.shape[0],
+                                res(cr.parity_threshold(nfft, scale)))
+            compare(got, rec, want, (nfft, offset))
+            # removed is the sum of exactly the restatement's cut bins: with equal counts, a mask that differed in a
+            # pair of bins would move `removed` by about a threshold's worth, far more than RTOL of a frame holds
+            assert want.cut.any() and not want.cut.all()
+    finally:
+        dev.set_unpack()
+    assert dev.get_unpack() == (127.5, 1.0 / 127.5)
+
+
+# ------------------------------------------------------------------------------------------------ 2. anchors
+@pytest.mark.parametrize("nfft", cr.NFFT)
+def test_anchors_are_bit_exact(dev, pair, res, nfft):
+    a, b = pair
+    h = nfft // 2
+    d_thr = res(cr.parity_threshold(nfft))
+    zero, one = res(np.zeros(2 * nfft)), res(np.tile(np.float32([1.0, 0.0]), nfft))
+    # W = 0: gj_excise_dev on capture a, whatever b is
+    ex_b, ex_r = excise_t.run(dev, a, a.nbytes, FA, N, nfft, d_thr)
+    assert ex_r["n_excised"].any()
+    for d_b, nbytes_b, first_b in ((b, b.nbytes, FB), (a, a.nbytes, 0)):
+        got, rec = run(dev, a, a.nbytes, FA, d_b, nbytes_b, first_b, N, nfft, zero, 3, 1, d_thr)
+        assert got.tobytes() == ex_b.tobytes(), (nfft, "bytes of gj_excise_dev")
+        for key in ("total", "removed", "n_excised"):
+            assert rec[key].tobytes() == ex_r[key].tobytes(), (nfft, key)
+        assert rec["total_in"].tobytes() == rec["total"].tobytes()
+    # a capture against itself with W = (1, 0): nothing is left
+    inf = res(np.full(nfft, np.inf))
+    try:
+        for offset, scale in cr.CONVENTIONS:
+            dev.set_unpack(offset, scale)
+            got, rec = run(dev, a, a.nbytes, FA, a, a.nbytes, FA, N, nfft, one, 1, 1, inf)
+            nf = rec.size
+            assert not rec["total"].any() and not rec["removed"].any() and not rec["n_excised"].any() and np.all(rec["total_in"] > 0)
+            if offset == 127.5:
+                assert np.all(got[2 * h:nf * nfft] == 128), (nfft, "rint(127.5) = 128")
+            raw = cr.parity_pair()[0]
+            assert got[:nfft].tobytes() == raw[2 * FA:2 * FA + nfft].tobytes()
+            assert got[nf * nfft:].tobytes() == raw[2 * FA + nf * nfft:2 * (FA + N)].tobytes()
+    finally:
+        dev.set_unpack()
+    # every threshold negative: everything that is left is removed
+    w = cr.parity_weights(nfft)
+    got, rec = run_pair(dev, pair, nfft, res(w.view(np.float32)), cr.PARITY_FRAMES_PER_SET, w.shape[0], res(np.full(nfft, -1.0)))
+    assert np.all(rec["n_excised"] == nfft) and rec["removed"].tobytes() == rec["total"].tobytes() and np.all(rec["total"] > 0)
+    assert np.all(got[2 * h:rec.size * nfft] == 128)
+
+
+# ------------------------------------------------------------------------------------------------ 3. translation
+@pytest.mark.parametrize("nfft", cr.NFFT)
+def test_translation_null_records_and_repetition(dev, pair, res, nfft):
+    h = nfft // 2
+    d_thr = res(cr.parity_threshold(nfft))
+    w = cr.parity_weights(nfft)
+    d_w, fps, n_sets = res(w.view(np.float32)), cr.PARITY_FRAMES_PER_SET, w.shape[0]
+    long_b, long_r = run_pair(dev, pair, nfft, d_w, fps, n_sets, d_thr)
+    again_b, again_r = run_pair(dev, pair, nfft, d_w, fps, n_sets, d_thr)
+    assert again_b.tobytes() == long_b.tobytes() and again_r.tobytes() == long_r.tobytes(), "two identical calls"
+    no_rec, _ = run_pair(dev, pair, nfft, d_w, fps, n_sets, d_thr, want_frames=False)
+    assert no_rec.tobytes() == long_b.tobytes(), "d_frames = NULL changes no byte"
+    nf = long_r.size
+
+    def shifted(k, d_sets, per_set, sets, ref_b, ref_r):
+        got_b, got_r = run_pair(dev, pair, nfft, d_sets, per_set, sets, d_thr, FA + k * h, FB + k * h, N - k * h)
+        assert got_r.tobytes() == ref_r[k:].tobytes(), (nfft, k, per_set, "records of the shared frames")
+        assert got_b[nfft:(nf - k) * nfft].tobytes() == ref_b[(k + 1) * nfft:nf * nfft].tobytes(), (nfft, k, per_set, "interior bytes")
+
+    # k a multiple of frames_per_set, the sets shifted alike
+    for sets_off in (1, 2):
+        k = sets_off * fps
+        if k + 2 <= nf and sets_off < n_sets:
+            shifted(k, d_w.ptr + 8 * nfft * sets_off, fps, n_sets - sets_off, long_b, long_r)
+    # one set: every k
+    one_b, one_r = run_pair(dev, pair, nfft, d_w, fps, 1, d_thr)
+    for k in (1, 2, 3, 4):
+        if k + 2 <= nf:
+            shifted(k, d_w, 2, 1, one_b, one_r)
+    # a set per frame
+    each_b, each_r = run_pair(dev, pair, nfft, d_w, 1, n_sets, d_thr)
+    assert each_r[:fps].tobytes() != long_r[:fps].tobytes() or n_sets == 1
+    for k in (1, 3):
+        if k + 2 <= nf and k < n_sets:
+            shifted(k, d_w.ptr + 8 * nfft * k, 1, n_sets - k, each_b, each_r)
+
+
+# ------------------------------------------------------------------------------------------------ 4. run seams
+SEAM_FRAMES_PER_SET = 7
+SEAM_FIRST_B = si.EXCISE_FIRST + 3              # capture b is capture a three samples on (d_b == d_a)
+
+
+@pytest.fixture(scope="module")
+def seam_cap(dev):
+    c = dev.capture(si.scale_excise_capture())
+    yield c
+    c.free()
+
+
+@pytest.mark.parametrize("nfft", (256, 4096))
+def test_runs_longer_than_four_frames(dev, seam_cap, res, nfft):
+    cus = dev.info()["compute_units"]
+    f, n, h, first = si.excise_frames(nfft), si.excise_samples(nfft), nfft // 2, si.EXCISE_FIRST
+    per = si.excise_per_run(cus, nfft, f)               # CancelCfg::min_waves and min_run are the excisor's 2 and 4
+    assert per >= 5 and per % 4 != 0, (f"{nfft}: {f} frames are sized for runs of five on {si.SIZED_FOR_CUS} CUs; on this device's {cus} a "
+                                       f"run holds {per} frames, which the parity tests cover already")
+    assert f == 2048 * (4096 // nfft) + 1 and (si.SIZED_FOR_CUS != cus or (per == 5 and f % per != 0))
+    cap, fps = seam_cap, SEAM_FRAMES_PER_SET
+    assert gpsjam.excise_frames(n, nfft) == f and SEAM_FIRST_B + n <= cap.nsamples
+    n_sets = -(-f // fps)
+    rng = np.random.default_rng(nfft)
+    w = (rng.uniform(0.0, 1.0, (n_sets, nfft)) * np.exp(2j * np.pi * rng.uniform(0.0, 1.0, (n_sets, nfft)))).astype(np.complex64)
+    d_w, d_thr = res(w.view(np.float32)), res(si.excise_thresholds(nfft))
+
+    def call(first_frame, n_samples, want_frames=True):
+        assert first_frame % fps == 0
+        s = first_frame // fps
+        return run(dev, cap, cap.nbytes, first + first_frame * h, cap, cap.nbytes, SEAM_FIRST_B + first_frame * h, n_samples, nfft,
+                   d_w.ptr + 8 * nfft * s, fps, n_sets - s, d_thr, want_frames)
+
+    long_b, long_r = call(0, n)
+    assert long_r["n_excised"].sum() > 0 and np.all(long_r["total"] > 0)
+    again_b, again_r = call(0, n)
+    assert again_b.tobytes() == long_b.tobytes() and again_r.tobytes() == long_r.tobytes(), "the long call repeated"
+    raw = si.scale_excise_capture()
+    assert long_b[:nfft].tobytes() == raw[2 * first:2 * first + nfft].tobytes(), "the first half frame is capture a's"
+    assert f * nfft < 2 * n and long_b[f * nfft:].tobytes() == raw[2 * first + f * nfft:2 * (first + n)].tobytes(), "the tail is capture a's"
+    # two overlapping halves with runs of another length, the second one started on a set's first frame
+    k2 = (f // 2 - 2) // fps * fps
+    covered = np.zeros(f, bool)
+    for k, m in ((0, f // 2 + 2), (k2, f - k2)):
+        half_per = si.excise_per_run(cus, nfft, m)
+        assert half_per != per and half_per >= si.EXCISE_MIN_RUN, (nfft, per, half_per)
+        piece_b, piece_r = call(k, (m - 1) * h + nfft if k == 0 else n - k * h)
+        assert piece_r.size == m and piece_r.tobytes() == long_r[k:k + m].tobytes(), (nfft, k, "records")
+        assert piece_b[nfft:m * nfft].tobytes() == long_b[(k + 1) * nfft:(k + m) * nfft].tobytes(), (nfft, k, "interior bytes")
+        covered[k + 1:k + m] = True
+    assert covered[1:].all(), "every hop of the long call lies inside a half"
+    # a float64 restatement of the frames around the first run seam, from their own bytes and sets
+    w0 = (5 * (4096 // nfft)) // fps * fps
+    frames = 3 * fps
+    sets = slice(w0 // fps, w0 // fps + 3)
+    ns = (frames - 1) * h + nfft
+    want = cr.cancel(raw, raw, w[sets], si.excise_thresholds(nfft), nfft, first + w0 * h, SEAM_FIRST_B + w0 * h, ns, fps)
+    assert er.threshold_margin(want.power, si.excise_thresholds(nfft)) >= cr.NEAR_TIE, "an input with a bin at its threshold"
+    np.testing.assert_array_equal(long_r["n_excised"][w0:w0 + frames], want.records["n_excised"])
+    for key in ("total_in", "total", "removed"):
+        assert np.max(np.abs(long_r[key][w0:w0 + frames] - want.records[key]) / want.records["total_in"]) <= RTOL, (nfft, key)
+    diff = np.abs(long_b[(w0 + 1) * nfft:(w0 + frames) * nfft].astype(np.int16) - want.out[nfft:frames * nfft].astype(np.int16))
+    assert diff.max() <= 1 and not diff[er.tie_distance(want.value) > cr.TIE_BAND].any(), (nfft, "bytes around the first seam")
+
+
+# ------------------------------------------------------------------------------------------------ 5. refusals
+def test_refusals_enqueue_nothing(dev, pair, res):
+    a, b = pair
+    n = 8 * 256
+    t256, t16 = res(np.full(256, -1.0)), res(np.full(16, -1.0))
+    w256 = res(np.zeros(2 * 2 * 256))
+    out, rec = dev.alloc(a.nbytes + PAD), dev.alloc(4096 * REC + PAD)
+
+    def args(d_a=a, nbytes_a=a.nbytes, first_a=0, d_b=b, nbytes_b=b.nbytes, first_b=0, n_samples=n, nfft=256, d_w=w256, fps=4, n_sets=2,
+             d_thr=t256, d_out=out, d_rec=rec):
+        return (d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, nfft, d_w, fps, n_sets, d_thr, d_out, d_rec)
+    try:
+        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
+        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
+        cases = [
+            (args(nfft=8), GJ_ERR_UNSUPPORTED),
+            (args(nfft=8192, n_samples=3 * 8192), GJ_ERR_UNSUPPORTED),
+            (args(nfft=48), GJ_ERR_UNSUPPORTED),
+            (args(nfft=0), GJ_ERR_UNSUPPORTED),
+            (args(n_samples=255), GJ_ERR_INVALID),                                   # n_samples < nfft
+            (args(n_samples=0), GJ_ERR_INVALID),
+            (args(first_a=FA + 1, n_samples=N), GJ_ERR_INVALID),                     # runs past capture a
+            (args(first_b=FB + 1, n_samples=N), GJ_ERR_INVALID),                     # ... past capture b alone
+            (args(first_a=a.nsamples + 1), GJ_ERR_INVALID),
+            (args(first_b=2 ** 63, n_samples=2 ** 63 + 256), GJ_ERR_INVALID),        # first + n wraps
+            (args(d_a=0), GJ_ERR_INVALID),                                           # null captures
+            (args(d_b=0), GJ_ERR_INVALID),
+            (args(d_a=a.ptr + 1, nbytes_a=a.nbytes - 2), GJ_ERR_INVALID),            # odd captures
+            (args(d_b=b.ptr + 1, nbytes_b=b.nbytes - 2), GJ_ERR_INVALID),
+            (args(d_out=0), GJ_ERR_INVALID),                                         # null d_out, d_threshold
+            (args(d_thr=0), GJ_ERR_INVALID),
+            (args(d_thr=t256.ptr + 2), GJ_ERR_INVALID),                              # misaligned d_threshold, d_frames
+            (args(d_rec=rec.ptr + 2), GJ_ERR_INVALID),
+            (args(fps=0), GJ_ERR_INVALID),                                           # the sets
+            (args(n_sets=0), GJ_ERR_INVALID),
+            (args(d_w=0), GJ_ERR_INVALID),
+            (args(d_w=w256.ptr + 4), GJ_ERR_INVALID),                                # d_weights: 8 bytes
+            (args(d_w=w256.ptr + 2), GJ_ERR_INVALID),
+            # d_out overlapping capture a, capture b (in place, shifted, touching the last byte), a capture inside d_out
+            (args(d_a=out, nbytes_a=a.nbytes), GJ_ERR_INVALID),
+            (args(d_b=out, nbytes_b=b.nbytes), GJ_ERR_INVALID),
+            (args(d_a=out, nbytes_a=a.nbytes, d_out=out.ptr + 2 * n), GJ_ERR_INVALID),
+            (args(d_b=out, nbytes_b=a.nbytes, d_out=out.ptr + a.nbytes - 1), GJ_ERR_INVALID),
+            (args(d_b=out.ptr + 512, nbytes_b=1024, n_samples=256, d_out=out.ptr + 1), GJ_ERR_INVALID),
+        ]
+        for call, status in cases:
+            with pytest.raises(gpsjam.GpsJamError) as e:
+                dev.cancel_dev(*call)
+            assert e.value.status == status, (call[1:3], call[4:12], e.value)
+        dev.synchronize()
+        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL)
+        # accepted: a call that just fits both captures, the output right behind an input's last byte, d_b == d_a at
+        # odd and different firsts, no records, 16 points at the capture's end
+        dev.cancel_dev(*args(first_a=FA, first_b=FB, n_samples=N))
+        dev.cancel_dev(*args(d_a=out, nbytes_a=2 * n, d_out=out.ptr + 2 * n, d_rec=None))
+        dev.cancel_dev(*args(d_b=a, nbytes_b=a.nbytes, first_a=1, first_b=5, d_rec=None))
+        dev.cancel_dev(*args(first_a=a.nsamples - 16, first_b=b.nsamples - 16, n_samples=16, nfft=16, d_thr=t16))
+        dev.synchronize()
+        assert np.all(out.download(np.uint8, PAD, a.nbytes) == SENTINEL)
+    finally:
+        out.free()
+        rec.free()
+
+
+# ------------------------------------------------------------------------------------------------ Device.cancel
+def test_device_cancel_takes_host_bytes_and_captures(dev, pair):
+    ra, rb = cr.parity_pair()
+    nfft = 256
+    w, thr = cr.parity_weights(nfft), cr.parity_threshold(nfft)
+    want = cr.parity_reference(nfft)
+    uploads = gpsjam.Capture.uploads
+    x, rec_x = dev.cancel(pair[0], pair[1], w, thr, nfft=nfft, first_a=FA, first_b=FB, frames_per_set=cr.PARITY_FRAMES_PER_SET)
+    assert gpsjam.Capture.uploads == uploads, "a cleaned capture is no host->device pass"
+    y, rec_y = dev.cancel(ra, rb, w, thr, nfft=nfft, first_a=FA, first_b=FB, frames_per_set=cr.PARITY_FRAMES_PER_SET)
+    try:
+        assert isinstance(x, gpsjam.Capture) and x.nbytes == 2 * N and rec_x.dtype == gpsjam.CANCEL_DTYPE
+        assert x.download().tobytes() == y.download().tobytes() and rec_x.tobytes() == rec_y.tobytes()
+        compare(x.download(), rec_x, want, "Device.cancel")
+        # one set, no threshold, the defaults: the whole of what both hold from sample 0
+        z, rec_z = dev.cancel(pair[0], pair[1], w[0], nfft=nfft)
+        assert z.nsamples == min(pair[0].nsamples, pair[1].nsamples) and not rec_z["n_excised"].any()
+        z.free()
+        with pytest.raises(ValueError):
+            dev.cancel(pair[0], pair[1], w, nfft=nfft)                  # several sets need frames_per_set
+        with pytest.raises(ValueError):
+            dev.cancel(pair[0], pair[1], np.zeros(nfft + 1, np.complex64), nfft=nfft)
+    finally:
+        x.free()
+        y.free()
+
+
+# ------------------------------------------------------------------------------------------------ 6. end to end
+@pytest.fixture(scope="module")
+def search(dev):
+    s = gnss.AcqSearch(dev, prns=[p for p, *_ in er.E2E_SATS])
+    yield s
+    s.close()
+
+
+def test_end_to_end_the_satellites_come_back(dev, search):
+    """Three C/A signals of 1.5 LSB in noise of sigma 10 LSB at each of two antennas; from sample 2^17 on a full-band
+    Gaussian jammer of sigma 30 LSB, in the second antenna 0.4 sample later and turned by 1.3 rad.  Neither the raw capture
+    nor mitigate.clean's acquires any of them (tests/test_cancel_host.py asserts that on the CPU, and that all three
+    acquire jammer-free); mitigate.clean_spatial brings all three back."""
+    free_a, _ = cr.e2e_pair(False)
+    raw_a, raw_b = cr.e2e_pair(True)
+    lead, nfft, m = er.E2E_LEAD, cr.E2E_NFFT, cr.E2E_FRAMES_PER_ROW
+    with dev.capture(free_a) as c:
+        free = search.search(c, first_sample=lead)
+    assert all(r.acquired for r in free), free
+    with dev.capture(raw_a) as ca, dev.capture(raw_b) as cb:
+        before = search.search(ca, first_sample=lead)
+        got = mitigate.clean_spatial(dev, ca, cb, nfft=nfft, frames_per_row=m, lag=0)
+    try:
+        assert got.cancelled and got.note == "" and got.capture.nbytes == raw_a.size
+        after = search.search(got.capture, first_sample=lead)
+        cleaned = got.capture.download()
+    finally:
+        got.capture.free()
+    assert not any(r.acquired for r in before), before
+    assert got.weights.shape == (5, nfft) and not got.weights[:4].any(), "nothing is flagged in the quiet rows: W = 0 there"
+    flagged = got.weights[4] != 0
+    w_abs = float(np.median(np.abs(got.weights[4][flagged])))
+    assert flagged.sum() >= nfft - 16 and not flagged[[0, 1, -1]].any() and 0.8 < w_abs < 1.0
+    print(f"{int(flagged.sum())} bins cancelled, median |W| {w_abs:.3f}, suppression {got.suppression_db}")
+    assert len(got.bands) >= 1 and all(5.0 < s < 10.0 for s in got.suppression_db)       # 10 log10(10 / (1 + |W|^2)) = 7.4 dB
+    for r, ref, dphi in zip(after, free, cr.E2E_SAT_DPHI):
+        want = ref.cn0 + cr.e2e_predicted_db(w_abs, dphi)
+        print(f"PRN {r.prn}: C/N0 {r.cn0:.2f} cleaned, {ref.cn0:.2f} jammer-free, predicted {want:.2f}, peak ratio {r.peak_ratio:.2f}")
+        assert r.acquired and r.code_index == ref.code_index and abs(r.freq_index - ref.freq_index) <= 1, (r, ref)
+        assert abs(r.cn0 - want) <= cr.E2E_CN0_TOL_DB, (r, ref, want)
+    quiet = 2 * (lead - nfft)                                  # every frame that ends in front of the jammer
+    assert cleaned[:quiet].tobytes() == raw_a[:quiet].tobytes(), "the quiet lead-in comes back byte-identical"
+    assert cleaned[2 * lead:].tobytes() != raw_a[2 * lead:].tobytes()
+
+
+def test_clean_spatial_with_nothing_to_cancel_returns_a_copy(dev):
+    free_a, free_b = cr.e2e_pair(False)
+    head = 2 * er.E2E_LEAD
+    got = mitigate.clean_spatial(dev, free_a[:head], free_b[:head], nfft=cr.E2E_NFFT, frames_per_row=cr.E2E_FRAMES_PER_ROW, lag=0)
+    try:
+        assert not got.cancelled and "copy of main" in got.note and got.bands == [] and got.suppression_db == []
+        assert got.capture.download().tobytes() == free_a[:head].tobytes()
+        assert got.records["total"].tobytes() == got.records["total_in"].tobytes() and not got.weights.any()
+    finally:
+        got.capture.free()
