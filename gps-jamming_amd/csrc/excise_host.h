@@ -1,17 +1,11 @@
-// What the two excisors, k_excise.hip and k_excise_chirp.hip, and the canceller, k_cancel.hip, share besides the transform
-// front end (stft_group.h; those three include this, nothing else does): the geometry their kernels take, the run
-// arithmetic of their launches and the copy of the edges no frame pair covers.  The transform kernels themselves stay
-// apart, each in its own file.
+// The host side the two excisors, k_excise.hip and k_excise_chirp.hip, and the canceller, k_cancel.hip, share (those three
+// include this, nothing else does): the geometry of a call, the refusals all three make in the same words, the run arithmetic
+// of their launches and the copy of the edges no frame pair covers.  Their shared device stages, excise_stages.h, come in
+// through here.  The transform kernels themselves stay apart, each in its own file.
 #pragma once
-#include "stft_group.h"
+#include "excise_stages.h"
 
 namespace gj {
-
-struct ExciseGeom {
-    unsigned long long first_sample, n_frames, per_run;
-    float offset;    // offset of the unpack convention
-    float scale2;    // scale^2: the transform runs on u8 - offset, the powers are scaled to the units of gj_ridge_dev
-};
 
 // the geometry of a call that has passed its checks; per_run is the launch's to fill in (excise_runs)
 inline ExciseGeom excise_geom(const gj_ctx* ctx, size_t first_sample, size_t n_samples, int nfft) {
@@ -22,6 +16,14 @@ inline ExciseGeom excise_geom(const gj_ctx* ctx, size_t first_sample, size_t n_s
     g.offset = 0.5f * (float)ctx->off2;
     g.scale2 = (float)(ctx->scale * ctx->scale);
     return g;
+}
+
+// the refusals the three entry points make in the same words, in the order all three make them
+inline int excise_check_shape(gj_ctx* ctx, const float* d_threshold, const void* d_frames, size_t n_samples, int nfft) {
+    if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
+    if (n_samples < (size_t)nfft) return fail(ctx, GJ_ERR_INVALID, "n_samples %zu is less than one frame of %d points", n_samples, nfft);
+    return GJ_OK;
 }
 
 // One round of transform groups, B to a workgroup: runs of equal length, the length from the frame count alone -- at least

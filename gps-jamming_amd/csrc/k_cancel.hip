@@ -6,9 +6,10 @@
 // (gpsjam/coherence.py, cancel_weights).
 //
 // This is excise_kernel (k_excise.hip) with csd_kernel's two-capture pattern (k_csd.hip) in front, on the front end of
-// stft_group.h and the host side of excise_host.h:
-//   * runs, the priming iteration, the carry of eight c2, the generic exchange schedule at 4096 points, the mask, the
-//     conjugate, the second pass, the overlap-add and the 16-bit stores are excise_kernel's, instruction for instruction:
+// stft_group.h, the device stages of excise_stages.h and the host side of excise_host.h:
+//   * runs with their priming iteration, the group sums, the overlap-add and its 16-bit stores are excise_kernel's text
+//     (excise_stages.h), the carry of eight c2, the generic exchange schedule at 4096 points and the second pass its
+//     structure; the mask loop, with the prediction and a fourth sum, keeps the excisor's arithmetic behind the subtraction:
 //     with every weight 0 the call writes gj_excise_dev's bytes on capture a;
 //   * per frame the group transforms a's frame and keeps its 16 bins in registers, transforms b's frame through the same
 //     LDS buffer (the front end's exchange ends with a barrier behind the gather, so the buffer is free again) and forms
@@ -75,31 +76,24 @@ __global__ __launch_bounds__(kBlockThreads, CancelCfg<N>::min_waves) void cancel
 #pragma unroll
     for (int s = 0; s < 16; ++s) thr[s] = thr_tab[jl + TF * s];
     const c2 koff = make_c2(-g.offset, -g.offset);
-    constexpr float inv_n = 1.0f / (float)N;
 
-    // this group's run: frames [run_first, run_end); iteration 0 primes the carry with the frame in front of it.  Every
-    // group of the grid makes per_run + 1 iterations; a frame index outside the call is clamped, for the samples and for
-    // the weight set alike, and writes nothing.
-    const long long last = (long long)g.n_frames - 1;
-    const long long run_first = (long long)(((unsigned long long)blockIdx.x * B + (unsigned)b) * g.per_run);
-    const long long run_end = run_first + (long long)g.per_run;
-    auto clamped = [&](long long f) { return (unsigned long long)(f < 0 ? 0 : (f > last ? last : f)); };
+    const ExciseRun run(g, blockIdx.x, b, B);   // iteration 0 primes the carry; samples and weight set are clamped alike
     auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, false>(dst, base, jl); };
     const uint8_t* const base_a = iq_a + 2ull * g.first_sample;
     const uint8_t* const base_b = iq_b + 2ull * cg.first_b;
 
     unsigned raw_a[16], raw_b[16];   // the NEXT pair's samples are fetched while the current ones are transformed
-    load_frame(raw_a, base_a + 2ull * (clamped(run_first - 1) * H));
-    load_frame(raw_b, base_b + 2ull * (clamped(run_first - 1) * H));
+    load_frame(raw_a, base_a + 2ull * (run.clamped(run.first - 1) * H));
+    load_frame(raw_b, base_b + 2ull * (run.clamped(run.first - 1) * H));
     c2 carry[8];                     // second half of the previous frame's inverse transform: y_{f-1}[jl + TF (s + 8)]
 #pragma unroll
     for (int s = 0; s < 8; ++s) carry[s] = make_c2(0.f, 0.f);
 
-    for (long long f = run_first - 1; f < run_end; ++f) {
-        const bool owned = f >= run_first && f <= last;
-        const bool more = f + 1 < run_end;   // workgroup-uniform
-        const unsigned long long next_at = clamped(f + 1) * H;
-        unsigned long long set = clamped(f) / cg.frames_per_set;
+    for (long long f = run.first - 1; f < run.end; ++f) {
+        const bool owned = f >= run.first && f <= run.last;
+        const bool more = f + 1 < run.end;   // workgroup-uniform
+        const unsigned long long next_at = run.clamped(f + 1) * H;
+        unsigned long long set = run.clamped(f) / cg.frames_per_set;
         set = set < cg.n_sets ? set : cg.n_sets - 1;
         const float2* wsrc = weights + set * (unsigned long long)N + jl;
 
@@ -131,22 +125,10 @@ __global__ __launch_bounds__(kBlockThreads, CancelCfg<N>::min_waves) void cancel
             cnt += cut ? 1.f : 0.f;        // at most 4096: exact in float
             v[s] = cut ? make_c2(0.f, 0.f) : make_c2(yx, -yy);
         }
-        const auto add = [](float x, float y) { return x + y; };
-        tin = group_reduce_f<S::G>(tin, add);
-        tot = group_reduce_f<S::G>(tot, add);
-        rem = group_reduce_f<S::G>(rem, add);
-        cnt = group_reduce_f<S::G>(cnt, add);
-        if constexpr (WPF > 1) {
-            waves_post(red_in[b], tid, tin);
-            waves_post(red_tot[b], tid, tot);
-            waves_post(red_rem[b], tid, rem);
-            waves_post(red_cnt[b], tid, cnt);
-            __syncthreads();
-            tin = waves_fold(red_in[b], add);
-            tot = waves_fold(red_tot[b], add);
-            rem = waves_fold(red_rem[b], add);
-            cnt = waves_fold(red_cnt[b], add);
-        }
+        const GroupSum<N> s_in{tin, red_in}, s_tot{tot, red_tot}, s_rem{rem, red_rem}, s_cnt{cnt, red_cnt};
+        group_sums_post<N>(b, tid, s_in, s_tot, s_rem, s_cnt);
+        if constexpr (WPF > 1) __syncthreads();
+        group_sums_fold<N>(b, s_in, s_tot, s_rem, s_cnt);
         if (frames && owned && jl == 0) {   // one lane per transform group
             gj_cancel_frame r;
             r.total_in = tin;
@@ -158,21 +140,10 @@ __global__ __launch_bounds__(kBlockThreads, CancelCfg<N>::min_waves) void cancel
 
         stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
 
-        // y_f = conj(v) / N; samples [f H, (f + 1) H) of the range = previous frame's second half + this one's first
         const bool store = owned && f >= 1;
         uint8_t* dst = out + 2ull * ((unsigned long long)(f < 0 ? 0 : f) * H) + 2 * jl;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const float yi = fmaf(v[s].x, inv_n, carry[s].x) + g.offset;
-            const float yq = fmaf(-v[s].y, inv_n, carry[s].y) + g.offset;
-            carry[s] = make_c2(v[s + 8].x * inv_n, -v[s + 8].y * inv_n);
-            if (store) {
-                const unsigned ui = (unsigned)fminf(fmaxf(__builtin_rintf(yi), 0.f), 255.f);
-                const unsigned uq = (unsigned)fminf(fmaxf(__builtin_rintf(yq), 0.f), 255.f);
-                struct __attribute__((packed, aligned(1))) U16 { uint16_t v; };
-                reinterpret_cast<U16*>(dst + 2 * TF * s)->v = (uint16_t)(ui | (uq << 8));
-            }
-        }
+        for (int s = 0; s < 8; ++s) excise_overlap_add<N>(v[s], v[s + 8], carry[s], g.offset, dst + 2 * TF * s, store);
     }
 }
 
@@ -202,9 +173,7 @@ int gj_cancel_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t first
     if (int rc = stft_check_capture(ctx, d_b)) return rc;
     if (frames_per_set == 0 || n_sets == 0) return fail(ctx, GJ_ERR_INVALID, "frames_per_set and n_sets must be >= 1");
     if (reinterpret_cast<uintptr_t>(d_weights) & 7) return fail(ctx, GJ_ERR_INVALID, "weights must be 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
-    if (n_samples < (size_t)nfft) return fail(ctx, GJ_ERR_INVALID, "n_samples %zu is less than one frame of %d points", n_samples, nfft);
+    if (int rc = excise_check_shape(ctx, d_threshold, d_frames, n_samples, nfft)) return rc;
     if (int rc = check_range_and_output(ctx, d_a, nbytes_a, first_a, n_samples, d_out)) return rc;
     if (int rc = check_range_and_output(ctx, d_b, nbytes_b, first_b, n_samples, d_out)) return rc;
     const CancelGeom cg{excise_geom(ctx, first_a, n_samples, nfft), first_b, frames_per_set, n_sets};

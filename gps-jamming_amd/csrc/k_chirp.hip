@@ -5,7 +5,8 @@
 // ridge's four numbers and keeps the rate with the largest peak (gpsjam/classify.py classify_swept reads the result).
 //
 // The front end is stft_group.h, used as ridge_kernel uses it: same workgroup of transform groups, same loads with the
-// next step's prefetch, same passes, same three reductions.  What is the search's own:
+// next step's prefetch, same passes, same three reductions; the frame walk and the host side of the call are ridge_kernel's
+// text (stft_frames.h), the reductions a copy of its text (stft_frames.h says why).  What is the search's own:
 //   * the unpacked, windowed frame stays in registers (held[16]) across the rate loop; every rate multiplies a copy by
 //     c_r and transforms the copy;
 //   * c_r[n] = exp(-i pi m / N^2) with the INTEGER phase m = (q_r n^2) mod 2 N^2.  2 N^2 is a power of two that divides
@@ -30,9 +31,7 @@
 //
 // A translation unit of its own with its own extern "C" entry point, like k_ridge.hip.
 #include "chirp_phase.h"
-#include "stft_group.h"
-
-#include <climits>
+#include "stft_frames.h"
 
 namespace gj {
 
@@ -88,24 +87,19 @@ __global__ __launch_bounds__(kBlockThreads, ChirpCfg<N>::min_waves) void chirp_k
     for (int s = 0; s < 8; ++s) wp[s] = stft_window_pair<N>(wintab, jl0, s);
     const c2 koff = make_c2(g.neg_off, g.neg_off);
 
-    const unsigned long long last = g.n_frames - 1;
-    // a group without a frame (behind the last one) transforms the last frame again: every load stays inside the capture
-    auto frame_base = [&](unsigned long long step) {
-        unsigned long long f = step * B + (unsigned)b;
-        if (f > last) f = last;
-        return iq + 2ull * (g.first_sample + f * g.hop);
+    auto load_frame = [&](unsigned (&dst)[16], unsigned long long step) {
+        stft_load_frame<N, Cfg::wide_load>(dst, frame_base(iq, g, step * B + (unsigned)b), jl0);
     };
-    auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, Cfg::wide_load>(dst, base, jl0); };
 
     unsigned raw[16];   // the NEXT step's samples are fetched while the current ones are transformed
     unsigned long long step = blockIdx.x;   // the grid never exceeds nsteps
-    load_frame(raw, frame_base(step));
+    load_frame(raw, step);
     for (; step < g.nsteps; step += gridDim.x) {
         const unsigned long long f = step * B + (unsigned)b;
-        const bool active = f <= last;
+        const bool active = f <= g.n_frames - 1;
         c2 held[16];   // the windowed frame, input index jl0 + TF s
         stft_unpack_window(held, raw, wp, koff);
-        if (step + gridDim.x < g.nsteps) load_frame(raw, frame_base(step + gridDim.x));   // workgroup-uniform
+        if (step + gridDim.x < g.nsteps) load_frame(raw, step + gridDim.x);   // workgroup-uniform
 
         float best_tot = 0.f, best_peak = 0.f, best_sec = 0.f;
         int best_bin = 0, best_rate = 0;
@@ -219,9 +213,7 @@ __global__ __launch_bounds__(kBlockThreads, ChirpCfg<N>::min_waves) void chirp_k
 
 template <int N>
 static void chirp_launch(gj_ctx* ctx, const uint8_t* d_iq, ChirpGeom g, gj_chirp_frame* d_out, float* d_peaks) {
-    constexpr unsigned long long B = kBlockPoints / N;
-    g.nsteps = (g.n_frames + B - 1) / B;
-    const unsigned grid = stft_one_round_grid(ctx, ChirpCfg<N>::min_waves, g.nsteps);
+    const unsigned grid = frames_one_round<N>(ctx, ChirpCfg<N>::min_waves, g);
     hipLaunchKernelGGL(chirp_kernel<N>, dim3(grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle, window_table(ctx, N),
                        d_out, d_peaks);
 }
@@ -244,24 +236,10 @@ int gj_chirp_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_s
     const long long q_last = (long long)rate_first + (long long)(n_rates - 1) * rate_step;
     if (rate_first < -half || q_last > half)
         return fail(ctx, GJ_ERR_INVALID, "rates %d .. %lld: |q| must not exceed nfft^2 / 2 = %lld", rate_first, q_last, half);
-    if (!d_iq || !d_out) return fail(ctx, GJ_ERR_INVALID, "null buffer");
-    if (int rc = stft_check_capture(ctx, d_iq)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
+    if (int rc = frames_check_buffers(ctx, d_iq, d_out)) return rc;
     if (reinterpret_cast<uintptr_t>(d_peaks) & 3) return fail(ctx, GJ_ERR_INVALID, "d_peaks must be 4-byte aligned");
-    if (hop < 1) return fail(ctx, GJ_ERR_INVALID, "hop must be >= 1");
-    if (guard < 0 || 2 * (long long)guard + 1 >= nfft) return fail(ctx, GJ_ERR_INVALID, "guard must be >= 0 with 2 guard + 1 < nfft");
-    const size_t fit = gj_ridge_frames(nbytes, first_sample, nfft, hop);
-    if (n_frames == 0 || n_frames > fit)
-        return fail(ctx, GJ_ERR_INVALID, "n_frames %zu: 1..%zu frames of %d points fit from sample %zu at hop %zu", n_frames, fit, nfft,
-                    first_sample, hop);
-    ChirpGeom g;
-    g.first_sample = first_sample;
-    g.hop = hop;
-    g.n_frames = n_frames;
-    g.nsteps = 0;
-    g.neg_off = -0.5f * (float)ctx->off2;
-    g.scale2 = (float)(ctx->scale * ctx->scale);
-    g.guard = guard;
+    if (int rc = frames_check_geometry(ctx, nbytes, first_sample, nfft, hop, n_frames, guard)) return rc;
+    ChirpGeom g = frames_geom<ChirpGeom>(ctx, first_sample, hop, n_frames, guard);
     g.rate_first = rate_first;
     g.rate_step = rate_step;
     g.n_rates = n_rates;

@@ -8,8 +8,8 @@
 //   * frames hop by N / 2, and a transform group owns a RUN of consecutive frames that it walks in order.  After the
 //     last pass a thread holds points jl + TF s (TF = N / 16); its slots s and s + 8 are N / 2 apart, so the
 //     overlap-add is prev[s + 8] + cur[s] in registers and eight c2 are carried from frame to frame: no LDS, no atomics;
-//   * a run is primed by transforming the frame in front of it once more, writing nothing: that frame's record and
-//     bytes belong to the run before.  Run boundaries come from the geometry alone (excise_launch);
+//   * a run is primed by transforming the frame in front of it once more (ExciseRun, excise_stages.h).  Run boundaries
+//     come from the geometry alone (excise_launch);
 //   * the inverse transform is the forward passes on the conjugate, IFFT(X) = conj(FFT(conj(X))) / N.  The output
 //     pattern of the forward transform (jl + TF s) is the input pattern pass 0 wants, so the mask and the second
 //     transform run on the registers as they are, with the same twiddle registers;
@@ -24,7 +24,8 @@
 // reproduces the interior bytes and the shared records bit for bit.
 //
 // The first half frame and the tail behind the last whole hop are copied from the input by a second small launch.
-// That copy, the geometry struct and the run arithmetic are excise_host.h, shared with k_excise_chirp.hip.
+// That copy and the run arithmetic are excise_host.h, the stages behind the transform excise_stages.h; k_excise_chirp.hip
+// and k_cancel.hip stand on both too.
 //
 // This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it.
 #include "excise_host.h"
@@ -66,62 +67,33 @@ __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise
 #pragma unroll
     for (int s = 0; s < 16; ++s) thr[s] = thr_tab[jl + TF * s];
     const c2 koff = make_c2(-g.offset, -g.offset);
-    constexpr float inv_n = 1.0f / (float)N;
 
-    // this group's run: frames [run_first, run_end); iteration 0 primes the carry with the frame in front of it.  Every
-    // group of the grid makes per_run + 1 iterations (the barriers of the large sizes are workgroup-wide, and lanes of
-    // one wave must stay together for the DPP steps); a frame index outside the call is clamped and writes nothing.
-    const long long last = (long long)g.n_frames - 1;
-    const long long run_first = (long long)(((unsigned long long)blockIdx.x * B + (unsigned)b) * g.per_run);
-    const long long run_end = run_first + (long long)g.per_run;
-    auto frame_base = [&](long long f) {
-        f = f < 0 ? 0 : (f > last ? last : f);
-        return iq + 2ull * (g.first_sample + (unsigned long long)f * H);
-    };
+    const ExciseRun run(g, blockIdx.x, b, B);   // iteration 0 primes the carry with the frame in front of the run
+    auto frame_base = [&](long long f) { return iq + 2ull * (g.first_sample + run.clamped(f) * H); };
     auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, false>(dst, base, jl); };
 
     unsigned raw[16];   // the NEXT frame's samples are fetched while the current ones are transformed
-    load_frame(raw, frame_base(run_first - 1));
+    load_frame(raw, frame_base(run.first - 1));
     c2 carry[8];        // second half of the previous frame's inverse transform: y_{f-1}[jl + TF (s + 8)]
 #pragma unroll
     for (int s = 0; s < 8; ++s) carry[s] = make_c2(0.f, 0.f);
 
-    for (long long f = run_first - 1; f < run_end; ++f) {
-        const bool owned = f >= run_first && f <= last;
+    for (long long f = run.first - 1; f < run.end; ++f) {
+        const bool owned = f >= run.first && f <= run.last;
         c2 v[16];
         stft_unpack_window(v, raw, wp, koff);
-        if (f + 1 < run_end) load_frame(raw, frame_base(f + 1));   // workgroup-uniform
+        if (f + 1 < run.end) load_frame(raw, frame_base(f + 1));   // workgroup-uniform
 
         stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
 
         // this thread's bins jl + TF s: power, mask, conjugate for the way back
         float tot = 0.f, rem = 0.f, cnt = 0.f;
 #pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            // no contraction here: the compiler otherwise fuses the scaling into the addition to `tot` (one rounding) but
-            // not into the selected addition to `rem` (two), and the two sum differently rounded values -- removed must
-            // equal total, bit for bit, when every bin is excised
-#pragma clang fp contract(off)
-            const float p = __builtin_fmaf(v[s].x, v[s].x, v[s].y * v[s].y) * g.scale2;
-            const bool cut = p > thr[s];   // strict; false for a NaN threshold
-            tot += p;
-            rem += cut ? p : 0.f;
-            cnt += cut ? 1.f : 0.f;        // at most 4096: exact in float
-            v[s] = cut ? make_c2(0.f, 0.f) : make_c2(v[s].x, -v[s].y);
-        }
-        const auto add = [](float a, float c) { return a + c; };
-        tot = group_reduce_f<S::G>(tot, add);
-        rem = group_reduce_f<S::G>(rem, add);
-        cnt = group_reduce_f<S::G>(cnt, add);
-        if constexpr (WPF > 1) {
-            waves_post(red_tot[b], tid, tot);
-            waves_post(red_rem[b], tid, rem);
-            waves_post(red_cnt[b], tid, cnt);
-            __syncthreads();
-            tot = waves_fold(red_tot[b], add);
-            rem = waves_fold(red_rem[b], add);
-            cnt = waves_fold(red_cnt[b], add);
-        }
+        for (int s = 0; s < 16; ++s) excise_mask_bin(v[s], thr[s], g.scale2, tot, rem, cnt);
+        const GroupSum<N> s_tot{tot, red_tot}, s_rem{rem, red_rem}, s_cnt{cnt, red_cnt};
+        group_sums_post<N>(b, tid, s_tot, s_rem, s_cnt);
+        if constexpr (WPF > 1) __syncthreads();
+        group_sums_fold<N>(b, s_tot, s_rem, s_cnt);
         if (frames && owned && jl == 0) {   // one lane per transform group
             gj_excise_frame r;
             r.total = tot;
@@ -133,21 +105,10 @@ __global__ __launch_bounds__(kBlockThreads, ExciseCfg<N>::min_waves) void excise
 
         stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
 
-        // y_f = conj(v) / N; samples [f H, (f + 1) H) of the range = previous frame's second half + this one's first
         const bool store = owned && f >= 1;
         uint8_t* dst = out + 2ull * ((unsigned long long)(f < 0 ? 0 : f) * H) + 2 * jl;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const float yi = fmaf(v[s].x, inv_n, carry[s].x) + g.offset;
-            const float yq = fmaf(-v[s].y, inv_n, carry[s].y) + g.offset;
-            carry[s] = make_c2(v[s + 8].x * inv_n, -v[s + 8].y * inv_n);
-            if (store) {
-                const unsigned ui = (unsigned)fminf(fmaxf(__builtin_rintf(yi), 0.f), 255.f);
-                const unsigned uq = (unsigned)fminf(fmaxf(__builtin_rintf(yq), 0.f), 255.f);
-                struct __attribute__((packed, aligned(1))) U16 { uint16_t v; };
-                reinterpret_cast<U16*>(dst + 2 * TF * s)->v = (uint16_t)(ui | (uq << 8));
-            }
-        }
+        for (int s = 0; s < 8; ++s) excise_overlap_add<N>(v[s], v[s + 8], carry[s], g.offset, dst + 2 * TF * s, store);
     }
 }
 
@@ -177,9 +138,7 @@ int gj_excise_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_
     if (int rc = stft_check_nfft(ctx, nfft)) return rc;
     if (!d_iq || !d_out || !d_threshold) return fail(ctx, GJ_ERR_INVALID, "null buffer");
     if (int rc = stft_check_capture(ctx, d_iq)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
-    if (n_samples < (size_t)nfft) return fail(ctx, GJ_ERR_INVALID, "n_samples %zu is less than one frame of %d points", n_samples, nfft);
+    if (int rc = excise_check_shape(ctx, d_threshold, d_frames, n_samples, nfft)) return rc;
     if (int rc = check_range_and_output(ctx, d_iq, nbytes, first_sample, n_samples, d_out)) return rc;
     const ExciseGeom g = excise_geom(ctx, first_sample, n_samples, nfft);
     stft_dispatch(nfft, [&](auto n) { excise_launch<decltype(n)::value>(ctx, d_iq, g, d_threshold, d_out, d_frames); });

@@ -4,9 +4,9 @@
 // rates it reads.  A sweep that crosses hundreds of bins inside one frame is, behind the de-chirp of its rate, a line of
 // a few bins: the mask takes that line out and the re-chirp puts everything else back where it was.
 //
-// The structure is excise_kernel's, statement for statement: the run of consecutive frames per transform group, the
-// priming iteration, the carry of eight c2, the generic exchange schedule at 4096 points, the records, the edges copy.
-// What is this kernel's own:
+// The structure is excise_kernel's: the run of consecutive frames per transform group with its priming iteration, the
+// mask, the group sums and the overlap-add are the same text (excise_stages.h), and so are the carry of eight c2, the
+// generic exchange schedule at 4096 points, the records and the edges copy.  What is this kernel's own:
 //   * the rate q_f of the frame is read by the transform group with the frame's samples (prefetched with them, clamped
 //     like them), so it is uniform in the group; the priming iteration reads the rate of the frame it primes with;
 //   * c_f[jl + TF s], the thread's sixteen factors, come from chirp_phase.h: exact integer phases, 2 + 16 / min(TF, 16)
@@ -25,7 +25,7 @@
 // Determinism: as excise_kernel, with "its own bytes" read as "its own bytes and its own q".
 //
 // A translation unit of its own with its own extern "C" entry points; the frame count is gj_excise_frames (k_excise.hip, by
-// its declaration in include/gpsjam.h); the geometry struct, the run arithmetic and the edges copy are excise_host.h, which
+// its declaration in include/gpsjam.h); the shared refusals, the run arithmetic and the edges copy are excise_host.h, which
 // gives this translation unit a copy of the edges kernel of its own: a kernel of another translation unit cannot be
 // launched from this one without relocatable device code.
 #include "chirp_phase.h"
@@ -63,63 +63,40 @@ __global__ __launch_bounds__(kBlockThreads, ExciseChirpCfg<N>::min_waves) void e
 #pragma unroll
     for (int s = 0; s < 16; ++s) thr[s] = thr_tab[jl + TF * s];
     const c2 koff = make_c2(-g.offset, -g.offset);
-    constexpr float inv_n = 1.0f / (float)N;
 
-    // this group's run: frames [run_first, run_end); iteration 0 primes the carry with the frame in front of it.  A frame
-    // index outside the call is clamped, for the samples and for the rate alike, and writes nothing.
-    const long long last = (long long)g.n_frames - 1;
-    const long long run_first = (long long)(((unsigned long long)blockIdx.x * B + (unsigned)b) * g.per_run);
-    const long long run_end = run_first + (long long)g.per_run;
-    auto clamped = [&](long long f) { return (unsigned long long)(f < 0 ? 0 : (f > last ? last : f)); };
-    auto frame_base = [&](long long f) { return iq + 2ull * (g.first_sample + clamped(f) * H); };
+    const ExciseRun run(g, blockIdx.x, b, B);   // iteration 0 primes the carry; samples and rate are clamped alike
+    auto frame_base = [&](long long f) { return iq + 2ull * (g.first_sample + run.clamped(f) * H); };
     auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, false>(dst, base, jl); };
 
     unsigned raw[16];   // the NEXT frame's samples and rate are fetched while the current ones are transformed
-    load_frame(raw, frame_base(run_first - 1));
-    unsigned q_next = (unsigned)rate[clamped(run_first - 1)];
+    load_frame(raw, frame_base(run.first - 1));
+    unsigned q_next = (unsigned)rate[run.clamped(run.first - 1)];
     c2 carry[8];        // second half of the previous frame's re-chirped inverse transform
 #pragma unroll
     for (int s = 0; s < 8; ++s) carry[s] = make_c2(0.f, 0.f);
 
-    for (long long f = run_first - 1; f < run_end; ++f) {
-        const bool owned = f >= run_first && f <= last;
+    for (long long f = run.first - 1; f < run.end; ++f) {
+        const bool owned = f >= run.first && f <= run.last;
         c2 v[16], c[16];
         stft_unpack_window(v, raw, wp, koff);
         chirp_factors<N>(c, q_next, jl);
-        if (f + 1 < run_end) {   // workgroup-uniform
+        if (f + 1 < run.end) {   // workgroup-uniform
             load_frame(raw, frame_base(f + 1));
-            q_next = (unsigned)rate[clamped(f + 1)];
+            q_next = (unsigned)rate[run.clamped(f + 1)];
         }
 #pragma unroll
         for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], c[s]);
 
         stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
 
-        // this thread's bins jl + TF s: power, mask, conjugate for the way back (excise_kernel's arithmetic)
+        // this thread's bins jl + TF s: power, mask, conjugate for the way back
         float tot = 0.f, rem = 0.f, cnt = 0.f;
 #pragma unroll
-        for (int s = 0; s < 16; ++s) {
-#pragma clang fp contract(off)
-            const float p = __builtin_fmaf(v[s].x, v[s].x, v[s].y * v[s].y) * g.scale2;
-            const bool cut = p > thr[s];   // strict; false for a NaN threshold
-            tot += p;
-            rem += cut ? p : 0.f;
-            cnt += cut ? 1.f : 0.f;        // at most 4096: exact in float
-            v[s] = cut ? make_c2(0.f, 0.f) : make_c2(v[s].x, -v[s].y);
-        }
-        const auto add = [](float a, float c0) { return a + c0; };
-        tot = group_reduce_f<S::G>(tot, add);
-        rem = group_reduce_f<S::G>(rem, add);
-        cnt = group_reduce_f<S::G>(cnt, add);
-        if constexpr (WPF > 1) {
-            waves_post(red_tot[b], tid, tot);
-            waves_post(red_rem[b], tid, rem);
-            waves_post(red_cnt[b], tid, cnt);
-            __syncthreads();
-            tot = waves_fold(red_tot[b], add);
-            rem = waves_fold(red_rem[b], add);
-            cnt = waves_fold(red_cnt[b], add);
-        }
+        for (int s = 0; s < 16; ++s) excise_mask_bin(v[s], thr[s], g.scale2, tot, rem, cnt);
+        const GroupSum<N> s_tot{tot, red_tot}, s_rem{rem, red_rem}, s_cnt{cnt, red_cnt};
+        group_sums_post<N>(b, tid, s_tot, s_rem, s_cnt);
+        if constexpr (WPF > 1) __syncthreads();
+        group_sums_fold<N>(b, s_tot, s_rem, s_cnt);
         if (frames && owned && jl == 0) {   // one lane per transform group
             gj_excise_frame r;
             r.total = tot;
@@ -131,23 +108,13 @@ __global__ __launch_bounds__(kBlockThreads, ExciseChirpCfg<N>::min_waves) void e
 
         stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
 
-        // y_f = conj(v c_f) / N; samples [f H, (f + 1) H) of the range = previous frame's second half + this one's first
+        // the re-chirp: y_f = conj(v c_f) / N
 #pragma unroll
         for (int s = 0; s < 16; ++s) v[s] = cmul(v[s], c[s]);
         const bool store = owned && f >= 1;
         uint8_t* dst = out + 2ull * ((unsigned long long)(f < 0 ? 0 : f) * H) + 2 * jl;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const float yi = fmaf(v[s].x, inv_n, carry[s].x) + g.offset;
-            const float yq = fmaf(-v[s].y, inv_n, carry[s].y) + g.offset;
-            carry[s] = make_c2(v[s + 8].x * inv_n, -v[s + 8].y * inv_n);
-            if (store) {
-                const unsigned ui = (unsigned)fminf(fmaxf(__builtin_rintf(yi), 0.f), 255.f);
-                const unsigned uq = (unsigned)fminf(fmaxf(__builtin_rintf(yq), 0.f), 255.f);
-                struct __attribute__((packed, aligned(1))) U16 { uint16_t v; };
-                reinterpret_cast<U16*>(dst + 2 * TF * s)->v = (uint16_t)(ui | (uq << 8));
-            }
-        }
+        for (int s = 0; s < 8; ++s) excise_overlap_add<N>(v[s], v[s + 8], carry[s], g.offset, dst + 2 * TF * s, store);
     }
 }
 
@@ -193,9 +160,7 @@ int gj_excise_chirp_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t 
     if (!d_iq || !d_out || !d_threshold || !d_rate) return fail(ctx, GJ_ERR_INVALID, "null buffer");
     if (int rc = stft_check_capture(ctx, d_iq)) return rc;
     if (reinterpret_cast<uintptr_t>(d_rate) & 3) return fail(ctx, GJ_ERR_INVALID, "rates must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
-    if (n_samples < (size_t)nfft) return fail(ctx, GJ_ERR_INVALID, "n_samples %zu is less than one frame of %d points", n_samples, nfft);
+    if (int rc = excise_check_shape(ctx, d_threshold, d_frames, n_samples, nfft)) return rc;
     if (int rc = check_range_and_output(ctx, d_iq, nbytes, first_sample, n_samples, d_out)) return rc;
     const ExciseGeom g = excise_geom(ctx, first_sample, n_samples, nfft);
     stft_dispatch(nfft, [&](auto n) { excise_chirp_launch<decltype(n)::value>(ctx, d_iq, g, d_rate, d_threshold, d_out, d_frames); });

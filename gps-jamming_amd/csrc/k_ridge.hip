@@ -4,7 +4,8 @@
 // cwJammer.py, chirpJammer.py, pulsedJammer.py, broadbandJammer.py; gpsjam/classify.py reads it).
 //
 // The transform front end -- the workgroup of transform groups, the loads, the window, the passes and their exchange
-// barrier, the group reductions -- is stft_group.h, shared with k_excise.hip and k_skurt.hip.  What is the ridge's own:
+// barrier, the group reductions -- is stft_group.h, shared with k_excise.hip and k_skurt.hip; the frame walk and the host
+// side of a call over n_frames frames are stft_frames.h, shared with k_chirp.hip.  What is the ridge's own:
 //   * a frame starts at first_sample + f * hop, any hop: a frame is only 2-byte aligned and has no fixed relation to
 //     its neighbours, so nothing is carried from step to step and every address is a 64-bit frame base + constants;
 //   * no mean removal (pulsedJammer.py's carrier sits at 0 Hz) and no PSD scaling: P[k] = |X[k]|^2 in sample units;
@@ -18,9 +19,7 @@
 //
 // This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it
 // (tests/hip_stub builds those by name), and K2's module is compiled exactly as before.
-#include "stft_group.h"
-
-#include <climits>
+#include "stft_frames.h"
 
 namespace gj {
 
@@ -67,24 +66,19 @@ __global__ __launch_bounds__(kBlockThreads, RidgeCfg<N>::min_waves) void ridge_k
     for (int s = 0; s < 8; ++s) wp[s] = stft_window_pair<N>(wintab, jl0, s);
     const c2 koff = make_c2(g.neg_off, g.neg_off);
 
-    const unsigned long long last = g.n_frames - 1;
-    // a group without a frame (behind the last one) transforms the last frame again: every load stays inside the capture
-    auto frame_base = [&](unsigned long long step) {
-        unsigned long long f = step * B + (unsigned)b;
-        if (f > last) f = last;
-        return iq + 2ull * (g.first_sample + f * g.hop);
+    auto load_frame = [&](unsigned (&dst)[16], unsigned long long step) {
+        stft_load_frame<N, Cfg::wide_load>(dst, frame_base(iq, g, step * B + (unsigned)b), jl0);
     };
-    auto load_frame = [&](unsigned (&dst)[16], const uint8_t* base) { stft_load_frame<N, Cfg::wide_load>(dst, base, jl0); };
 
     unsigned raw[16];   // the NEXT step's samples are fetched while the current ones are transformed
     unsigned long long step = blockIdx.x;   // the grid never exceeds nsteps
-    load_frame(raw, frame_base(step));
+    load_frame(raw, step);
     for (; step < g.nsteps; step += gridDim.x) {
         const unsigned long long f = step * B + (unsigned)b;
-        const bool active = f <= last;
+        const bool active = f <= g.n_frames - 1;
         c2 v[16];
         stft_unpack_window(v, raw, wp, koff);
-        if (step + gridDim.x < g.nsteps) load_frame(raw, frame_base(step + gridDim.x));   // workgroup-uniform
+        if (step + gridDim.x < g.nsteps) load_frame(raw, step + gridDim.x);   // workgroup-uniform
 
         if constexpr (XP) stft_passes_x4096(v, lds0, tid, tw, ktw);
         else stft_passes<N, 0>(v, lds0, b * lds_span(N), jl, tw, ktw);
@@ -145,9 +139,7 @@ __global__ __launch_bounds__(kBlockThreads, RidgeCfg<N>::min_waves) void ridge_k
 
 template <int N>
 static void ridge_launch(gj_ctx* ctx, const uint8_t* d_iq, RidgeGeom g, gj_ridge_frame* d_out) {
-    constexpr unsigned long long B = kBlockPoints / N;
-    g.nsteps = (g.n_frames + B - 1) / B;
-    const unsigned grid = stft_one_round_grid(ctx, RidgeCfg<N>::min_waves, g.nsteps);
+    const unsigned grid = frames_one_round<N>(ctx, RidgeCfg<N>::min_waves, g);
     hipLaunchKernelGGL(ridge_kernel<N>, dim3(grid), dim3(kBlockThreads), 0, ctx->stream, d_iq, g, ctx->d_twiddle, window_table(ctx, N),
                        d_out);
 }
@@ -169,23 +161,9 @@ int gj_ridge_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_s
     if (!ctx) return GJ_ERR_INVALID;
     Guard lock(ctx);
     if (int rc = stft_check_nfft(ctx, nfft)) return rc;
-    if (!d_iq || !d_out) return fail(ctx, GJ_ERR_INVALID, "null buffer");
-    if (int rc = stft_check_capture(ctx, d_iq)) return rc;
-    if (reinterpret_cast<uintptr_t>(d_out) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
-    if (hop < 1) return fail(ctx, GJ_ERR_INVALID, "hop must be >= 1");
-    if (guard < 0 || 2 * (long long)guard + 1 >= nfft) return fail(ctx, GJ_ERR_INVALID, "guard must be >= 0 with 2 guard + 1 < nfft");
-    const size_t fit = gj_ridge_frames(nbytes, first_sample, nfft, hop);
-    if (n_frames == 0 || n_frames > fit)
-        return fail(ctx, GJ_ERR_INVALID, "n_frames %zu: 1..%zu frames of %d points fit from sample %zu at hop %zu", n_frames, fit, nfft,
-                    first_sample, hop);
-    RidgeGeom g;
-    g.first_sample = first_sample;
-    g.hop = hop;
-    g.n_frames = n_frames;
-    g.nsteps = 0;
-    g.neg_off = -0.5f * (float)ctx->off2;
-    g.scale2 = (float)(ctx->scale * ctx->scale);
-    g.guard = guard;
+    if (int rc = frames_check_buffers(ctx, d_iq, d_out)) return rc;
+    if (int rc = frames_check_geometry(ctx, nbytes, first_sample, nfft, hop, n_frames, guard)) return rc;
+    const RidgeGeom g = frames_geom<RidgeGeom>(ctx, first_sample, hop, n_frames, guard);
     stft_dispatch(nfft, [&](auto n) { ridge_launch<decltype(n)::value>(ctx, d_iq, g, d_out); });
     GJ_LAUNCH_CHECK(ctx);
     return GJ_OK;

@@ -221,26 +221,24 @@ class FineCorr(NamedTuple):
     n_samples: int
 
 
-class Ridge:
-    """The short-time spectral ridge of a capture (``Device.ridge``; gj_ridge_frame, include/gpsjam.h): per frame the
-    total power, the peak |X[k]|^2, the largest value outside the guard band around the peak and the peak's bin, as
-    the numpy structured array ``records`` (RIDGE_DTYPE) plus the geometry they were computed with.  Frame f starts
-    at sample ``first_sample + f * hop``.  ``ridge[a:b]`` is the Ridge of those frames."""
+class _FrameRecords:
+    """What ``Ridge`` and ``ChirpScan`` share: the records, the frames' geometry, slicing by frame and the ridge's four
+    numbers.  A subclass names its dtype and the word of its slicing errors (``_as``) and builds a slice (``_sliced``)."""
 
     def __init__(self, records, nfft: int, hop: int, first_sample: int = 0, guard: int = 2):
-        self.records = np.ascontiguousarray(records, dtype=RIDGE_DTYPE).reshape(-1)
+        self.records = np.ascontiguousarray(records, dtype=self._dtype).reshape(-1)
         self.nfft, self.hop, self.first_sample, self.guard = int(nfft), int(hop), int(first_sample), int(guard)
 
     def __len__(self) -> int:
         return self.records.size
 
-    def __getitem__(self, key) -> "Ridge":
+    def __getitem__(self, key):
         if not isinstance(key, slice):
-            raise TypeError("a Ridge is sliced by frame: ridge[a:b]")
+            raise TypeError(f"a {type(self).__name__} is sliced by frame: {self._as}[a:b]")
         start, _, step = key.indices(len(self))
         if step != 1:
-            raise ValueError("a Ridge keeps consecutive frames: the step must be 1")
-        return Ridge(self.records[key], self.nfft, self.hop, self.first_sample + start * self.hop, self.guard)
+            raise ValueError(f"a {type(self).__name__} keeps consecutive frames: the step must be 1")
+        return self._sliced(key, self.first_sample + start * self.hop)
 
     total = property(lambda self: self.records["total"])
     peak = property(lambda self: self.records["peak"])
@@ -249,9 +247,21 @@ class Ridge:
 
     @property
     def concentration(self) -> np.ndarray:
-        """peak / total: the share of each frame's power in its peak bin (0 for an empty frame)."""
+        """peak / total: the share of each frame's power in its peak bin (0 for an empty frame); for a ChirpScan at the
+        best rate, in its de-chirped peak bin."""
         t = self.total.astype(np.float64)
         return np.divide(self.peak, t, out=np.zeros(t.shape), where=t > 0)
+
+
+class Ridge(_FrameRecords):
+    """The short-time spectral ridge of a capture (``Device.ridge``; gj_ridge_frame, include/gpsjam.h): per frame the
+    total power, the peak |X[k]|^2, the largest value outside the guard band around the peak and the peak's bin, as
+    the numpy structured array ``records`` (RIDGE_DTYPE) plus the geometry they were computed with.  Frame f starts
+    at sample ``first_sample + f * hop``.  ``ridge[a:b]`` is the Ridge of those frames."""
+    _dtype, _as = RIDGE_DTYPE, "ridge"
+
+    def _sliced(self, key, first_sample) -> "Ridge":
+        return Ridge(self.records[key], self.nfft, self.hop, first_sample, self.guard)
 
     def freq_hz(self, fs: float = 2.048e6) -> np.ndarray:
         """Signed frequency of peak_bin: bins from nfft/2 on are negative frequencies."""
@@ -262,50 +272,32 @@ CHIRP_DTYPE = np.dtype([("total", np.float32), ("peak", np.float32), ("second", 
                         ("rate_index", np.int32), ("reserved", np.int32)])
 
 
-class ChirpScan:
+class ChirpScan(_FrameRecords):
     """The chirp-rate search of a capture (``Device.chirp``; gj_chirp_frame, include/gpsjam.h): per frame the ridge's four
     numbers behind the de-chirp that concentrates the frame best, and which rate that was, as the numpy structured array
     ``records`` (CHIRP_DTYPE) plus the geometry and the rate grid ``rates = (first, step, n)`` they were computed with.
     Rates count bins per frame length: one unit is fs^2 / nfft^2 Hz/s.  ``peaks``: the peak of every frame at every
     rate, ``[frames, n]``, or None.  Frame f starts at sample ``first_sample + f * hop``; ``scan[a:b]`` is the
     ChirpScan of those frames."""
+    _dtype, _as = CHIRP_DTYPE, "scan"
 
     def __init__(self, records, nfft: int, hop: int, rates, first_sample: int = 0, guard: int = 2, peaks=None):
-        self.records = np.ascontiguousarray(records, dtype=CHIRP_DTYPE).reshape(-1)
-        self.nfft, self.hop, self.first_sample, self.guard = int(nfft), int(hop), int(first_sample), int(guard)
+        super().__init__(records, nfft, hop, first_sample, guard)
         self.rates = tuple(int(v) for v in rates)
         if len(self.rates) != 3:
             raise ValueError("rates is (first, step, n)")
         self.peaks = None if peaks is None else np.ascontiguousarray(peaks, dtype=np.float32).reshape(self.records.size, self.rates[2])
 
-    def __len__(self) -> int:
-        return self.records.size
-
-    def __getitem__(self, key) -> "ChirpScan":
-        if not isinstance(key, slice):
-            raise TypeError("a ChirpScan is sliced by frame: scan[a:b]")
-        start, _, step = key.indices(len(self))
-        if step != 1:
-            raise ValueError("a ChirpScan keeps consecutive frames: the step must be 1")
-        return ChirpScan(self.records[key], self.nfft, self.hop, self.rates, self.first_sample + start * self.hop, self.guard,
+    def _sliced(self, key, first_sample) -> "ChirpScan":
+        return ChirpScan(self.records[key], self.nfft, self.hop, self.rates, first_sample, self.guard,
                          None if self.peaks is None else self.peaks[key])
 
-    total = property(lambda self: self.records["total"])
-    peak = property(lambda self: self.records["peak"])
-    second = property(lambda self: self.records["second"])
-    peak_bin = property(lambda self: self.records["peak_bin"])
     rate_index = property(lambda self: self.records["rate_index"])
 
     @property
     def rate(self) -> np.ndarray:
         """The q of each frame's rate_index, in bins per frame length."""
         return self.rates[0] + self.rates[1] * self.rate_index.astype(np.int64)
-
-    @property
-    def concentration(self) -> np.ndarray:
-        """peak / total at the best rate: the share of each frame's power in its de-chirped peak bin (0 for an empty frame)."""
-        t = self.total.astype(np.float64)
-        return np.divide(self.peak, t, out=np.zeros(t.shape), where=t > 0)
 
     def sweep_hz_per_s(self, fs: float = 2.048e6) -> np.ndarray:
         """Each frame's best rate in Hz/s: q fs^2 / nfft^2."""
@@ -315,6 +307,15 @@ class ChirpScan:
         """Signed frequency of the de-chirped line at the CENTRE of each frame: bin + q / 2, wrapped to [-fs/2, fs/2)."""
         k = self.peak_bin.astype(np.float64) + 0.5 * self.rate
         return ((k + self.nfft / 2.0) % self.nfft - self.nfft / 2.0) * (float(fs) / self.nfft)
+
+
+def _frames_to_compute(n_frames: Optional[int], nbytes: int, first_sample: int, nfft: int, hop: int):
+    """(n_frames, empty): a given frame count as it is, None means all that fit (``ridge_frames``).  ``empty``: none does
+    although the library takes nfft and hop, so the answer is the result without frames and nothing is launched."""
+    if n_frames is not None:
+        return n_frames, False
+    n_frames = ridge_frames(nbytes, first_sample, nfft, hop)
+    return n_frames, n_frames == 0 and 16 <= int(nfft) <= 4096 and hop >= 1
 
 
 def _row_args_fit(nfft: int, frames_per_row: int, *sizes: int) -> bool:
@@ -1020,10 +1021,9 @@ class Device:
         ``raw``: host bytes (uploaded once, like a ``Capture``) or a resident ``Capture``.  16 bytes per frame come back."""
         hop = int(nfft) // 2 if hop is None else int(hop)
         with self._resident(raw) as cap:
-            if n_frames is None:
-                n_frames = ridge_frames(cap.nbytes, first_sample, nfft, hop)
-                if n_frames == 0 and 16 <= int(nfft) <= 4096 and hop >= 1:
-                    return Ridge(np.empty(0, RIDGE_DTYPE), nfft, hop, first_sample, guard)
+            n_frames, empty = _frames_to_compute(n_frames, cap.nbytes, first_sample, nfft, hop)
+            if empty:
+                return Ridge(np.empty(0, RIDGE_DTYPE), nfft, hop, first_sample, guard)
             self._count("ridge")
             with DevBuf(self, max(int(n_frames), 1) * RIDGE_DTYPE.itemsize) as out:
                 self.ridge_dev(cap, cap.nbytes, first_sample, nfft, hop, n_frames, guard, out)
@@ -1040,11 +1040,10 @@ class Device:
         hop = nfft // 2 if hop is None else int(hop)
         first, step, n = (int(v) for v in rates)
         with self._resident(raw) as cap:
-            if n_frames is None:
-                n_frames = ridge_frames(cap.nbytes, first_sample, nfft, hop)
-                if n_frames == 0 and 16 <= nfft <= 4096 and hop >= 1 and 1 <= n <= _ffi.GJ_CHIRP_MAX_RATES:
-                    return ChirpScan(np.empty(0, CHIRP_DTYPE), nfft, hop, (first, step, n), first_sample, guard,
-                                     np.empty((0, n), np.float32) if want_peaks else None)
+            n_frames, empty = _frames_to_compute(n_frames, cap.nbytes, first_sample, nfft, hop)
+            if empty and 1 <= n <= _ffi.GJ_CHIRP_MAX_RATES:
+                return ChirpScan(np.empty(0, CHIRP_DTYPE), nfft, hop, (first, step, n), first_sample, guard,
+                                 np.empty((0, n), np.float32) if want_peaks else None)
             n_frames = int(n_frames)
             self._count("chirp")
             with DevBuf(self, max(n_frames, 1) * CHIRP_DTYPE.itemsize) as out, \
