@@ -1,7 +1,7 @@
-// The host side the two excisors, k_excise.hip and k_excise_chirp.hip, and the canceller, k_cancel.hip, share (those three
-// include this, nothing else does): the geometry of a call, the refusals all three make in the same words, the run arithmetic
-// of their launches and the copy of the edges no frame pair covers.  Their shared device stages, excise_stages.h, come in
-// through here.  The transform kernels themselves stay apart, each in its own file.
+// The host side the two excisors, k_excise.hip and k_excise_chirp.hip, and the two cancellers, k_cancel.hip and k_cancel2.hip,
+// share (those four include this, nothing else does): the geometry of a call, the refusals all four make in the same words,
+// the run arithmetic of their launches and the copy of the edges no frame pair covers.  Their shared device stages,
+// excise_stages.h, come in through here.  The transform kernels themselves stay apart, each in its own file.
 #pragma once
 #include "excise_stages.h"
 
@@ -18,7 +18,7 @@ inline ExciseGeom excise_geom(const gj_ctx* ctx, size_t first_sample, size_t n_s
     return g;
 }
 
-// the refusals the three entry points make in the same words, in the order all three make them
+// the refusals the four entry points make in the same words, in the order all four make them
 inline int excise_check_shape(gj_ctx* ctx, const float* d_threshold, const void* d_frames, size_t n_samples, int nfft) {
     if (reinterpret_cast<uintptr_t>(d_threshold) & 3) return fail(ctx, GJ_ERR_INVALID, "thresholds must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_frames) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");

@@ -1,9 +1,10 @@
-// The device stages excise_kernel (k_excise.hip), excise_chirp_kernel (k_excise_chirp.hip) and cancel_kernel (k_cancel.hip)
-// share behind the front end of stft_group.h: their geometry, a group's run of frames, the excisors' mask on a bin, the group
-// sums of a frame's record and the overlap-add of an output pair.  These fix the bits of records and output, so each stands
-// once: "W = 0" and "rate 0" write gj_excise_dev's bytes because the kernels inline the same text.  Included through
-// excise_host.h only.  No helper holds a barrier (as stft_group.h) or a loop over a thread's bins: one element per call, like
-// stft_window_pair -- the loops written in here compiled to other registers and branches (profiles/NOTES_stages.md).
+// The device stages excise_kernel (k_excise.hip), excise_chirp_kernel (k_excise_chirp.hip), cancel_kernel (k_cancel.hip) and
+// cancel2_kernel (k_cancel2.hip) share behind the front end of stft_group.h: their geometry, a group's run of frames, the
+// excisors' mask on a bin, the cancellers' prediction on a bin, the group sums of a frame's record and the overlap-add of an
+// output pair.  These fix the bits of records and output, so each stands once: "W = 0" and "rate 0" write gj_excise_dev's
+// bytes because the kernels inline the same text.  Included through excise_host.h only.  No helper holds a barrier (as
+// stft_group.h) or a loop over a thread's bins: one element per call, like stft_window_pair -- the loops written in here
+// compiled to other registers and branches (profiles/NOTES_stages.md).
 #pragma once
 #include "stft_group.h"
 
@@ -43,6 +44,14 @@ __device__ __forceinline__ void excise_mask_bin(c2& v, float thr, float scale2, 
     rem += cut ? p : 0.f;
     cnt += cut ? 1.f : 0.f;     // at most 4096: exact in float
     v = cut ? make_c2(0.f, 0.f) : make_c2(v.x, -v.y);
+}
+
+// The cancellers' prediction on one bin (k_cancel.hip, k_cancel2.hip): W B with every product rounded on its own, never
+// contracted: what a complex64 multiplication on the host computes, and exactly 0 for W = 0 and exactly B for W = (1, 0)
+__device__ __forceinline__ c2 cancel_predict(c2 w, c2 b) {
+#pragma clang fp contract(off)
+    const float pr = w.x * b.x, qr = w.y * b.y, pi = w.x * b.y, qi = w.y * b.x;
+    return make_c2(pr - qr, pi + qi);
 }
 
 // The sums of a frame's record over its transform group, in every lane: the lane ladders, then where the group spans waves

@@ -43,14 +43,6 @@ struct CancelGeom {
     unsigned long long first_b, frames_per_set, n_sets;
 };
 
-// W B with every product rounded on its own, never contracted: what a complex64 multiplication on the host computes, and
-// exactly 0 for W = 0 and exactly B for W = (1, 0)
-__device__ __forceinline__ c2 cancel_predict(c2 w, c2 b) {
-#pragma clang fp contract(off)
-    const float pr = w.x * b.x, qr = w.y * b.y, pi = w.x * b.y, qi = w.y * b.x;
-    return make_c2(pr - qr, pi + qi);
-}
-
 template <int N>
 __global__ __launch_bounds__(kBlockThreads, CancelCfg<N>::min_waves) void cancel_kernel(
     const uint8_t* __restrict__ iq_a, const uint8_t* __restrict__ iq_b, CancelGeom cg, const cf* __restrict__ twtab,

@@ -1,6 +1,6 @@
-// The short-time transform front end of k_ridge.hip, k_excise.hip, k_skurt.hip, k_chirp.hip, k_excise_chirp.hip, k_csd.hip
-// and k_cancel.hip (those seven include it through stft_frames.h, excise_stages.h or stft_rows.h).  The transform is K2's
-// (k_welch.hip): one 256-thread workgroup holds 4096 / N transform groups of N / 16 threads,
+// The short-time transform front end of k_ridge.hip, k_excise.hip, k_skurt.hip, k_chirp.hip, k_excise_chirp.hip, k_csd.hip,
+// k_cancel.hip and k_cancel2.hip (those eight include it through stft_frames.h, excise_stages.h or stft_rows.h).  The
+// transform is K2's (k_welch.hip): one 256-thread workgroup holds 4096 / N transform groups of N / 16 threads,
 // every thread pulls its 16 samples straight from the uint8 stream, applies unpack and the periodic Hann window of K2's
 // table and runs the register-resident Stockham passes of fft_core.h with LDS exchanges.  Unlike K2's segments a frame may
 // start at any sample, so it is only 2-byte aligned, and there is one LDS buffer with two barriers per exchange.

@@ -1169,6 +1169,41 @@ class Device:
                 cap_a, cap_a.nbytes, first_a, cap_b, cap_b.nbytes, first_b, n_samples, nfft, d_w, frames_per_set, n_sets,
                 thr, d_out, d_rec))
 
+    def cancel2(self, a, b, c, weights, threshold=None, nfft: int = 1024, first_a: int = 0, first_b: int = 0,
+                first_c: int = 0, n_samples: Optional[int] = None, frames_per_set: Optional[int] = None):
+        """Three-antenna per-bin cancellation (gj_cancel2_dev): ``cancel`` with two auxiliaries.  From every bin of every
+        nfft-point frame of ``a`` at first_a, ``W1[k] * B_f[k]`` and then ``W2[k] * C_f[k]`` are subtracted, B_f and C_f
+        being the frames of ``b`` at first_b and of ``c`` at first_c; n_samples defaults to as many as all three captures
+        hold.  ``a``, ``b`` and ``c``: host bytes (uploaded once each) or resident ``Capture``s.  ``weights``:
+        complex64[2][nfft] (one set: W1, W2) or complex64[n_sets][2][nfft] in FFT order
+        (``gpsjam.coherence.cancel_weights2`` builds them); sets, ``frames_per_set``, ``threshold`` and the result
+        ``(cleaned, records)`` as ``cancel``."""
+        nfft, first_a, first_b, first_c = int(nfft), int(first_a), int(first_b), int(first_c)
+        w = np.asarray(weights)
+        if w.ndim not in (2, 3) or w.shape[-2:] != (2, nfft) or w.size == 0:
+            raise ValueError(f"weights must be complex64[2][{nfft}] or [n_sets][2][{nfft}], not {w.shape}")
+        w = np.ascontiguousarray(w.reshape(-1, 2, nfft), np.complex64)
+        n_sets = w.shape[0]
+        with contextlib.ExitStack() as temps:
+            cap_a = temps.enter_context(self._resident(a))
+            cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
+            cap_c = cap_a if c is a else cap_b if c is b else temps.enter_context(self._resident(c))
+            if n_samples is None:
+                n_samples = max(0, min(cap_a.nsamples - first_a, cap_b.nsamples - first_b, cap_c.nsamples - first_c))
+            n_samples = int(n_samples)
+            frames = excise_frames(n_samples, nfft)
+            if frames_per_set is None:
+                if n_sets > 1:
+                    raise ValueError(f"{n_sets} weight sets need frames_per_set")
+                frames_per_set = max(frames, 1)
+            thr = np.full(nfft, np.inf, np.float32) if threshold is None else threshold
+            thr = self._on_device(temps, thr, np.float32, nfft, "threshold", f"nfft is {nfft}")
+            d_w = self._on_device(temps, w.view(np.float32), np.float32, 4 * n_sets * nfft, "weights", "")
+            self._count("cancel2")
+            return self._cleaned(n_samples, frames, CANCEL_DTYPE, lambda d_out, d_rec: self.cancel2_dev(
+                cap_a, cap_a.nbytes, first_a, cap_b, cap_b.nbytes, first_b, cap_c, cap_c.nbytes, first_c, n_samples, nfft,
+                d_w, frames_per_set, n_sets, thr, d_out, d_rec))
+
     def blank(self, raw, threshold: float, window: int = 16, guard: int = 8, first_sample: int = 0,
               n_samples: Optional[int] = None):
         """Time-domain pulse blanking (gj_blank_dev): samples first_sample .. + n_samples of ``raw`` (default: to the
@@ -1245,6 +1280,15 @@ class Device:
         self._check(self._lib.gj_cancel_dev(self._ctx, _ptr(d_a), int(nbytes_a), int(first_a), _ptr(d_b), int(nbytes_b),
                                             int(first_b), int(n_samples), int(nfft), _ptr(d_weights), int(frames_per_set),
                                             int(n_sets), _ptr(d_threshold), _ptr(d_out), _ptr(d_frames) or None))
+
+    def cancel2_dev(self, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, d_c, nbytes_c, first_c, n_samples, nfft, d_weights,
+                    frames_per_set, n_sets, d_threshold, d_out, d_frames=None):
+        """gj_cancel2_dev: gj_cancel_dev with a third capture and the float32[n_sets][2][nfft][2] weights (W1, then W2, of
+        every set) in d_weights, on the context's stream."""
+        self._check(self._lib.gj_cancel2_dev(self._ctx, _ptr(d_a), int(nbytes_a), int(first_a), _ptr(d_b), int(nbytes_b),
+                                             int(first_b), _ptr(d_c), int(nbytes_c), int(first_c), int(n_samples), int(nfft),
+                                             _ptr(d_weights), int(frames_per_set), int(n_sets), _ptr(d_threshold), _ptr(d_out),
+                                             _ptr(d_frames) or None))
 
     def excise_dev(self, d_iq, nbytes, first_sample, n_samples, nfft, d_threshold, d_out, d_frames=None):
         """gj_excise_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 16-byte record (EXCISE_DTYPE) per

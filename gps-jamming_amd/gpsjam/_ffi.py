@@ -229,6 +229,7 @@ SIGNATURES = {
     "gj_excise_chirp_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp]),
     "gj_chirp_rates_dev": (_i, [_vp, _vp, _sz, _i, _i, _f, _vp]),
     "gj_cancel_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "gj_cancel2_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _vp, _sz, _sz, _sz, _i, _vp, _sz, _sz, _vp, _vp, _vp]),
     "gj_blank_blocks": (_sz, [_sz]),
     "gj_blank_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _f, _vp, _vp]),
     "gj_byte_histogram_dev": (_i, [_vp, _vp, _sz, _sz, _i, _i, _vp]),

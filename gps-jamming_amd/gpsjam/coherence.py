@@ -25,7 +25,9 @@ Limits:
 prints the coherent bands and their delays.
 
 What is found can be taken out: ``cancel_weights`` turns the sums into the per-bin weights of the two-antenna canceller
-(``Device.cancel``, gj_cancel_dev; ``gpsjam.mitigate.clean_spatial`` joins the two).
+(``Device.cancel``, gj_cancel_dev; ``gpsjam.mitigate.clean_spatial`` joins the two).  With a third antenna,
+``spectral_matrix`` takes the sums of the three pairs and ``cancel_weights2`` solves the 2 x 2 system per cell for the
+two weights of the three-antenna canceller (``Device.cancel2``, gj_cancel2_dev; ``gpsjam.mitigate.clean_spatial2``).
 
 Nothing here computes on the CPU but the decisions on the rows x nfft numbers.
 """
@@ -36,7 +38,7 @@ from typing import List, NamedTuple, Optional
 
 import numpy as np
 
-from . import CrossSpectrum, _bands
+from . import CrossSpectrum, _bands, csd_rows
 
 K5_SAMPLES = 65536          # the slice ``scan(lag="k5")`` hands to K5
 
@@ -121,6 +123,88 @@ def cancel_weights(result: CrossSpectrum, detection: Detection, per_row: bool = 
     use = flagged & (sbb > 0) & np.isfinite(sbb) & np.isfinite(sab)
     w = np.zeros(sab.shape, np.complex128)
     w[use] = np.conj(sab[use]) / sbb[use]
+    return w.astype(np.complex64)
+
+
+class SpectralMatrix(NamedTuple):
+    """The sums of a capture triple over the same rows (``spectral_matrix``): ``ab.sab`` = sum B conj(A), ``ac.sab`` =
+    sum C conj(A), ``bc.sab`` = sum C conj(B); Saa = ``ab.saa``, Sbb = ``ab.sbb``, Scc = ``ac.sbb``."""
+    ab: CrossSpectrum
+    ac: CrossSpectrum
+    bc: CrossSpectrum
+    lags: tuple                 # the integer lags (b, c) the auxiliaries were aligned by
+
+
+def spectral_matrix(dev, main, aux_b, aux_c, lags=(0, 0), nfft: int = 256, frames_per_row: int = 1024,
+                    hop: Optional[int] = None) -> SpectralMatrix:
+    """The per-bin 3 x 3 spectral matrix of a capture triple: three ``dev.cross_spectrum`` calls, (a,b), (a,c) and (b,c),
+    over the same rows of the range all three captures hold.  ``lags``: the integer samples by which each auxiliary lags
+    main, or "k5" for K5's integer lag of the first K5_SAMPLES samples of each pair; the triple is aligned by them first.
+    Host bytes are uploaded once each.  Three pair calls cost six transforms per frame triple where three would do."""
+    nfft, m = int(nfft), int(frames_per_row)
+    hop = nfft if hop is None else int(hop)
+    with contextlib.ExitStack() as temps:
+        cap_a = temps.enter_context(dev._resident(main))
+        cap_b = cap_a if aux_b is main else temps.enter_context(dev._resident(aux_b))
+        cap_c = cap_a if aux_c is main else cap_b if aux_c is aux_b else temps.enter_context(dev._resident(aux_c))
+        if isinstance(lags, str):
+            if lags != "k5":
+                raise ValueError(f'lags must be two integers or "k5", not {lags!r}')
+            lag_b, lag_c = _k5_lag(dev, cap_a, cap_b), _k5_lag(dev, cap_a, cap_c)
+        else:
+            lag_b, lag_c = (int(v) for v in lags)
+        first_a = max(0, -lag_b, -lag_c)
+        first_b, first_c = first_a + lag_b, first_a + lag_c
+        rows = min(csd_rows(cap_a.nbytes, first_a, cap_b.nbytes, first_b, nfft, hop, m),
+                   csd_rows(cap_a.nbytes, first_a, cap_c.nbytes, first_c, nfft, hop, m))
+        if rows == 0:
+            none = np.empty((0, nfft), np.float32)
+            return SpectralMatrix(CrossSpectrum(none, none, none, none, nfft, hop, m, first_a, first_b),
+                                  CrossSpectrum(none, none, none, none, nfft, hop, m, first_a, first_c),
+                                  CrossSpectrum(none, none, none, none, nfft, hop, m, first_b, first_c), (lag_b, lag_c))
+        pair = lambda x, y, fx, fy: dev.cross_spectrum(x, y, nfft=nfft, hop=hop, frames_per_row=m, first_a=fx, first_b=fy,
+                                                       n_rows=rows)
+        return SpectralMatrix(pair(cap_a, cap_b, first_a, first_b), pair(cap_a, cap_c, first_a, first_c),
+                              pair(cap_b, cap_c, first_b, first_c), (lag_b, lag_c))
+
+
+def cancel_weights2(matrix: SpectralMatrix, flagged, loading: float = 1e-6) -> np.ndarray:
+    """The per-cell MMSE weights of the three-antenna canceller (``Device.cancel2`` subtracts W1 B and W2 C from A):
+    complex64[n_rows][2][nfft], W1 and W2 of every row, solved in float64 from the row's own sums
+
+        W1 Sbb       + W2 Sbc = conj(Sab)
+        W1 conj(Sbc) + W2 Scc = conj(Sac)            Sxy = sum Y conj(X)
+
+    in the ``flagged`` cells (bool[n_rows][nfft] or bool[nfft]), exactly 0 elsewhere.  Where det = Sbb Scc - |Sbc|^2 is
+    not finite or <= ``loading`` Sbb Scc -- the auxiliaries see the same thing, ``aux_c is aux_b`` included -- the cell
+    falls back to the single weight conj(Sax) / Sxx of the auxiliary more coherent with a, the other weight exactly 0;
+    where neither auxiliary is usable (Sxx = 0 or a sum that is not finite) both are 0."""
+    ab, ac, bc = matrix.ab, matrix.ac, matrix.bc
+    sab, sac, sbc = (r.sab.astype(np.complex128) for r in (ab, ac, bc))
+    sbb, scc = ab.sbb.astype(np.float64), ac.sbb.astype(np.float64)
+    flagged = np.asarray(flagged, bool)
+    if flagged.shape not in ((ab.nfft,), sab.shape) or sac.shape != sab.shape or sbc.shape != sab.shape:
+        raise ValueError(f"flags of shape {flagged.shape} do not fit {sab.shape[0]} rows of {ab.nfft} bins")
+    flagged = np.broadcast_to(flagged, sab.shape)
+    with np.errstate(all="ignore"):
+        ok_b = (sbb > 0) & np.isfinite(sbb) & np.isfinite(sab)
+        ok_c = (scc > 0) & np.isfinite(scc) & np.isfinite(sac)
+        det = sbb * scc - (sbc.real * sbc.real + sbc.imag * sbc.imag)
+        full = flagged & ok_b & ok_c & np.isfinite(det) & (det > float(loading) * sbb * scc)
+        safe = np.where(full, det, 1.0)
+        w1 = (np.conj(sab) * scc - np.conj(sac) * sbc) / safe
+        w2 = (np.conj(sac) * sbb - np.conj(sab) * np.conj(sbc)) / safe
+        # the fallback: the single auxiliary whose coherence with a is larger (|Sax|^2 / Sxx, Saa being common)
+        cb = np.where(ok_b, (sab.real ** 2 + sab.imag ** 2) / np.where(ok_b, sbb, 1.0), -1.0)
+        cc = np.where(ok_c, (sac.real ** 2 + sac.imag ** 2) / np.where(ok_c, scc, 1.0), -1.0)
+        one_b = flagged & ~full & ok_b & (cb >= cc)
+        one_c = flagged & ~full & ok_c & ~one_b
+        s1 = np.conj(sab) / np.where(ok_b, sbb, 1.0)
+        s2 = np.conj(sac) / np.where(ok_c, scc, 1.0)
+    w = np.zeros((sab.shape[0], 2, ab.nfft), np.complex128)
+    w[:, 0][full], w[:, 1][full] = w1[full], w2[full]
+    w[:, 0][one_b] = s1[one_b]
+    w[:, 1][one_c] = s2[one_c]
     return w.astype(np.complex64)
 
 

@@ -8,6 +8,7 @@ measures its spectrum, the excisor cleans the whole capture.
     python -m gpsjam.mitigate IN.bin OUT.bin [--nfft N] [--rise-db D] [--swept]
     python -m gpsjam.mitigate IN.bin OUT.bin --pulsed [--window W] [--guard G] [--rise-db D]
     python -m gpsjam.mitigate A.bin OUT.bin --spatial B.bin [--nfft N] [--frames-per-row M] [--p-fa P] [--lag L|k5]
+    python -m gpsjam.mitigate A.bin OUT.bin --spatial B.bin --spatial2 C.bin [--lag L|k5] [--lag2 L|k5]
 
 writes the cleaned file, byte for byte as long as the input, for gnssdec.
 
@@ -26,6 +27,12 @@ bins the two captures share (``coherence.scan``, gj_csd_dev), builds the per-bin
 (``coherence.cancel_weights``) and subtracts the auxiliary antenna's weighted spectrum from the main one's
 (``Device.cancel``, gj_cancel_dev).  One auxiliary antenna gives one null per bin: a satellite whose inter-antenna phase
 is near the jammer's is attenuated with it, and the main antenna's receiver noise rises by up to 1 + |W|^2.
+
+Two Gaussian jammers from different directions in one band leave a single auxiliary half blind: its one null fits one of
+them.  With a third antenna ``clean_spatial2`` (``--spatial2``) takes the sums of the three pairs
+(``coherence.spectral_matrix``), solves the 2 x 2 system per cell (``coherence.cancel_weights2``) and subtracts both
+auxiliaries' weighted spectra (``Device.cancel2``, gj_cancel2_dev): two nulls per bin, the noise rising by up to
+1 + |W1|^2 + |W2|^2.
 
 Nothing here computes on the CPU but the threshold's arithmetic on one PSD row or one floor value, and the weights'
 on the rows x nfft sums.
@@ -305,6 +312,74 @@ def clean_spatial(dev, main, aux, nfft: int = 1024, frames_per_row: int = 256, p
     return CleanedSpatial(cleaned, rec, weights, found, cancelled, suppression, True, "")
 
 
+class CleanedSpatial2(NamedTuple):
+    """Result of ``clean_spatial2``: ``CleanedSpatial``'s fields -- ``weights`` is complex64[n_sets][2][nfft], W1 and W2 of
+    every set, ``scan`` the coherence scan of (main, aux_b) -- and the scans of (main, aux_c) and (aux_b, aux_c)."""
+    capture: Capture
+    records: np.ndarray
+    weights: np.ndarray
+    scan: object
+    bands: List
+    suppression_db: List[float]
+    cancelled: bool
+    note: str
+    scan_c: object
+    scan_bc: object
+
+
+def clean_spatial2(dev, main, aux_b, aux_c, nfft: int = 1024, frames_per_row: int = 256, p_fa: float = 1e-6, lags="k5",
+                   threshold=None, fs: float = 2.048e6) -> CleanedSpatial2:
+    """``main`` with what it shares with ``aux_b`` and ``aux_c`` cancelled bin by bin (gj_cancel2_dev): ``clean_spatial``
+    with two auxiliaries, step by step.  The three captures are resident ``Capture``s or host bytes (uploaded once each)
+    of three antennas on one clock.
+
+    ``coherence.spectral_matrix`` runs at hop = nfft over rows of ``frames_per_row`` frame triples, aligned by ``lags``
+    (samples by which each auxiliary lags main, or "k5").  A cell is flagged when ``coherence.detect_cells`` flags it for
+    (main, aux_b) or for (main, aux_c); a flagged cell gets the 2 x 2 solution of its own row's sums
+    (``coherence.cancel_weights2``), every other cell exactly 0, so a row without a jammer goes through untouched.  One
+    weight set per row at ``frames_per_set`` = 2 M as in ``clean_spatial``; ``threshold``: the excisor's mask behind the
+    cancellation, None for none.  The result covers the aligned range: main from sample max(0, -lag_b, -lag_c) on, as long
+    as all three captures hold samples.  With nothing flagged the result is a copy of the whole of ``main`` and
+    ``cancelled`` is False."""
+    from . import coherence
+    nfft, m = int(nfft), int(frames_per_row)
+    with contextlib.ExitStack() as temps:
+        cap_a = temps.enter_context(dev._resident(main))
+        cap_b = cap_a if aux_b is main else temps.enter_context(dev._resident(aux_b))
+        cap_c = cap_a if aux_c is main else cap_b if aux_c is aux_b else temps.enter_context(dev._resident(aux_c))
+        if excise_frames(cap_a.nsamples, nfft) == 0:
+            raise ValueError(f"the capture holds {cap_a.nsamples} samples, fewer than one frame of {nfft}")
+        mat = coherence.spectral_matrix(dev, cap_a, cap_b, cap_c, lags=lags, nfft=nfft, frames_per_row=m)
+        scans = []
+        for res, lag in zip(mat, (mat.lags[0], mat.lags[1], mat.lags[1] - mat.lags[0])):
+            det = coherence.detect(res, p_fa)
+            found = [bd._replace(delay=coherence.band_delay(res, bd, lag)) for bd in coherence.bands(res, det, fs)]
+            scans.append(coherence.Scan(res, det, found, lag))
+        cells_b, cells_c = coherence.detect_cells(mat.ab, p_fa), coherence.detect_cells(mat.ac, p_fa)
+        flagged = cells_b.flagged | cells_c.flagged
+        if not flagged.any():
+            zero = np.zeros((1, 2, nfft), np.complex64)
+            cleaned, rec = dev.cancel2(cap_a, cap_a, cap_a, zero, threshold, nfft=nfft)
+            return CleanedSpatial2(cleaned, rec, zero, scans[0], [], [], False, "nothing coherent was flagged: a copy of main",
+                                   scans[1], scans[2])
+        weights = coherence.cancel_weights2(mat, flagged)
+        cleaned, rec = dev.cancel2(cap_a, cap_b, cap_c, weights, threshold, nfft=nfft, first_a=mat.ab.first_a,
+                                   first_b=mat.ab.first_b, first_c=mat.ac.first_b, frames_per_set=2 * m)
+    union = coherence.Detection(flagged.any(axis=0), cells_b.threshold, cells_b.p_fa)
+    msc = np.fmax(mat.ab.msc, mat.ac.msc)                     # a band's median MSC: the better auxiliary's, cell by cell
+    cancelled = [coherence.Band(*run) for _, *run in _bands.runs(union.flagged, msc, fs)]
+    sets = np.minimum(np.arange(rec.size) // (2 * m), weights.shape[0] - 1)
+    t_in, t_out = rec["total_in"].astype(np.float64), rec["total"].astype(np.float64)
+    shifted = _bands.shifted_order(nfft)
+    suppression = []
+    for bd in cancelled:
+        at = int(np.flatnonzero(shifted == bd.first_bin)[0])
+        active = np.any(weights[:, :, shifted[at:at + bd.n_bins]] != 0, axis=(1, 2))[sets]
+        num, den = t_in[active].sum(), t_out[active].sum()
+        suppression.append(float(10.0 * np.log10(num / den)) if num > 0 and den > 0 else float("nan"))
+    return CleanedSpatial2(cleaned, rec, weights, scans[0], cancelled, suppression, True, "", scans[1], scans[2])
+
+
 def main(argv=None) -> int:
     import argparse
     from . import Device
@@ -321,12 +396,37 @@ def main(argv=None) -> int:
     ap.add_argument("--guard", type=int, default=8, help="--pulsed: samples blanked on either side of a detection")
     ap.add_argument("--spatial", metavar="B.bin", default=None,
                     help="cancel what the input shares with this second antenna's capture (clean_spatial)")
+    ap.add_argument("--spatial2", metavar="C.bin", default=None,
+                    help="with --spatial: a third antenna's capture, two nulls per bin (clean_spatial2)")
+    ap.add_argument("--lag2", default=None, help="--spatial2: integer samples by which C lags the input, or k5 (default: --lag)")
     ap.add_argument("--frames-per-row", type=int, default=256, help="--spatial: frame pairs per weight set")
     ap.add_argument("--p-fa", type=float, default=1e-6, help="--spatial: false-alarm probability per cell")
     ap.add_argument("--lag", default="k5", help="--spatial: integer samples by which B lags the input, or k5")
     args = ap.parse_args(argv)
     if sum(map(bool, (args.pulsed, args.swept, args.spatial))) > 1:
         ap.error("--pulsed, --swept and --spatial exclude each other")
+    if args.spatial2 and not args.spatial:
+        ap.error("--spatial2 needs --spatial")
+    if args.spatial2:
+        as_lag = lambda v: "k5" if v == "k5" else int(v)
+        lag_b, lag_c = as_lag(args.lag), as_lag(args.lag if args.lag2 is None else args.lag2)
+        lags = "k5" if lag_b == lag_c == "k5" else (lag_b, lag_c)
+        if "k5" in (lag_b, lag_c) and lags != "k5":
+            ap.error("--lag and --lag2 are both k5 or both integers")
+        with Device(args.device) as dev:
+            with dev.capture(args.input) as cap, dev.capture(args.spatial) as aux_b, dev.capture(args.spatial2) as aux_c:
+                res = clean_spatial2(dev, cap, aux_b, aux_c, nfft=args.nfft, frames_per_row=args.frames_per_row, p_fa=args.p_fa,
+                                     lags=lags, fs=args.fs)
+                try:
+                    res.capture.download().tofile(args.output)
+                finally:
+                    res.capture.free()
+        print(f"{args.output}: {res.records.size} frames of {args.nfft} points, aligned by {res.scan.lag} and {res.scan_c.lag}, "
+              + (f"{len(res.bands)} band(s) cancelled with two auxiliaries" if res.cancelled else res.note))
+        for bd, db in zip(res.bands, res.suppression_db):
+            print(f"  {bd.freq_lo_hz / 1e3:9.1f} .. {bd.freq_hi_hz / 1e3:9.1f} kHz  ({bd.n_bins} bins)  median MSC {bd.median_msc:.3f}  "
+                  f"suppression {db:.1f} dB")
+        return 0
     if args.spatial:
         lag = "k5" if args.lag == "k5" else int(args.lag)
         with Device(args.device) as dev:

@@ -493,6 +493,45 @@ int gj_cancel_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t first
                   size_t frames_per_set, size_t n_sets, const float* d_threshold /* [nfft] */,
                   uint8_t* d_out /* [2*n_samples] */, gj_cancel_frame* d_frames /* [F] or NULL */);
 
+/* ------------------------------------------------- three-antenna per-bin canceller -- */
+/* The multiple sidelobe canceller of a receiver with three antennas: gj_cancel_dev with two auxiliaries, two complex
+ * weights per bin and so two nulls per bin.  Two Gaussian jammers from different directions in one band, of which a
+ * single auxiliary can null only one, are removed together.  The MMSE weights solve, per bin, the 2 x 2 system
+ *   W1 Sbb + W2 Sbc = conj(Sab),   W1 conj(Sbc) + W2 Scc = conj(Sac)
+ * on gj_csd_dev's sums of the pairs (a,b), (a,c) and (b,c) (gpsjam/coherence.py, cancel_weights2).  Everything is
+ * gj_cancel_dev's -- F, h, w, x, scale, set(f), the mask, the inverse transform, the overlap-add, the copied edges, the
+ * record gj_cancel_frame with total_in capture a's power -- except:
+ *
+ *   C_f[k]  = sum_n w[n] x_c[first_c + f*h + n] exp(-2 pi i k n / N)      from capture c, as B_f from capture b
+ *   Y_f[k]  = (A_f[k] - W1[set(f)][k] * B_f[k]) - W2[set(f)][k] * C_f[k]  every product of W1 * B and W2 * C rounded on
+ *                                                                         its own, the two subtractions in this order
+ *
+ * d_weights: DEVICE float32[n_sets][2][nfft][2]: set s holds W1[s][k] at d_weights + s*4*nfft and W2[s][k] 2*nfft floats
+ * further, both (re, im) in FFT order; 8-byte aligned; the host never reads it.
+ * Bit-exact anchors: with every W2 = 0 the call writes the bytes and records of gj_cancel_dev(a, b, W1), whatever c
+ * holds; with every W1 = 0 those of gj_cancel_dev(a, c, W2), whatever b holds; with both 0 those of gj_excise_dev on
+ * capture a (total_in == total).
+ * Output: d_out[2*n_samples], range-relative; the first half frame and everything from F*h on are copied from capture a.
+ * The call writes exactly 2*n_samples bytes.  d_frames (optional) receives one record per frame.  first_a, first_b and
+ * first_c may be odd and may all differ; d_a == d_b == d_c is allowed.
+ * Refusals: those of gj_cancel_dev, applied to all three captures (nfft, n_samples < nfft, a range past any capture, a null
+ * or odd d_a, d_b or d_c, a null d_out or d_threshold, a d_threshold or d_frames that is not 4-byte aligned, d_out
+ * overlapping any of the three captures, frames_per_set == 0 or n_sets == 0, a null d_weights or one that is not 8-byte
+ * aligned; GJ_ERR_INVALID but for nfft: GJ_ERR_UNSUPPORTED).  A refused call enqueues nothing.  Needs no workspace;
+ * enqueues on the context's stream (two launches: the transform kernel and the edge copy) and returns.
+ * Determinism: an output sample depends only on the bytes of the two frame triples that cover it and on their weight
+ * sets, and every sum runs in an order fixed by nfft.  So a call started k*h samples later in all three captures, with the
+ * sets shifted alike, reproduces the overlapping interior bytes and the records of the shared frames bit for bit; two
+ * identical calls give identical bytes; and d_frames == NULL changes no byte.
+ * Limits: two auxiliaries give two nulls per bin -- a signal whose steering vector lies near the plane of the two
+ * jammers' is attenuated with them -- and capture a's receiver noise rises by up to 1 + |W1|^2 + |W2|^2.  The three
+ * captures must share a clock and be aligned to well under nfft samples, as for gj_csd_dev. */
+int gj_cancel2_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t first_a, const uint8_t* d_b, size_t nbytes_b,
+                   size_t first_b, const uint8_t* d_c, size_t nbytes_c, size_t first_c, size_t n_samples, int nfft,
+                   const float* d_weights /* [n_sets][2][nfft][2] */, size_t frames_per_set, size_t n_sets,
+                   const float* d_threshold /* [nfft] */, uint8_t* d_out /* [2*n_samples] */,
+                   gj_cancel_frame* d_frames /* [F] or NULL */);
+
 /* ------------------------------------------------- time-domain pulse blanking ------- */
 /* The pulse blanker a receiver puts in front of its FFT excisor: a cleaned capture, uint8 I/Q again, with every sample
  * near a window of excess power put to mid-level (simulate/frontend/jammers/pulsedJammer.py and every sweep that crosses
