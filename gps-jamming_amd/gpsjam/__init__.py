@@ -30,7 +30,7 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
            "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE",
            "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks", "FINE_BLOCK", "FINE_MAX_HALF", "fine_blocks", "FineCorr",
-           "CrossSpectrum", "csd_rows", "CANCEL_DTYPE"]
+           "CrossSpectrum", "csd_rows", "CANCEL_DTYPE", "CORR_MAX_BLOCK", "CORR_CHANNEL_DTYPE", "corr_blocks", "CorrBank"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -219,6 +219,60 @@ class FineCorr(NamedTuple):
     c: np.ndarray           # complex128[2R+1]
     blocks: Optional[np.ndarray]   # complex128[blocks][2R+1] or None
     n_samples: int
+
+
+CORR_MAX_BLOCK = _ffi.GJ_CORR_MAX_BLOCK
+CORR_CHANNEL_DTYPE = np.dtype([("code_phase", np.uint64), ("code_step", np.uint64), ("carr_phase", np.uint32),
+                               ("carr_step", np.uint32), ("code_row", np.int32), ("reserved", np.int32)])
+
+
+def corr_blocks(n_samples: int, block_samples: int) -> int:
+    """Block records of the correlator bank over n_samples: one per block_samples samples, the last one ragged
+    (gj_corr_blocks)."""
+    if not 0 <= int(n_samples) < 2 ** 64 or not 1 <= int(block_samples) < 2 ** 31:
+        return 0
+    return int(_ffi.load().gj_corr_blocks(int(n_samples), int(block_samples)))
+
+
+class CorrBank(NamedTuple):
+    """``Device.corr_bank``: the exact integers of gj_corr_bank_dev.  ``iq[ch, m, j]`` = (I, Q) of channel ch, block m
+    (``block_samples`` samples, the last one ragged) and tap ``taps[j]`` (whole samples; 0 is the prompt)."""
+    iq: np.ndarray          # int32[n_channels][n_blocks][n_taps][2]
+    taps: tuple
+    block_samples: int
+    n_samples: int
+
+    def tap(self, offset: int = 0) -> np.ndarray:
+        """complex128[n_channels][n_blocks]: I + jQ of the tap at ``offset`` samples (default: the prompt)."""
+        j = self.taps.index(int(offset))
+        return self.iq[:, :, j, 0].astype(np.float64) + 1j * self.iq[:, :, j, 1].astype(np.float64)
+
+
+def _corr_channels(channels, n_code_rows: int) -> np.ndarray:
+    """The channel table of ``Device.corr_bank`` as CORR_CHANNEL_DTYPE records, its fields checked on the host: they
+    live in device memory once uploaded, where gj_corr_bank_dev cannot answer for them with a status."""
+    if isinstance(channels, np.ndarray) and channels.dtype == CORR_CHANNEL_DTYPE:
+        rec = np.ascontiguousarray(channels).reshape(-1)
+    else:
+        rows = [tuple(int(v) for v in c) for c in channels]
+        for r in rows:
+            if len(r) != 6 or not (0 <= r[0] < 2 ** 64 and 0 <= r[1] < 2 ** 64 and 0 <= r[2] < 2 ** 32 and 0 <= r[3] < 2 ** 32
+                                   and -2 ** 31 <= r[4] < 2 ** 31 and -2 ** 31 <= r[5] < 2 ** 31):
+                raise GpsJamError(-1, f"invalid argument: a channel is (code_phase, code_step, carr_phase, carr_step, code_row, 0), not {r}")
+        rec = np.array(rows, CORR_CHANNEL_DTYPE).reshape(-1)
+    for k, c in enumerate(rec):
+        what = None
+        if int(c["reserved"]) != 0:
+            what = "reserved must be 0"
+        elif not 0 <= int(c["code_row"]) < n_code_rows:
+            what = f"code_row {int(c['code_row'])} outside the {n_code_rows} rows"
+        elif int(c["code_phase"]) >= _ffi.GJ_CORR_CODE_LEN << 32:
+            what = "code_phase is not below 1023 * 2^32"
+        elif int(c["code_step"]) >= _ffi.GJ_CORR_MAX_CODE_STEP:
+            what = "code_step is not below 2^34"
+        if what:
+            raise GpsJamError(-1, f"invalid argument: channel {k}: {what}")
+    return rec
 
 
 class _FrameRecords:
@@ -1246,7 +1300,50 @@ class Device:
         c = (total[:, 0] + 1j * total[:, 1]) / 4.0
         return FineCorr(lags, c, None if rec is None else (rec[..., 0] + 1j * rec[..., 1]) / 4.0, n_samples)
 
+    def corr_bank(self, capture, channels, codes, first_sample: int = 0, n_samples: Optional[int] = None,
+                  block_samples: int = 2048, taps=(0, -1, 1)) -> CorrBank:
+        """The correlator bank (gj_corr_bank_dev): every channel of ``channels`` mixed with its carrier, multiplied with
+        its code row at every tap and summed per ``block_samples`` samples, over ``n_samples`` samples from
+        ``first_sample`` (default: to the end).  ``capture``: host bytes (uploaded once) or a resident ``Capture``;
+        ``channels``: CORR_CHANNEL_DTYPE records or (code_phase, code_step, carr_phase, carr_step, code_row, 0) rows,
+        what ``gpsjam.postcorr.channel`` makes; ``codes``: int16[rows][1023] of +-1 on the host, or a device buffer
+        ``(buffer, rows)``; ``taps``: whole-sample offsets.  The channel fields are checked HERE, on the host, before
+        they are uploaded (GJ_ERR_INVALID): the library cannot answer for device memory with a status."""
+        first_sample, block_samples = int(first_sample), int(block_samples)
+        taps = tuple(int(d) for d in taps)
+        with contextlib.ExitStack() as temps:
+            cap = temps.enter_context(self._resident(capture))
+            n_samples = max(0, cap.nsamples - first_sample) if n_samples is None else int(n_samples)
+            if isinstance(codes, tuple):
+                d_codes, n_rows = codes[0], int(codes[1])
+            else:
+                host = np.ascontiguousarray(codes, np.int16)
+                if host.ndim != 2 or host.shape[1] != _ffi.GJ_CORR_CODE_LEN:
+                    raise ValueError(f"codes must be int16[rows][{_ffi.GJ_CORR_CODE_LEN}]")
+                n_rows = int(host.shape[0])
+                d_codes = temps.enter_context(DevBuf(self, max(host.nbytes, 2))).upload(host)
+            rec = _corr_channels(channels, n_rows)
+            blocks = corr_blocks(n_samples, block_samples)
+            d_ch = temps.enter_context(DevBuf(self, max(rec.nbytes, 32))).upload(rec)
+            d_out = temps.enter_context(DevBuf(self, 8 * max(rec.size * blocks * len(taps), 1)))
+            self._count("corr_bank")
+            self.corr_bank_dev(cap, cap.nbytes, first_sample, n_samples, block_samples, d_codes, n_rows, d_ch, rec.size, taps, d_out)
+            iq = d_out.download(np.int32, 2 * rec.size * blocks * len(taps)).reshape(rec.size, blocks, len(taps), 2)
+        return CorrBank(iq, taps, block_samples, n_samples)
+
     # ------------------------------------------------------------------ device pointers
+    def corr_bank_dev(self, d_iq, nbytes, first_sample, n_samples, block_samples, d_codes, n_code_rows, d_channels, n_channels,
+                      taps, d_out):
+        """gj_corr_bank_dev: int32 (I, Q) of every channel, block and tap into d_out, on the context's stream; ``taps`` is a
+        host sequence of whole-sample offsets."""
+        taps = [int(d) for d in taps]
+        if any(not -2 ** 31 <= d < 2 ** 31 for d in taps):
+            raise GpsJamError(-5, "unsupported: a tap offset outside int32")
+        arr = (C.c_int32 * max(len(taps), 1))(*taps)
+        self._check(self._lib.gj_corr_bank_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples),
+                                               int(block_samples), _ptr(d_codes), int(n_code_rows), _ptr(d_channels),
+                                               int(n_channels), arr, len(taps), _ptr(d_out)))
+
     def xcorr_fine_dev(self, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, lag_center, half_width, d_total,
                        d_blocks=None):
         """gj_xcorr_fine_dev: int64 (re, im) of the 2 * half_width + 1 lags into d_total and, if asked for, the int32

@@ -156,6 +156,12 @@ class BlankBlock(C.Structure):
     _fields_ = [("total", C.c_uint64), ("removed", C.c_uint64), ("n_blanked", C.c_int32), ("n_rising", C.c_int32)]
 
 
+class CorrChannel(C.Structure):
+    """gj_corr_channel: one channel of the correlator bank (include/gpsjam.h)."""
+    _fields_ = [("code_phase", C.c_uint64), ("code_step", C.c_uint64), ("carr_phase", C.c_uint32), ("carr_step", C.c_uint32),
+                ("code_row", C.c_int32), ("reserved", C.c_int32)]
+
+
 GJ_CP_ODD_CHUNK_ZERO = 1
 GJ_WELCH_SHIFT = 1
 GJ_MAX_ANTENNAS = 16
@@ -168,6 +174,14 @@ GJ_CHIRP_MAX_RATES = 256
 GJ_BLANK_BLOCK = 4096
 GJ_FINE_BLOCK = 4096
 GJ_FINE_MAX_HALF = 32
+GJ_CORR_MAX_BLOCK = 4096
+GJ_CORR_MAX_TAPS = 9
+GJ_CORR_MAX_TAP_OFFSET = 64
+GJ_CORR_MAX_CHANNELS = 64
+GJ_CORR_MAX_SAMPLES = 1 << 28
+GJ_CORR_MAX_CODE_STEP = 1 << 34
+GJ_CORR_CODE_LEN = 1023
+GJ_CORR_COS_TABLE = (32, 30, 23, 12, 0, -12, -23, -30, -32, -30, -23, -12, 0, 12, 23, 30)
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
 _pf, _psz = C.POINTER(C.c_float), C.POINTER(C.c_size_t)
@@ -285,6 +299,8 @@ SIGNATURES = {
     "gj_xcorr_caf_workspace": (_sz, [_vp, _i, _sz, _i, _i, _i]),
     "gj_fine_blocks": (_sz, [_sz]),
     "gj_xcorr_fine_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, C.c_int32, _i, _vp, _vp]),
+    "gj_corr_blocks": (_sz, [_sz, _i]),
+    "gj_corr_bank_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
     "gj_pack_result_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gj_synth_u8_dev": (_i, [_vp, C.POINTER(SynthParams), C.c_int64, _sz, _vp]),
 }

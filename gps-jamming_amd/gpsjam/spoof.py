@@ -1,0 +1,162 @@
+"""Two-antenna spoofing detection: the carrier phase difference of every PRN between two antennas on one clock.
+
+Authentic satellites arrive from different directions: the phase of a PRN at antenna b against antenna a,
+2 pi (baseline . direction) / wavelength, differs from PRN to PRN.  A spoofer sends every PRN from ONE antenna: all
+its PRNs share one phase difference.  ``pair_phases`` measures the difference per PRN from the correlator bank's prompt
+series (``gpsjam.postcorr``), ``common_direction`` finds the largest set of PRNs inside one arc and the probability of
+such a set under uniform phases, and ``scan`` puts the two together.
+
+The premise is ``coherence.scan``'s: the two receivers share a clock and the captures are sample-aligned (the
+deployment ``gpsjam.local`` holds).
+
+Limits.  One baseline measures one angle: it cannot separate a spoofer from satellites that happen to share its phase
+cone, and ``p_chance`` is the price list for that.  Fewer than ``min_common`` (4) acquired PRNs give no verdict
+(``spoofed`` is None).  A spoofer that overpowers the authentic signals is what the acquisition finds, and the weaker
+authentic peak of the same PRN is not searched for: a second-peak search is out of scope here.
+
+    python -m gpsjam.spoof A.bin B.bin
+"""
+from __future__ import annotations
+
+import math
+from typing import List, NamedTuple, Optional, Sequence
+
+import numpy as np
+
+from . import gnss, postcorr
+
+
+class PairPhase(NamedTuple):
+    prn: int
+    phase: float         # arg sum_k P_b[k] conj(P_a[k]), rad: antenna b against antenna a
+    coherence: float     # |sum| / sqrt(sum |P_a|^2 sum |P_b|^2), 0 .. 1
+    cn0_dbhz: float      # at antenna a
+    doppler_hz: float
+
+
+class Common(NamedTuple):
+    members: List[int]   # indices into the phases given, in their order
+    centre: float        # middle of the arc that holds them, rad
+    p_chance: float      # bound on the probability of a set this large under uniform phases
+
+
+class SpoofReport(NamedTuple):
+    prns: List[int]
+    phase: np.ndarray
+    coherence: np.ndarray
+    cn0: np.ndarray
+    common_prns: List[int]
+    p_chance: float
+    spoofed: Optional[bool]      # None: fewer than min_common PRNs, no verdict
+
+
+def pair_phases(dev, a, b, search, first_sample: int = 0, duration_s: float = 0.1) -> List[PairPhase]:
+    """Acquire on ``a`` (``postcorr.observe``: the channels at the refined Doppler) and run the SAME channels on ``b``.
+    z_p = sum_k P_b[k] conj(P_a[k]): navigation bits and whatever Doppler is left are common to both antennas and
+    cancel, block by block.  Per acquired PRN ``phase = arg z_p`` and
+    ``coherence = |z_p| / sqrt(sum |P_a|^2 sum |P_b|^2)``."""
+    with dev._resident(a) as cap_a, dev._resident(b) as cap_b:
+        obs = postcorr.observe(dev, cap_a, search, first_sample, duration_s)
+        if not obs:
+            return []
+        B = postcorr.block_samples(search)
+        n = min(int(round(duration_s * search.fs)), cap_a.nsamples - int(first_sample), cap_b.nsamples - int(first_sample))
+        bank = dev.corr_bank(cap_b, [o.channel for o in obs], postcorr.codes([o.prn for o in obs]), first_sample, n, B, (0,))
+    out = []
+    for o, pb in zip(obs, postcorr.tap_periods(bank, 0, [o.first_block for o in obs])):
+        m = min(o.prompts.size, pb.size)
+        pa, pb = o.prompts[:m], pb[:m]
+        z = np.sum(pb * np.conj(pa))
+        den = math.sqrt(float(np.sum(np.abs(pa) ** 2)) * float(np.sum(np.abs(pb) ** 2)))
+        out.append(PairPhase(o.prn, float(np.angle(z)), float(abs(z) / den) if den > 0.0 else 0.0, o.cn0_dbhz, o.doppler_hz))
+    return out
+
+
+def chance(k: int, n: int, tol: float) -> float:
+    """A bound on the probability that SOME arc of width 2 tol holds at least k of n independent uniform phases.
+
+    Take the member of such a set that comes first going round anticlockwise: the others lie in the arc of width 2 tol that starts
+    at it.  So the event is the union over the n phases i of A_i = "at least k - 1 of the other n - 1 phases lie in
+    [phi_i, phi_i + 2 tol]".  Given phi_i, each of the others lies there with probability w = 2 tol / (2 pi) = tol / pi,
+    independently, so P(A_i) = P(Binomial(n - 1, w) >= k - 1), and by the union bound
+
+        P <= n sum_{m = k-1}^{n-1} C(n - 1, m) w^m (1 - w)^(n - 1 - m).
+
+    For k = n and w < 1/2 the A_i exclude each other and the bound is the exact n (tol / pi)^(n - 1)."""
+    k, n = int(k), int(n)
+    if n < 1 or k < 2:
+        return 1.0
+    w = min(max(float(tol) / math.pi, 0.0), 1.0)
+    tail = sum(math.comb(n - 1, m) * w ** m * (1.0 - w) ** (n - 1 - m) for m in range(k - 1, n))
+    return min(1.0, n * tail)
+
+
+def common_direction(phases: Sequence[float], tol: float = 0.15) -> Common:
+    """The largest set of phases that lie within one arc of width 2 tol (rad), and ``chance`` of a set of its size
+    among as many phases.  Every phase in turn is taken as the arc's start; of equally large sets the narrowest wins."""
+    ph = np.asarray(phases, np.float64).reshape(-1)
+    n = int(ph.size)
+    if n == 0:
+        return Common([], 0.0, 1.0)
+    best, best_span = [], 0.0
+    for i in range(n):
+        ahead = (ph - ph[i]) % (2.0 * math.pi)
+        inside = np.nonzero(ahead <= 2.0 * float(tol))[0]
+        span = float(ahead[inside].max())
+        if len(inside) > len(best) or (len(inside) == len(best) and span < best_span):
+            best, best_span, start = inside.tolist(), span, float(ph[i])
+    centre = (start + 0.5 * best_span + math.pi) % (2.0 * math.pi) - math.pi
+    return Common(best, centre, chance(len(best), n, tol))
+
+
+def scan(dev, a, b, search=None, tol: float = 0.15, min_common: int = 4, first_sample: int = 0,
+         duration_s: float = 0.1) -> SpoofReport:
+    """``pair_phases`` and ``common_direction``: ``spoofed`` when at least ``min_common`` PRNs share one arc, None when
+    fewer than that were acquired at all.  ``search``: a ``gnss.AcqSearch`` of the caller's (default: one over all 32
+    PRNs, closed again)."""
+    own = search is None
+    if own:
+        search = gnss.AcqSearch(dev)
+    try:
+        found = pair_phases(dev, a, b, search, first_sample, duration_s)
+    finally:
+        if own:
+            search.close()
+    prns = [f.prn for f in found]
+    common = common_direction([f.phase for f in found], tol)
+    verdict = None if len(prns) < int(min_common) else len(common.members) >= int(min_common)
+    return SpoofReport(prns, np.array([f.phase for f in found]), np.array([f.coherence for f in found]),
+                       np.array([f.cn0_dbhz for f in found]), [prns[i] for i in common.members], common.p_chance, verdict)
+
+
+def main(argv=None) -> int:
+    import argparse
+    from . import Device
+    ap = argparse.ArgumentParser(prog="python -m gpsjam.spoof", description="print each PRN's phase between two antennas and the spoofing verdict")
+    ap.add_argument("a")
+    ap.add_argument("b")
+    ap.add_argument("--tol", type=float, default=0.15, help="half width of the common arc, rad")
+    ap.add_argument("--min-common", type=int, default=4)
+    ap.add_argument("--first-sample", type=int, default=0)
+    ap.add_argument("--duration", type=float, default=0.1, help="seconds")
+    ap.add_argument("--fs", type=float, default=2.048e6)
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    with Device(args.device) as dev:
+        search = gnss.AcqSearch(dev, fs=args.fs)
+        try:
+            with dev.capture(args.a) as cap_a, dev.capture(args.b) as cap_b:
+                rep = scan(dev, cap_a, cap_b, search, args.tol, args.min_common, args.first_sample, args.duration)
+        finally:
+            search.close()
+    print(f"{args.a} / {args.b}: {len(rep.prns)} PRN(s) acquired on the first antenna")
+    for prn, ph, co, c in zip(rep.prns, rep.phase, rep.coherence, rep.cn0):
+        mark = " *" if prn in rep.common_prns and len(rep.common_prns) >= args.min_common else ""
+        print(f"  PRN {prn:2d}  phase {ph:+7.3f} rad  coherence {co:5.3f}  C/N0 {c:5.1f} dB-Hz{mark}")
+    verdict = "no verdict (too few PRNs)" if rep.spoofed is None else ("SPOOFED" if rep.spoofed else "not flagged")
+    print(f"largest common arc (+-{args.tol} rad): {len(rep.common_prns)} PRN(s) {rep.common_prns}, chance {rep.p_chance:.3g}: {verdict}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -841,6 +841,66 @@ int gj_xcorr_fine_dev(gj_ctx* ctx, const uint8_t* d_a, size_t nbytes_a, size_t f
                       int64_t* d_total /* [2R+1][2]  re, im */,
                       int32_t* d_blocks /* [gj_fine_blocks(n_samples)][2R+1][2] or NULL */);
 
+/* ------------------------------------------------- correlator bank: post-correlation I/Q ---- */
+/* The reference's second hot loop (correlator, sdrcmn.c:707-740: mixcarr -> rescode -> dot_23 / dot_22) as a batch:
+ * with code phase and Doppler known from the acquisition and the code rate tied to the Doppler, every block of every
+ * channel is independent, so a whole capture is correlated in one launch, open loop.  Integer arithmetic from the byte
+ * to the sum: gpsjam/postcorr.py makes Doppler, C/N0 and carrier phase of the prompt series on the host.
+ *
+ * For sample t = 0 .. n_samples-1 of the range (sample first_sample + t of the capture), I, Q = byte - 128 (the
+ * acquisition's fixed unpacking, sdrrcv.c:104-106, WHATEVER gj_set_unpack says), and for channel ch:
+ *
+ *   carrier   theta = (carr_phase + t*carr_step) mod 2^32,   i = theta >> 28
+ *             wI = C[i]*I - S[i]*Q,   wQ = S[i]*I + C[i]*Q,   S[i] = C[(i - 4) & 15]
+ *             C = GJ_CORR_COS_TABLE: floor(cos(2 pi i / 16) * 32 + 0.5), the reference's SSE2 table (sdrcmn.c:629-630)
+ *   code      for tap j, d = tap_offsets[j]:
+ *             chip = floor((code_phase + (t + d)*code_step) / 2^32) mod 1023
+ *             exact integers, mathematical floor and mod: a negative t + d is well defined
+ *             c = d_codes[code_row][chip]; taps are whole-sample shifts of the resampled code (the reference's
+ *             code +- s[i] pointers).  The chips are +-1: a value < 0 counts as -1, every other value as +1
+ *   record    (ch, block m, tap j) = (sum wI*c, sum wQ*c) over t in [m*B, (m+1)*B), B = block_samples; last block ragged
+ *
+ * d_out: int32[n_channels][gj_corr_blocks(n_samples, B)][n_taps][2] (I, Q).  |w| <= 128*46 = 5888 (|C[i]| + |S[i]| <= 46),
+ * so a record is at most 4096 * 5888 = 24 117 248 < 2.5e7 in magnitude: int32 never wraps.  Every value is an exact
+ * integer: the result does not depend on tiling or order, two calls give identical bits, and it depends on the bytes
+ * of the range alone.  A capture that holds code * exp(-2j pi f t) peaks at carr_step = +f / fs * 2^32.
+ * Limits (GJ_ERR_UNSUPPORTED): block_samples a multiple of 16 in 16 .. GJ_CORR_MAX_BLOCK; n_taps 1 .. GJ_CORR_MAX_TAPS
+ * (the reference's 1 + 2 corrn); |tap_offsets[j]| <= GJ_CORR_MAX_TAP_OFFSET; n_channels 1 .. GJ_CORR_MAX_CHANNELS;
+ * n_samples 1 .. GJ_CORR_MAX_SAMPLES (t*code_step < 2^62).
+ * GJ_ERR_INVALID: a null ctx, d_iq, d_codes, d_channels, tap_offsets or d_out; an odd d_iq or d_codes, a d_channels
+ * that is not 8-byte aligned, a d_out that is not 4-byte aligned; n_code_rows < 1; a range that runs past the capture.
+ * A refused call enqueues nothing.
+ * The channel fields are in DEVICE memory, so the entry point cannot answer for them with a status.  They are checked
+ * twice: Device.corr_bank (gpsjam/__init__.py) checks them on the host before it uploads them and raises
+ * GJ_ERR_INVALID; and every workgroup of the kernel checks all of them before it reads a chip: if ANY channel has
+ * reserved != 0, a code_row outside 0 .. n_code_rows-1, code_phase >= 1023 * 2^32 or code_step >= GJ_CORR_MAX_CODE_STEP,
+ * the launch writes NOTHING (d_out is left as it was) and never reads outside d_codes.
+ * One launch on the context's stream; no workspace, no memset, no atomics: 0 bytes to gj_reserve, the call never
+ * allocates.  Each record is written by exactly one workgroup.  tap_offsets is a HOST array, read before the call returns. */
+typedef struct gj_corr_channel {      /* 32 bytes */
+    uint64_t code_phase;   /* Q32.32 chips at sample first_sample; < 1023 * 2^32 */
+    uint64_t code_step;    /* Q32.32 chips per sample; < GJ_CORR_MAX_CODE_STEP */
+    uint32_t carr_phase;   /* cycles * 2^32 at sample first_sample */
+    uint32_t carr_step;    /* cycles * 2^32 per sample, modulo 2^32 (negative Doppler = two's complement) */
+    int32_t code_row;      /* row of d_codes */
+    int32_t reserved;      /* must be 0 */
+} gj_corr_channel;
+#define GJ_CORR_MAX_BLOCK 4096                  /* block_samples: a multiple of 16 in 16 .. 4096 */
+#define GJ_CORR_MAX_TAPS 9
+#define GJ_CORR_MAX_TAP_OFFSET 64
+#define GJ_CORR_MAX_CHANNELS 64
+#define GJ_CORR_MAX_SAMPLES (1ull << 28)
+#define GJ_CORR_MAX_CODE_STEP (1ull << 34)      /* 4 chips per sample */
+#define GJ_CORR_CODE_LEN 1023
+#define GJ_CORR_COS_TABLE {32, 30, 23, 12, 0, -12, -23, -30, -32, -30, -23, -12, 0, 12, 23, 30}
+/* block records over n_samples: ceil(n_samples / block_samples), 0 for block_samples < 1; pure host arithmetic */
+size_t gj_corr_blocks(size_t n_samples, int block_samples);
+int gj_corr_bank_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples,
+                     int block_samples, const int16_t* d_codes /* [n_code_rows][1023], +-1 */, int n_code_rows,
+                     const gj_corr_channel* d_channels, int n_channels,
+                     const int32_t* tap_offsets /* HOST array [n_taps], samples */, int n_taps,
+                     int32_t* d_out /* [n_channels][gj_corr_blocks][n_taps][2]  I, Q */);
+
 /* ------------------------------------------------- per-stream result vector ---------- */
 /* What one rank sends to rank 0 (gpsjam/sharded.py):
  * double[40 + n_chunks + nperseg + 5*pair_capacity] =
