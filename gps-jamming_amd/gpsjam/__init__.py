@@ -30,7 +30,8 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "release_resident", "CafPeak", "xcorr_fft_len", "xcorr_bin_hz", "caf_bin_range", "Ridge", "RIDGE_DTYPE",
            "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE",
            "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks", "FINE_BLOCK", "FINE_MAX_HALF", "fine_blocks", "FineCorr",
-           "CrossSpectrum", "csd_rows", "CANCEL_DTYPE", "CORR_MAX_BLOCK", "CORR_CHANNEL_DTYPE", "corr_blocks", "CorrBank"]
+           "CrossSpectrum", "csd_rows", "CANCEL_DTYPE", "CORR_MAX_BLOCK", "CORR_CHANNEL_DTYPE", "corr_blocks", "CorrBank",
+           "ACQ_MAX_PEAKS", "ACQ_PEAK_DTYPE", "ACQ_FLOOR_DTYPE"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -246,6 +247,11 @@ class CorrBank(NamedTuple):
         """complex128[n_channels][n_blocks]: I + jQ of the tap at ``offset`` samples (default: the prompt)."""
         j = self.taps.index(int(offset))
         return self.iq[:, :, j, 0].astype(np.float64) + 1j * self.iq[:, :, j, 1].astype(np.float64)
+
+
+ACQ_MAX_PEAKS = _ffi.GJ_ACQ_MAX_PEAKS
+ACQ_PEAK_DTYPE = np.dtype([("power", np.float64), ("code_index", np.int32), ("freq_index", np.int32)])        # gj_acq_peak
+ACQ_FLOOR_DTYPE = np.dtype([("mean_power", np.float64), ("kept_columns", np.int32), ("reserved", np.int32)])  # gj_acq_floor
 
 
 def _corr_channels(channels, n_code_rows: int) -> np.ndarray:
@@ -1331,7 +1337,44 @@ class Device:
             iq = d_out.download(np.int32, 2 * rec.size * blocks * len(taps)).reshape(rec.size, blocks, len(taps), 2)
         return CorrBank(iq, taps, block_samples, n_samples)
 
+    def acq_peaks(self, power, k: int = 2, guard: int = 4, shape=None):
+        """The K-peak search (gj_acq_peaks_dev) over power surfaces double[n_prn][n_freq][nsamp]: per PRN the ``k``
+        largest peaks under successive exclusion of the columns within ``guard`` (circular) of a peak already taken, and
+        the mean of the columns left.  ``power``: a float64 array of that shape on the host (uploaded), or a device
+        buffer with ``shape = (n_prn, n_freq, nsamp)``.  Returns ``(peaks, floor)``: ACQ_PEAK_DTYPE[n_prn][k] and
+        ACQ_FLOOR_DTYPE[n_prn].  The arguments are checked by the library: a refusal raises ``GpsJamError``."""
+        k, guard = int(k), int(guard)
+        with contextlib.ExitStack() as temps:
+            if isinstance(power, (DevBuf, int)) or hasattr(power, "data_ptr"):
+                if shape is None or len(shape) != 3:
+                    raise ValueError("a device surface needs shape = (n_prn, n_freq, nsamp)")
+                d_power = power
+            else:
+                host = np.ascontiguousarray(power, np.float64)
+                if host.ndim != 3:
+                    raise ValueError("power must be float64[n_prn][n_freq][nsamp]")
+                shape = host.shape
+                d_power = temps.enter_context(DevBuf(self, max(host.nbytes, 8))).upload(host)
+            n_prn, n_freq, nsamp = (int(v) for v in shape)
+            records = max(n_prn, 1) * min(max(k, 1), ACQ_MAX_PEAKS)
+            d_peaks = temps.enter_context(DevBuf(self, ACQ_PEAK_DTYPE.itemsize * records))
+            d_floor = temps.enter_context(DevBuf(self, ACQ_FLOOR_DTYPE.itemsize * max(n_prn, 1)))
+            self._count("acq_peaks")
+            self.acq_peaks_dev(d_power, n_prn, n_freq, nsamp, k, guard, d_peaks, d_floor)
+            return d_peaks.download(ACQ_PEAK_DTYPE, n_prn * k).reshape(n_prn, k), d_floor.download(ACQ_FLOOR_DTYPE, n_prn)
+
     # ------------------------------------------------------------------ device pointers
+    def acq_peaks_workspace(self, nsamp: int, n_prn: int) -> int:
+        return int(self._lib.gj_acq_peaks_workspace(self._ctx, int(nsamp), int(n_prn)))
+
+    def acq_peaks_dev(self, d_power, n_prn, n_freq, nsamp, k, guard, d_peaks, d_floor):
+        """gj_acq_peaks_dev: gj_acq_peak[n_prn][k] into d_peaks and gj_acq_floor[n_prn] into d_floor, on the context's
+        stream."""
+        args = [int(v) for v in (n_prn, n_freq, nsamp, k, guard)]
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in args):
+            raise GpsJamError(-5, "unsupported: an argument outside int32")
+        self._check(self._lib.gj_acq_peaks_dev(self._ctx, _ptr(d_power) or None, *args, _ptr(d_peaks) or None, _ptr(d_floor) or None))
+
     def corr_bank_dev(self, d_iq, nbytes, first_sample, n_samples, block_samples, d_codes, n_code_rows, d_channels, n_channels,
                       taps, d_out):
         """gj_corr_bank_dev: int32 (I, Q) of every channel, block and tap into d_out, on the context's stream; ``taps`` is a

@@ -181,6 +181,7 @@ GJ_CORR_MAX_CHANNELS = 64
 GJ_CORR_MAX_SAMPLES = 1 << 28
 GJ_CORR_MAX_CODE_STEP = 1 << 34
 GJ_CORR_CODE_LEN = 1023
+GJ_ACQ_MAX_PEAKS = 8
 GJ_CORR_COS_TABLE = (32, 30, 23, 12, 0, -12, -23, -30, -32, -30, -23, -12, 0, 12, 23, 30)
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
@@ -282,6 +283,8 @@ SIGNATURES = {
     "gj_acq_workspace": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "gj_acq_series_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _d, _f, _vp]),
     "gj_acq_series_workspace": (_sz, [_vp, _i, _i, _i, _i, _i, _i]),
+    "gj_acq_peaks_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gj_acq_peaks_workspace": (_sz, [_vp, _i, _i]),
     "gj_comm_unique_id": (_i, [_vp]),
     "gj_comm_init_rank": (_i, [_vp, _vp, _i, _i, C.POINTER(_vp)]),
     "gj_comm_rank": (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),

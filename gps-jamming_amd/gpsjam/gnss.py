@@ -14,7 +14,9 @@ at start-up, in a few microseconds per channel (GpsJammerApp/backend/):
 ``AcqSearch.series`` runs the search epoch after epoch over a whole capture (``gj_acq_series_dev``), and
 ``telemetry`` turns the result into gnssdec-shaped records for the drop-in worker's detector.  The C/N0 there is
 the acquisition's 10 log10(maxP / meanP / ctime), not gnssdec's tracking SNR: comparable between the epochs of one
-capture, not with gnssdec's numbers.
+capture, not with gnssdec's numbers.  ``AcqSearch.peaks`` keeps the K largest peaks of every PRN's surface at code phases
+a guard apart (``gj_acq_peaks_dev``) and tests each against ``peak_threshold``, a ratio to the floor that needs no
+calibration: the second signal of a PRN that is in the air twice is the second peak.
 
 Nothing here is a CPU fallback for the kernels: without the HIP library ``AcqSearch`` cannot be built.
 """
@@ -22,6 +24,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import Iterator, List, Sequence
 
@@ -144,6 +147,61 @@ class AcqResult:
 
 
 @dataclass
+class AcqPeak:
+    power: float
+    ratio: float             # power / the PRN's floor (``AcqPeaks.mean_power``)
+    code_index: int
+    freq_index: int
+    doppler_hz: float
+    significant: bool        # ratio > peak_threshold(steps, n_freq nsamp, pfa)
+
+
+@dataclass
+class AcqPeaks:
+    """``AcqSearch.peaks`` of one PRN: its ``k`` largest peaks at code phases at least a guard apart, largest first."""
+    prn: int
+    steps: int               # integration steps of the surface: all ``intg`` of them
+    mean_power: float        # the floor: mean of the cells outside every peak's zone
+    peaks: List[AcqPeak]
+
+
+def _erlang_tail(s: int, x: float) -> float:
+    """Q(s, x) = exp(-x) sum_{j < s} x^j / j!: the probability that a sum of ``s`` unit exponentials exceeds x."""
+    if x <= 0.0:
+        return 1.0
+    lx = math.log(x)
+    return math.fsum(math.exp(-x + j * lx - math.lgamma(j + 1.0)) for j in range(int(s)))
+
+
+def peak_threshold(steps: int, n_cells: int, pfa: float = 1e-3) -> float:
+    """The ratio gamma of a cell to the floor above which a peak of a noise-only surface of ``n_cells`` cells has
+    probability at most ``pfa``: n_cells Q(steps, gamma steps) = pfa, by bisection.
+
+    Under noise a correlation sample is a complex Gaussian, its squared magnitude an exponential, and a cell of the
+    surface the sum of ``steps`` of them: divided by the floor (the mean of such cells, ``steps`` in units of one
+    exponential's mean) it exceeds gamma with probability Q(steps, gamma steps).  The union bound over all cells makes
+    ``pfa`` a bound per PRN; neighbouring Doppler bins are correlated, which only makes it conservative.  At one step
+    gamma = ln(n_cells / pfa); 10 steps and 71 x 2048 cells give 3.93."""
+    steps, n_cells, pfa = int(steps), int(n_cells), float(pfa)
+    if steps < 1 or n_cells < 1 or not pfa > 0.0:
+        raise ValueError("steps and n_cells must be at least 1 and pfa positive")
+    if n_cells <= pfa:
+        return 0.0
+    lo, hi = 0.0, 1.0
+    while n_cells * _erlang_tail(steps, hi * steps) > pfa:
+        lo, hi = hi, 2.0 * hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if mid <= lo or mid >= hi:
+            break
+        if n_cells * _erlang_tail(steps, mid * steps) > pfa:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+@dataclass
 class AcqSeries:
     """One search per epoch over a capture: arrays [n_epochs][n_prn] (PRNs in ``prns`` order), and per epoch its
     first sample and that sample's time from the start of the capture."""
@@ -213,14 +271,17 @@ class AcqSearch:
 
     def search_dev(self, d_iq, nbytes: int, first_sample: int = 0, d_power=None):
         """Enqueue one search (no host synchronisation); results land in ``self.d_out``."""
+        self._search_dev(d_iq, nbytes, first_sample, d_power, self.threshold, self.d_out)
+
+    def _search_dev(self, d_iq, nbytes, first_sample, d_power, threshold, d_out):
         from . import _ptr
         self.dev._check(self.dev._lib.gj_acq_search_dev(
             self.dev._ctx, _ptr(d_iq), int(nbytes), int(first_sample), self.nsamp, self.intg, self.d_codes.ptr,
-            len(self.prns), self.d_phase.ptr, len(self.freqs), self.nsampchip, self.ctime, self.threshold,
-            self.d_out.ptr, _ptr(d_power) or None))
+            len(self.prns), self.d_phase.ptr, len(self.freqs), self.nsampchip, self.ctime, threshold,
+            d_out.ptr, _ptr(d_power) or None))
 
-    def results(self) -> List[AcqResult]:
-        raw = self.d_out.download(np.uint8, C.sizeof(_AcqStruct) * len(self.prns)).tobytes()
+    def results(self, d_out=None) -> List[AcqResult]:
+        raw = (d_out or self.d_out).download(np.uint8, C.sizeof(_AcqStruct) * len(self.prns)).tobytes()
         out = []
         for k, prn in enumerate(self.prns):
             r = _AcqStruct.from_buffer_copy(raw, k * C.sizeof(_AcqStruct))
@@ -242,6 +303,45 @@ class AcqSearch:
             if want_power:
                 return res, d_power.download(np.float64).reshape(len(self.prns), len(self.freqs), self.nsamp)
         return res
+
+    def peaks(self, capture, first_sample: int = 0, k: int = 2, guard=None, pfa: float = 1e-3, want_results: bool = False):
+        """The ``k`` largest peaks of every PRN's surface at code phases more than ``guard`` samples apart (default
+        2 nsampchip: checkacquisition's zone), largest first: a second signal of one PRN -- a counterfeit above the
+        authentic one -- is the second peak.  The search runs with a threshold that never passes, so every PRN
+        integrates all ``intg`` steps (``self.threshold`` and ``self.d_out`` are left alone); gj_acq_peaks_dev reduces
+        the surface where it lies.  A peak is ``significant`` when its ratio to the floor exceeds
+        ``peak_threshold(steps, n_freq nsamp, pfa)``.  One ``AcqPeaks`` per PRN; ``want_results``: also the
+        ``AcqResult`` records of the same search, whose maximum is peak 0."""
+        nbytes = getattr(capture, "nbytes", None)
+        if nbytes is None:
+            nbytes = capture.numel() * capture.element_size()
+        k = int(k)
+        guard = 2 * self.nsampchip if guard is None else int(guard)
+        n_prn, n_freq = len(self.prns), len(self.freqs)
+        from . import ACQ_FLOOR_DTYPE, ACQ_MAX_PEAKS, ACQ_PEAK_DTYPE
+        held = min(max(k, 1), ACQ_MAX_PEAKS)           # a k outside 1 .. ACQ_MAX_PEAKS is the library's to refuse
+        dev = self.dev
+        with dev.alloc(8 * n_prn * n_freq * self.nsamp) as d_power, dev.alloc(C.sizeof(_AcqStruct) * n_prn) as d_out, \
+                dev.alloc(16 * n_prn * held) as d_peaks, dev.alloc(16 * n_prn) as d_floor:
+            dev.timer_start()
+            self._search_dev(capture, nbytes, first_sample, d_power, float("inf"), d_out)
+            dev.acq_peaks_dev(d_power, n_prn, n_freq, self.nsamp, k, guard, d_peaks, d_floor)
+            dev.last_kernel_ms = dev.timer_stop()
+            results = self.results(d_out)
+            pk = d_peaks.download(ACQ_PEAK_DTYPE, n_prn * k).reshape(n_prn, k)
+            fl = d_floor.download(ACQ_FLOOR_DTYPE, n_prn)
+        out, gamma = [], {}
+        for p, r in enumerate(results):
+            if r.steps not in gamma:
+                gamma[r.steps] = peak_threshold(r.steps, n_freq * self.nsamp, pfa)
+            mean = float(fl["mean_power"][p])
+            peaks = []
+            for rec in pk[p]:
+                ratio = float(rec["power"]) / mean if mean > 0.0 else float("inf")
+                peaks.append(AcqPeak(float(rec["power"]), ratio, int(rec["code_index"]), int(rec["freq_index"]),
+                                     float(self.freqs[int(rec["freq_index"])]), ratio > gamma[r.steps]))
+            out.append(AcqPeaks(r.prn, r.steps, mean, peaks))
+        return (out, results) if want_results else out
 
     def series_workspace(self, n_epochs: int, epochs_per_launch: int = 0) -> int:
         return int(self.dev._lib.gj_acq_series_workspace(self.dev._ctx, self.nsamp, len(self.freqs), len(self.prns),

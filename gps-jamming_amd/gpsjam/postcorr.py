@@ -165,13 +165,15 @@ def tap_periods(bank, tap: int, starts) -> List[np.ndarray]:
     return [periods(row, s) for row, s in zip(z, starts)]
 
 
-def observe(dev, capture, search, first_sample: int = 0, duration_s: float = 0.1) -> List[Observation]:
+def observe(dev, capture, search, first_sample: int = 0, duration_s: float = 0.1, results=None) -> List[Observation]:
     """The chain on a resident capture (or host bytes): acquisition at ``first_sample``; a bank at each bin's Doppler
     over ``duration_s``; the residual Doppler of each PRN and, from the early and late taps, the fraction of a sample by
     which the acquisition's code phase is off (``code_shift``); a bank again at the refined Doppler and code phase.
-    One ``Observation`` per acquired PRN, in the search's order; its prompts are one per code period of that PRN."""
+    One ``Observation`` per acquired PRN, in the search's order; its prompts are one per code period of that PRN.
+    ``results``: ``gnss.AcqResult`` records to use in place of ``search.search`` -- the candidates of a K-peak search,
+    say, in which a PRN may stand twice; at most as many acquired ones as one bank takes channels."""
     with dev._resident(capture) as cap:
-        results = search.search(cap, first_sample)
+        results = search.search(cap, first_sample) if results is None else list(results)
         prns, chans = channels_from_acq(search, results, first_sample)
         if not prns:
             return []

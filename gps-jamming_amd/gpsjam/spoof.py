@@ -11,10 +11,13 @@ deployment ``gpsjam.local`` holds).
 
 Limits.  One baseline measures one angle: it cannot separate a spoofer from satellites that happen to share its phase
 cone, and ``p_chance`` is the price list for that.  Fewer than ``min_common`` (4) acquired PRNs give no verdict
-(``spoofed`` is None).  A spoofer that overpowers the authentic signals is what the acquisition finds, and the weaker
-authentic peak of the same PRN is not searched for: a second-peak search is out of scope here.
+(``spoofed`` is None).  A spoofer that overpowers the authentic signals is what the acquisition finds: ``scan`` sees one
+peak per PRN, the counterfeit one, and loses a PRN whose two copies share a Doppler bin (the weaker one is the peak
+test's second power).  ``scan_peaks`` takes its candidates from the K-peak search instead (``gnss.AcqSearch.peaks``, up to
+``k`` per PRN), and names, next to the counterfeit signals in the common arc, the authentic ones outside it.  Two
+signals of one PRN closer than the guard (2 samples per chip either side) are one peak to it.
 
-    python -m gpsjam.spoof A.bin B.bin
+    python -m gpsjam.spoof A.bin B.bin [--peaks K]
 """
 from __future__ import annotations
 
@@ -50,13 +53,13 @@ class SpoofReport(NamedTuple):
     spoofed: Optional[bool]      # None: fewer than min_common PRNs, no verdict
 
 
-def pair_phases(dev, a, b, search, first_sample: int = 0, duration_s: float = 0.1) -> List[PairPhase]:
+def pair_phases(dev, a, b, search, first_sample: int = 0, duration_s: float = 0.1, results=None) -> List[PairPhase]:
     """Acquire on ``a`` (``postcorr.observe``: the channels at the refined Doppler) and run the SAME channels on ``b``.
     z_p = sum_k P_b[k] conj(P_a[k]): navigation bits and whatever Doppler is left are common to both antennas and
     cancel, block by block.  Per acquired PRN ``phase = arg z_p`` and
-    ``coherence = |z_p| / sqrt(sum |P_a|^2 sum |P_b|^2)``."""
+    ``coherence = |z_p| / sqrt(sum |P_a|^2 sum |P_b|^2)``.  ``results``: as in ``postcorr.observe``."""
     with dev._resident(a) as cap_a, dev._resident(b) as cap_b:
-        obs = postcorr.observe(dev, cap_a, search, first_sample, duration_s)
+        obs = postcorr.observe(dev, cap_a, search, first_sample, duration_s, results)
         if not obs:
             return []
         B = postcorr.block_samples(search)
@@ -129,6 +132,79 @@ def scan(dev, a, b, search=None, tol: float = 0.15, min_common: int = 4, first_s
                        np.array([f.cn0_dbhz for f in found]), [prns[i] for i in common.members], common.p_chance, verdict)
 
 
+class PeakCandidate(NamedTuple):
+    """One significant peak of the K-peak search, measured on both antennas."""
+    prn: int
+    code_index: int      # the peak's: samples after ``first_sample`` at which the code starts
+    doppler_hz: float    # the bin's Doppler plus the residual
+    cn0_dbhz: float      # at antenna a
+    phase: float         # antenna b against antenna a, rad
+    coherence: float
+    ratio: float         # the peak's power over the surface's floor
+
+
+class PeakSpoofReport(NamedTuple):
+    candidates: List[PeakCandidate]
+    common: List[int]                    # indices into ``candidates`` of the largest set within one arc
+    common_prns: List[int]               # their PRNs, each once
+    p_chance: float
+    spoofed: Optional[bool]              # None: fewer than min_common distinct PRNs, no verdict
+    counterfeit: List[PeakCandidate]     # when spoofed: the candidates in the arc
+    authentic: List[PeakCandidate]       # when spoofed: the candidates outside it of PRNs that have one inside
+
+
+BANK_CHANNELS = 64                       # GJ_CORR_MAX_CHANNELS: candidates per bank
+
+
+def pair_phases_peaks(dev, a, b, search, k: int = 2, pfa: float = 1e-3, first_sample: int = 0,
+                      duration_s: float = 0.1) -> List[PeakCandidate]:
+    """``pair_phases`` on the candidates of ``search.peaks(a, first_sample, k, pfa=pfa)``: every significant peak is a
+    channel of its own, at its code index and its bin's Doppler, so a PRN that is in the air twice stands twice.  The
+    candidates go through ``postcorr.observe`` and the same channels on ``b`` in slices of at most BANK_CHANNELS; phase
+    and coherence are ``pair_phases``'s.  In the search's PRN order, a PRN's peaks largest first."""
+    with dev._resident(a) as cap_a, dev._resident(b) as cap_b:
+        found = [(p.prn, pk) for p in search.peaks(cap_a, first_sample, k, pfa=pfa) for pk in p.peaks if pk.significant]
+        out = []
+        for at in range(0, len(found), BANK_CHANNELS):
+            part = found[at:at + BANK_CHANNELS]
+            results = [gnss.AcqResult(prn, True, pk.ratio, 0.0, pk.code_index, pk.freq_index, pk.doppler_hz, 0, pk.power, 0.0, 0.0)
+                       for prn, pk in part]
+            for (prn, pk), f in zip(part, pair_phases(dev, cap_a, cap_b, search, first_sample, duration_s, results)):
+                out.append(PeakCandidate(prn, pk.code_index, f.doppler_hz, f.cn0_dbhz, f.phase, f.coherence, pk.ratio))
+    return out
+
+
+def scan_peaks(dev, a, b, search=None, k: int = 2, tol: float = 0.15, min_common: int = 4, pfa: float = 1e-3,
+               first_sample: int = 0, duration_s: float = 0.1) -> PeakSpoofReport:
+    """``pair_phases_peaks`` and ``common_direction`` over ALL candidates.  A PRN counts once toward ``min_common``,
+    however many of its candidates lie in the arc: ``spoofed`` is None when fewer than ``min_common`` distinct PRNs
+    have a candidate at all, and otherwise whether that many distinct PRNs share the arc.  When spoofed, ``counterfeit``
+    lists the candidates in the arc and ``authentic`` the candidates outside it of PRNs that also have one inside: the
+    signals a receiver should go back to.  ``search``: as in ``scan``."""
+    own = search is None
+    if own:
+        search = gnss.AcqSearch(dev)
+    try:
+        found = pair_phases_peaks(dev, a, b, search, k, pfa, first_sample, duration_s)
+    finally:
+        if own:
+            search.close()
+    common = common_direction([f.phase for f in found], tol)
+    inside = sorted({found[i].prn for i in common.members})
+    verdict = None if len({f.prn for f in found}) < int(min_common) else len(inside) >= int(min_common)
+    counterfeit = [found[i] for i in common.members] if verdict else []
+    members = set(common.members)
+    authentic = [f for i, f in enumerate(found) if i not in members and f.prn in inside] if verdict else []
+    return PeakSpoofReport(found, list(common.members), inside, common.p_chance, verdict, counterfeit, authentic)
+
+
+def _print_candidates(title, rows):
+    print(f"{title}: {len(rows)}")
+    for c in rows:
+        print(f"  PRN {c.prn:2d}  code {c.code_index:5d}  Doppler {c.doppler_hz:+9.1f} Hz  C/N0 {c.cn0_dbhz:5.1f} dB-Hz  "
+              f"phase {c.phase:+7.3f} rad  coherence {c.coherence:5.3f}  peak/floor {c.ratio:6.1f}")
+
+
 def main(argv=None) -> int:
     import argparse
     from . import Device
@@ -141,14 +217,29 @@ def main(argv=None) -> int:
     ap.add_argument("--duration", type=float, default=0.1, help="seconds")
     ap.add_argument("--fs", type=float, default=2.048e6)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--peaks", type=int, default=0, metavar="K",
+                    help="search K peaks per PRN and list counterfeit and authentic signals of the same PRN apart")
+    ap.add_argument("--pfa", type=float, default=1e-3, help="with --peaks: false-alarm bound per PRN of a significant peak")
     args = ap.parse_args(argv)
     with Device(args.device) as dev:
         search = gnss.AcqSearch(dev, fs=args.fs)
         try:
             with dev.capture(args.a) as cap_a, dev.capture(args.b) as cap_b:
-                rep = scan(dev, cap_a, cap_b, search, args.tol, args.min_common, args.first_sample, args.duration)
+                if args.peaks:
+                    rep = scan_peaks(dev, cap_a, cap_b, search, args.peaks, args.tol, args.min_common, args.pfa,
+                                     args.first_sample, args.duration)
+                else:
+                    rep = scan(dev, cap_a, cap_b, search, args.tol, args.min_common, args.first_sample, args.duration)
         finally:
             search.close()
+    if args.peaks:
+        _print_candidates(f"{args.a} / {args.b}: significant peaks on the first antenna (up to {args.peaks} per PRN)", rep.candidates)
+        verdict = "no verdict (too few PRNs)" if rep.spoofed is None else ("SPOOFED" if rep.spoofed else "not flagged")
+        print(f"largest common arc (+-{args.tol} rad): {len(rep.common_prns)} PRN(s) {rep.common_prns}, chance {rep.p_chance:.3g}: {verdict}")
+        if rep.spoofed:
+            _print_candidates("counterfeit (in the arc)", rep.counterfeit)
+            _print_candidates("authentic (outside the arc, same PRNs)", rep.authentic)
+        return 0
     print(f"{args.a} / {args.b}: {len(rep.prns)} PRN(s) acquired on the first antenna")
     for prn, ph, co, c in zip(rep.prns, rep.phase, rep.coherence, rep.cn0):
         mark = " *" if prn in rep.common_prns and len(rep.common_prns) >= args.min_common else ""

@@ -1112,6 +1112,41 @@ int gj_acq_series_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t fi
  * 0 for arguments it would refuse by sign. */
 size_t gj_acq_series_workspace(gj_ctx* ctx, int nsamp, int n_freq, int n_prn, int intg, int n_epochs,
                                int epochs_per_launch);
+/* K-peak search: the k largest peaks of every PRN's power surface under successive column exclusion, and the floor
+ * outside all of them.  checkacquisition (sdracq.c:52-84) keeps one peak per PRN; a second signal of the same PRN --
+ * a counterfeit above the authentic one -- is a second peak of the same surface, at another code phase.
+ *
+ * d_power: double[n_prn][n_freq][nsamp], as gj_acq_search_dev writes it; cell (f, c) has the flat index f * nsamp + c.
+ * For every PRN, j = 0 .. k - 1:
+ *   peak j   = the cell of largest power among the columns (code indices) c not excluded by peaks 0 .. j - 1; of
+ *              equal powers the smallest flat index wins (checkacquisition's first maximum, maxvd);
+ *   excluded by a peak at code index c0 are the columns c with min(|c - c0|, nsamp - |c - c0|) <= guard, in EVERY
+ *              Doppler row (a signal's Doppler sidelobes sit at its own code phase).  With guard = 2 * nsampchip these
+ *              are the indices checkacquisition drops, its wrapped case included;
+ *   floor    = the mean of the n_freq * kept_columns cells of the columns no peak excludes.
+ * Powers are finite and >= 0 (what the search writes); on anything else the call still writes its own records only.
+ * Peaks are exact (comparisons only); the floor is a sum of doubles in a fixed order, equal from call to call and
+ * within n_freq * kept_columns * 2^-53 relative of any other order.
+ *
+ * Limits: nsamp 8 .. 65536 (any value), n_freq 1 .. 4096, k 1 .. GJ_ACQ_MAX_PEAKS (GJ_ERR_UNSUPPORTED); n_prn >= 1,
+ * guard >= 0, k * (2 * guard + 1) < nsamp, no null pointer, all three buffers 8-byte aligned (GJ_ERR_INVALID).  A
+ * refused call enqueues nothing.  Two launches on the context's stream, no atomics, no memset; allocates nothing when
+ * gj_acq_peaks_workspace bytes were reserved (gj_reserve). */
+#define GJ_ACQ_MAX_PEAKS 8
+typedef struct gj_acq_peak {          /* 16 bytes */
+    double power;
+    int32_t code_index;
+    int32_t freq_index;
+} gj_acq_peak;
+typedef struct gj_acq_floor {         /* 16 bytes */
+    double mean_power;
+    int32_t kept_columns;
+    int32_t reserved;                 /* 0 */
+} gj_acq_floor;
+int gj_acq_peaks_dev(gj_ctx* ctx, const double* d_power, int n_prn, int n_freq, int nsamp, int k, int guard,
+                     gj_acq_peak* d_peaks /* [n_prn][k] */, gj_acq_floor* d_floor /* [n_prn] */);
+/* The workspace gj_acq_peaks_dev ensures for these arguments; 0 for arguments it would refuse. */
+size_t gj_acq_peaks_workspace(gj_ctx* ctx, int nsamp, int n_prn);
 
 /* ------------------------------------------------- collectives (RCCL over xGMI) ------- */
 /* One communicator rank per GPU / process, for hosts without torch.distributed.  The path
