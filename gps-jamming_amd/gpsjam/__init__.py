@@ -31,7 +31,8 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "ridge_frames", "EXCISE_DTYPE", "excise_frames", "SpectralKurtosis", "sk_rows", "ChirpScan", "CHIRP_DTYPE",
            "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks", "FINE_BLOCK", "FINE_MAX_HALF", "fine_blocks", "FineCorr",
            "CrossSpectrum", "csd_rows", "CANCEL_DTYPE", "CORR_MAX_BLOCK", "CORR_CHANNEL_DTYPE", "corr_blocks", "CorrBank",
-           "ACQ_MAX_PEAKS", "ACQ_PEAK_DTYPE", "ACQ_FLOOR_DTYPE"]
+           "ACQ_MAX_PEAKS", "ACQ_PEAK_DTYPE", "ACQ_FLOOR_DTYPE", "SUB_BLOCK", "SUB_DTYPE", "SUB_FRAC", "SUB_MAX_AMP",
+           "subtract_blocks"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -247,6 +248,20 @@ class CorrBank(NamedTuple):
         """complex128[n_channels][n_blocks]: I + jQ of the tap at ``offset`` samples (default: the prompt)."""
         j = self.taps.index(int(offset))
         return self.iq[:, :, j, 0].astype(np.float64) + 1j * self.iq[:, :, j, 1].astype(np.float64)
+
+
+SUB_BLOCK = _ffi.GJ_SUB_BLOCK
+SUB_FRAC = _ffi.GJ_SUB_FRAC
+SUB_MAX_AMP = _ffi.GJ_SUB_MAX_AMP
+SUB_DTYPE = np.dtype([("total", np.uint64), ("removed", np.uint64), ("n_clipped", np.int32), ("reserved", np.int32)])
+
+
+def subtract_blocks(n_samples: int) -> int:
+    """Records of the counterfeit-signal subtraction over n_samples: one per SUB_BLOCK samples, the last one ragged
+    (gj_subtract_blocks)."""
+    if not 0 <= int(n_samples) < 2 ** 64:
+        return 0
+    return int(_ffi.load().gj_subtract_blocks(int(n_samples)))
 
 
 ACQ_MAX_PEAKS = _ffi.GJ_ACQ_MAX_PEAKS
@@ -1337,6 +1352,39 @@ class Device:
             iq = d_out.download(np.int32, 2 * rec.size * blocks * len(taps)).reshape(rec.size, blocks, len(taps), 2)
         return CorrBank(iq, taps, block_samples, n_samples)
 
+    def subtract(self, capture, channels, codes, amplitudes, first_sample: int = 0, n_samples: Optional[int] = None,
+                 block_samples: int = 256, dither: bool = True, seed: int = 0):
+        """Counterfeit-signal subtraction (gj_subtract_dev): the replicas of ``channels`` -- each its code times its
+        carrier times one complex amplitude per ``block_samples`` samples -- taken off samples first_sample ..
+        + n_samples of ``capture`` (default: to the end).  ``capture``, ``channels`` and ``codes`` as in ``corr_bank``;
+        ``amplitudes``: int32[n_channels][corr_blocks(n_samples, block_samples)][2] (aI, aQ) in units of 2^-SUB_FRAC,
+        what ``gpsjam.postcorr.amplitudes`` makes of a bank's prompts, on the host or in a device buffer; ``dither``:
+        the replica is brought down to whole LSB by a dithered floor (seeded by ``seed``) instead of rounding.  The
+        channel fields are checked HERE, on the host (GJ_ERR_INVALID), as in ``corr_bank``.  Returns
+        ``(cleaned, records)``: the cleaned range as a resident ``Capture`` of its own (the caller frees it) and one
+        SUB_DTYPE record per SUB_BLOCK samples."""
+        first_sample, block_samples = int(first_sample), int(block_samples)
+        with contextlib.ExitStack() as temps:
+            cap = temps.enter_context(self._resident(capture))
+            n_samples = max(0, cap.nsamples - first_sample) if n_samples is None else int(n_samples)
+            if isinstance(codes, tuple):
+                d_codes, n_rows = codes[0], int(codes[1])
+            else:
+                host = np.ascontiguousarray(codes, np.int16)
+                if host.ndim != 2 or host.shape[1] != _ffi.GJ_CORR_CODE_LEN:
+                    raise ValueError(f"codes must be int16[rows][{_ffi.GJ_CORR_CODE_LEN}]")
+                n_rows = int(host.shape[0])
+                d_codes = temps.enter_context(DevBuf(self, max(host.nbytes, 2))).upload(host)
+            rec = _corr_channels(channels, n_rows)
+            blocks = corr_blocks(n_samples, block_samples)
+            d_amp = self._on_device(temps, amplitudes, np.int32, 2 * rec.size * blocks, "amplitudes",
+                                    f"{rec.size} channels of {blocks} blocks take {2 * rec.size * blocks}")
+            d_ch = temps.enter_context(DevBuf(self, max(rec.nbytes, 32))).upload(rec)
+            self._count("subtract")
+            return self._cleaned(n_samples, subtract_blocks(n_samples), SUB_DTYPE, lambda d_out, d_rec: self.subtract_dev(
+                cap, cap.nbytes, first_sample, n_samples, block_samples, d_codes, n_rows, d_ch, rec.size, d_amp,
+                _ffi.GJ_SUB_DITHER if dither else 0, seed, d_out, d_rec))
+
     def acq_peaks(self, power, k: int = 2, guard: int = 4, shape=None):
         """The K-peak search (gj_acq_peaks_dev) over power surfaces double[n_prn][n_freq][nsamp]: per PRN the ``k``
         largest peaks under successive exclusion of the columns within ``guard`` (circular) of a peak already taken, and
@@ -1386,6 +1434,15 @@ class Device:
         self._check(self._lib.gj_corr_bank_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples),
                                                int(block_samples), _ptr(d_codes), int(n_code_rows), _ptr(d_channels),
                                                int(n_channels), arr, len(taps), _ptr(d_out)))
+
+    def subtract_dev(self, d_iq, nbytes, first_sample, n_samples, block_samples, d_codes, n_code_rows, d_channels, n_channels,
+                     d_amp, flags, seed, d_out, d_blocks=None):
+        """gj_subtract_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 24-byte record (SUB_DTYPE) per
+        SUB_BLOCK samples into d_blocks, on the context's stream; ``seed`` is taken modulo 2^32."""
+        self._check(self._lib.gj_subtract_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples),
+                                              int(block_samples), _ptr(d_codes), int(n_code_rows), _ptr(d_channels),
+                                              int(n_channels), _ptr(d_amp), int(flags), int(seed) & 0xFFFFFFFF, _ptr(d_out),
+                                              _ptr(d_blocks) or None))
 
     def xcorr_fine_dev(self, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, lag_center, half_width, d_total,
                        d_blocks=None):

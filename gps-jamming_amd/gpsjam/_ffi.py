@@ -162,6 +162,11 @@ class CorrChannel(C.Structure):
                 ("code_row", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SubtractBlock(C.Structure):
+    """gj_subtract_block: one GJ_SUB_BLOCK-sample record of the counterfeit-signal subtraction (include/gpsjam.h)."""
+    _fields_ = [("total", C.c_uint64), ("removed", C.c_uint64), ("n_clipped", C.c_int32), ("reserved", C.c_int32)]
+
+
 GJ_CP_ODD_CHUNK_ZERO = 1
 GJ_WELCH_SHIFT = 1
 GJ_MAX_ANTENNAS = 16
@@ -182,6 +187,10 @@ GJ_CORR_MAX_SAMPLES = 1 << 28
 GJ_CORR_MAX_CODE_STEP = 1 << 34
 GJ_CORR_CODE_LEN = 1023
 GJ_ACQ_MAX_PEAKS = 8
+GJ_SUB_BLOCK = 4096
+GJ_SUB_FRAC = 16
+GJ_SUB_MAX_AMP = 1 << 19
+GJ_SUB_DITHER = 1
 GJ_CORR_COS_TABLE = (32, 30, 23, 12, 0, -12, -23, -30, -32, -30, -23, -12, 0, 12, 23, 30)
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
@@ -304,6 +313,8 @@ SIGNATURES = {
     "gj_xcorr_fine_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _sz, C.c_int32, _i, _vp, _vp]),
     "gj_corr_blocks": (_sz, [_sz, _i]),
     "gj_corr_bank_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
+    "gj_subtract_blocks": (_sz, [_sz]),
+    "gj_subtract_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _i, _vp, _i, _vp, _i, C.c_uint32, _vp, _vp]),
     "gj_pack_result_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gj_synth_u8_dev": (_i, [_vp, C.POINTER(SynthParams), C.c_int64, _sz, _vp]),
 }

@@ -9,8 +9,9 @@ measures its spectrum, the excisor cleans the whole capture.
     python -m gpsjam.mitigate IN.bin OUT.bin --pulsed [--window W] [--guard G] [--rise-db D]
     python -m gpsjam.mitigate A.bin OUT.bin --spatial B.bin [--nfft N] [--frames-per-row M] [--p-fa P] [--lag L|k5]
     python -m gpsjam.mitigate A.bin OUT.bin --spatial B.bin --spatial2 C.bin [--lag L|k5] [--lag2 L|k5]
+    python -m gpsjam.mitigate A.bin OUT.bin --spoofed B.bin [--peaks K] [--out-b OUT_B.bin]
 
-writes the cleaned file, byte for byte as long as the input, for gnssdec.
+writes the cleaned file, byte for byte as long as the input (``--spoofed``: as long as the range it cleans), for gnssdec.
 
 A fast sweep crosses hundreds of bins inside one frame and escapes the per-bin mask.  ``clean_swept`` (``--swept``)
 measures its rate (``classify.characterise_swept``), searches a few integer rates around it frame by frame
@@ -34,8 +35,14 @@ them.  With a third antenna ``clean_spatial2`` (``--spatial2``) takes the sums o
 auxiliaries' weighted spectra (``Device.cancel2``, gj_cancel2_dev): two nulls per bin, the noise rising by up to
 1 + |W1|^2 + |W2|^2.
 
-Nothing here computes on the CPU but the threshold's arithmetic on one PSD row or one floor value, and the weights'
-on the rows x nfft sums.
+A spoofer is no interference in any of these senses: its signals have the satellites' own codes.  With a second antenna
+``spoof.scan_peaks`` tells them by their common direction, and ``clean_spoofed`` (``--spoofed``) takes them out of both
+captures by successive interference cancellation: each counterfeit signal rebuilt from its correlator outputs
+(``Device.corr_bank``, ``postcorr.amplitudes``) and subtracted (``Device.subtract``, gj_subtract_dev).  A plain
+acquisition on the result locks onto the authentic signals.
+
+Nothing here computes on the CPU but the threshold's arithmetic on one PSD row or one floor value, the weights'
+on the rows x nfft sums, and the amplitudes' on a hundred prompts per signal.
 """
 from __future__ import annotations
 
@@ -380,6 +387,49 @@ def clean_spatial2(dev, main, aux_b, aux_c, nfft: int = 1024, frames_per_row: in
     return CleanedSpatial2(cleaned, rec, weights, scans[0], cancelled, suppression, True, "", scans[1], scans[2])
 
 
+class CleanedSpoofed(NamedTuple):
+    """Result of ``clean_spoofed``: the cleaned ranges of both antennas as resident ``Capture``s of their own (the caller
+    frees them), the ``spoof.PeakSpoofReport`` they were cleaned by, one ``spoof.Removal`` per counterfeit signal and
+    antenna, and the SUB_DTYPE records of both subtractions.  ``report.spoofed`` False or None: nothing was removed, the
+    ranges are byte for byte the input's and the removal lists are empty."""
+    capture_a: Capture
+    capture_b: Capture
+    report: object
+    removals_a: List
+    removals_b: List
+    records_a: np.ndarray
+    records_b: np.ndarray
+
+
+def clean_spoofed(dev, a, b, k: int = 2, search=None, tol: float = 0.15, min_common: int = 4, pfa: float = 1e-3,
+                  first_sample: int = 0, duration_s: float = 0.1, dither: bool = True) -> CleanedSpoofed:
+    """Two antennas on one clock with the counterfeit signals taken out.  ``spoof.scan_peaks`` (``k`` peaks per PRN) names
+    the counterfeit candidates: the ones that share one inter-antenna phase.  When it says ``spoofed``, ``spoof.remove``
+    takes them out of ``a`` -- re-observed, one amplitude per code period from the correlator bank, replicas subtracted
+    by gj_subtract_dev -- and out of ``b`` with the SAME channels and b's own amplitudes.  What is left holds the
+    authentic signals: a plain acquisition on it finds them, and ``spoof.scan`` on the cleaned pair measures their
+    phases.  ``a`` and ``b``: resident ``Capture``s or host bytes (uploaded once each); ``search``: as in
+    ``spoof.scan``.  The result covers samples first_sample .. + duration_s (``spoof.remove`` states why no more)."""
+    from . import gnss, spoof
+    own = search is None
+    if own:
+        search = gnss.AcqSearch(dev)
+    try:
+        with dev._resident(a) as cap_a, dev._resident(b) as cap_b:
+            report = spoof.scan_peaks(dev, cap_a, cap_b, search, k, tol, min_common, pfa, first_sample, duration_s)
+            fakes = report.counterfeit if report.spoofed else []
+            out_a = spoof.remove(dev, cap_a, fakes, search, first_sample, duration_s, dither)
+            try:
+                out_b = spoof.remove(dev, cap_b, fakes, search, first_sample, duration_s, dither, observations=out_a.observations)
+            except BaseException:
+                out_a.capture.free()
+                raise
+    finally:
+        if own:
+            search.close()
+    return CleanedSpoofed(out_a.capture, out_b.capture, report, out_a.removals, out_b.removals, out_a.records, out_b.records)
+
+
 def main(argv=None) -> int:
     import argparse
     from . import Device
@@ -402,11 +452,47 @@ def main(argv=None) -> int:
     ap.add_argument("--frames-per-row", type=int, default=256, help="--spatial: frame pairs per weight set")
     ap.add_argument("--p-fa", type=float, default=1e-6, help="--spatial: false-alarm probability per cell")
     ap.add_argument("--lag", default="k5", help="--spatial: integer samples by which B lags the input, or k5")
+    ap.add_argument("--spoofed", metavar="B.bin", default=None,
+                    help="take the counterfeit signals out that the input shares with this second antenna's capture (clean_spoofed); "
+                         "the output holds ONLY the cleaned range, --duration seconds (0.1) from --first-sample, not the whole input")
+    ap.add_argument("--peaks", type=int, default=2, metavar="K", help="--spoofed: peaks searched per PRN")
+    ap.add_argument("--out-b", metavar="OUT_B.bin", default=None, help="--spoofed: also write the second antenna's cleaned range")
+    ap.add_argument("--first-sample", type=int, default=0, help="--spoofed: where the cleaned range starts")
+    ap.add_argument("--duration", type=float, default=0.1, help="--spoofed: seconds of the cleaned range")
     args = ap.parse_args(argv)
-    if sum(map(bool, (args.pulsed, args.swept, args.spatial))) > 1:
-        ap.error("--pulsed, --swept and --spatial exclude each other")
+    if sum(map(bool, (args.pulsed, args.swept, args.spatial, args.spoofed))) > 1:
+        ap.error("--pulsed, --swept, --spatial and --spoofed exclude each other")
     if args.spatial2 and not args.spatial:
         ap.error("--spatial2 needs --spatial")
+    if args.spoofed:
+        from . import gnss, spoof
+        with Device(args.device) as dev:
+            search = gnss.AcqSearch(dev, fs=args.fs)
+            try:
+                with dev.capture(args.input) as cap, dev.capture(args.spoofed) as aux:
+                    res = clean_spoofed(dev, cap, aux, k=args.peaks, search=search, first_sample=args.first_sample,
+                                        duration_s=args.duration)
+                    try:
+                        res.capture_a.download().tofile(args.output)
+                        if args.out_b:
+                            res.capture_b.download().tofile(args.out_b)
+                    finally:
+                        res.capture_a.free()
+                        res.capture_b.free()
+            finally:
+                search.close()
+        rep = res.report
+        verdict = "no verdict (too few PRNs)" if rep.spoofed is None else ("SPOOFED" if rep.spoofed else "not flagged")
+        print(f"{args.output}: {res.capture_a.nsamples} samples from sample {args.first_sample}, {len(rep.candidates)} significant peak(s), "
+              f"{len(rep.common_prns)} PRN(s) in one arc: {verdict}" + ("" if rep.spoofed else ", written as it came"))
+        spoof._print_candidates(f"significant peaks on the input (up to {args.peaks} per PRN)", rep.candidates)
+        if rep.spoofed:
+            spoof._print_candidates("counterfeit (in the arc)", rep.counterfeit)
+            spoof._print_candidates("authentic (outside the arc, same PRNs)", rep.authentic)
+            spoof._print_removals("removed from the input", res.removals_a)
+            spoof._print_removals(f"removed from {args.spoofed}", res.removals_b)
+            print(f"bytes clipped: {int(res.records_a['n_clipped'].sum())} and {int(res.records_b['n_clipped'].sum())}")
+        return 0
     if args.spatial2:
         as_lag = lambda v: "k5" if v == "k5" else int(v)
         lag_b, lag_c = as_lag(args.lag), as_lag(args.lag if args.lag2 is None else args.lag2)

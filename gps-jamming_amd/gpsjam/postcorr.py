@@ -16,7 +16,7 @@ from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from . import gnss
+from . import _ffi, gnss
 
 L1_HZ = 1575.42e6              # carrier the code rate is tied to (FREQ1)
 TAPS = (0, -1, 1)              # prompt, late, early: whole samples (gj_corr_bank_dev's taps shift the code by t + d)
@@ -163,6 +163,41 @@ def tap_periods(bank, tap: int, starts) -> List[np.ndarray]:
     """``periods`` of every channel of a ``CorrBank`` at one tap, without the ragged last block."""
     z = bank.tap(tap)[:, :bank.n_samples // bank.block_samples]
     return [periods(row, s) for row, s in zip(z, starts)]
+
+
+MIXER_GAIN = 1042.5            # the mean of C[i]^2 + S[i]^2 over GJ_CORR_COS_TABLE
+SUB_FRAC = _ffi.GJ_SUB_FRAC    # fraction bits of an amplitude of gj_subtract_dev
+
+
+def amplitudes(bank, starts, tap: int = 0) -> np.ndarray:
+    """int32[n_channels][n_blocks][2]: the amplitudes (aI, aQ) with which ``Device.subtract`` takes out what a
+    ``CorrBank`` of the same channels, range and block size saw at ``tap``.  Per channel the least-squares amplitude of
+    the bank's own template, held constant over each code period of that PRN: a period is SUB_BLOCKS blocks from block
+    ``starts[ch]`` (``Observation.first_block``) on, the blocks in front of the first period are a group of their own,
+    so are the blocks behind the last whole one, and the ragged last block counts the samples it holds.  For a group
+
+        alpha = sum of its prompts / (its samples * MIXER_GAIN),    a = round(alpha * 2^SUB_FRAC)
+
+    A sample of the replica alpha c (C - jS) adds alpha (C^2 + S^2) to the prompt; MIXER_GAIN = 1042.5 is the mean of
+    C^2 + S^2 over the 16 table entries (1024 at the multiples of 4, 1044 and 1058 elsewhere: every entry, and so the
+    mean along any carrier step, a still carrier included, is within 1.8 % of 1042.5).  The sum is over the period, not per block: an eighth of
+    a period carries 9 dB less SNR, and amplitudes made per eighth take more noise out with the signal."""
+    z = bank.tap(tap)
+    n_ch, n_blocks = z.shape
+    B, n = int(bank.block_samples), int(bank.n_samples)
+    samples = np.full(n_blocks, B, np.float64)
+    if n_blocks:
+        samples[-1] = n - (n_blocks - 1) * B
+    out = np.zeros((n_ch, n_blocks, 2), np.int32)
+    for k in range(n_ch):
+        s = int(starts[k]) % SUB_BLOCKS
+        edges = ([0] if s else []) + list(range(s, n_blocks, SUB_BLOCKS)) + [n_blocks]
+        for lo, hi in zip(edges, edges[1:]):
+            if hi <= lo:
+                continue
+            alpha = z[k, lo:hi].sum() / (samples[lo:hi].sum() * MIXER_GAIN) * 2.0 ** SUB_FRAC
+            out[k, lo:hi, 0], out[k, lo:hi, 1] = int(round(alpha.real)), int(round(alpha.imag))
+    return out
 
 
 def observe(dev, capture, search, first_sample: int = 0, duration_s: float = 0.1, results=None) -> List[Observation]:

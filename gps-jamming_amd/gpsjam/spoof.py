@@ -17,6 +17,10 @@ test's second power).  ``scan_peaks`` takes its candidates from the K-peak searc
 ``k`` per PRN), and names, next to the counterfeit signals in the common arc, the authentic ones outside it.  Two
 signals of one PRN closer than the guard (2 samples per chip either side) are one peak to it.
 
+``remove`` takes the counterfeit candidates out of a capture -- replicas rebuilt from the bank's prompts and subtracted
+(``Device.subtract``, gj_subtract_dev) -- so that a receiver can go back to the authentic ones;
+``gpsjam.mitigate.clean_spoofed`` does it for both antennas.
+
     python -m gpsjam.spoof A.bin B.bin [--peaks K]
 """
 from __future__ import annotations
@@ -196,6 +200,105 @@ def scan_peaks(dev, a, b, search=None, k: int = 2, tol: float = 0.15, min_common
     members = set(common.members)
     authentic = [f for i, f in enumerate(found) if i not in members and f.prn in inside] if verdict else []
     return PeakSpoofReport(found, list(common.members), inside, common.p_chance, verdict, counterfeit, authentic)
+
+
+class Removal(NamedTuple):
+    """One signal taken out by ``remove``, measured by the bank on the range before and after."""
+    prn: int
+    code_index: int
+    doppler_hz: float        # refined, what the replica was made with
+    cn0_before: float        # moments C/N0 of its prompts, dB-Hz
+    cn0_after: float
+    suppression_db: float    # 10 log10 of the mean |prompt|^2 before over after
+
+
+class Removed(NamedTuple):
+    """Result of ``remove``: the cleaned range as a resident ``Capture`` of its own (the caller frees it), one ``Removal``
+    per candidate, the SUB_DTYPE records of the subtraction and the ``postcorr.Observation`` of every candidate, whose
+    channels the replicas were made with.  Where more than BANK_CHANNELS candidates go out in several passes, ``total``
+    is the input's and ``removed`` and ``n_clipped`` are summed over the passes: every byte changed or clipped counts
+    in the pass that did it."""
+    capture: object
+    removals: List[Removal]
+    records: np.ndarray
+    observations: list
+
+
+def _copy_range(dev, cap, first_sample: int, n: int):
+    """The range as a capture of its own and its records, through the subtraction with one channel of amplitude zero:
+    byte for byte, by the definition (q = floor(d / 65536) = 0).  The library has no device-to-device copy of its own;
+    ``mitigate.clean_spatial`` returns its unflagged copy the same way, through the canceller with zero weights."""
+    ones = np.ones((1, gnss.CA_LEN), np.int16)
+    B = 4096
+    return dev.subtract(cap, [postcorr.Channel(0, 0, 0, 0, 0)], ones, np.zeros((1, -(-n // B), 2), np.int32), first_sample, n, B,
+                        dither=False)
+
+
+def remove(dev, capture, candidates, search, first_sample: int = 0, duration_s: float = 0.1, dither: bool = True,
+           observations=None) -> Removed:
+    """Successive interference cancellation of ``candidates`` (``PeakCandidate``s: ``scan_peaks(...).counterfeit``) from
+    samples first_sample .. + duration_s of ``capture``, open loop: the candidates are observed again
+    (``postcorr.observe(results=...)``: refined Doppler, sub-sample code phase), a one-tap bank at
+    ``postcorr.block_samples`` gives each one's complex prompt per eighth of a code period, ``postcorr.amplitudes``
+    turns them into one amplitude per code period, and ``Device.subtract`` rebuilds the replicas and takes them off
+    the bytes (gj_subtract_dev).  A bank on the cleaned range measures what is left.  At most BANK_CHANNELS candidates
+    go out per pass; more are taken in slices, each from the range the slice before it left.  ``observations``: those of
+    an earlier ``remove`` on another antenna of the same clock -- the candidates are then not observed again, the SAME
+    channels are used, and the amplitudes are this capture's own.  No candidate: the range comes back byte for byte.
+
+    Limits.  One set of channels serves the whole range: 0.1 s is fine, ten seconds of a moving receiver are not.  The
+    replica has the mixer's 16-step carrier: what the bank sees is nulled, about 1 % of the signal's power stays behind
+    as the staircase's harmonics, far from its Doppler.  Per code period one complex dimension of the noise goes out
+    with the signal.  Two copies closer than the K-peak guard are one peak and are removed as one."""
+    candidates = list(candidates)
+    with dev._resident(capture) as cap:
+        first = int(first_sample)
+        n = min(int(round(duration_s * search.fs)), cap.nsamples - first)
+        B, removals, seen, held, records = postcorr.block_samples(search), [], [], None, None
+        period_s = postcorr.SUB_BLOCKS * B / float(search.fs)
+        if not candidates:
+            cleaned, records = _copy_range(dev, cap, first, n)
+            return Removed(cleaned, [], records, [])
+        try:
+            for at in range(0, len(candidates), BANK_CHANNELS):
+                part = candidates[at:at + BANK_CHANNELS]
+                src = cap if held is None else held
+                if observations is None:
+                    results = [gnss.AcqResult(c.prn, True, c.ratio, c.cn0_dbhz, c.code_index,
+                                              int(np.argmin(np.abs(np.asarray(search.freqs) - c.doppler_hz))), c.doppler_hz, 0, 0.0, 0.0, 0.0)
+                               for c in part]
+                    obs = postcorr.observe(dev, src, search, first, duration_s, results)
+                else:
+                    obs = list(observations[at:at + BANK_CHANNELS])
+                chans, rows, starts = [o.channel for o in obs], postcorr.codes([o.prn for o in obs]), [o.first_block for o in obs]
+                before = dev.corr_bank(src, chans, rows, first, n, B, (0,))
+                cleaned, rec = dev.subtract(src, chans, rows, postcorr.amplitudes(before, starts), first, n, B, dither=dither)
+                if records is None:
+                    records = rec                            # ``total`` is the input's: the first pass reads it
+                else:
+                    records["removed"] += rec["removed"]
+                    records["n_clipped"] += rec["n_clipped"]
+                if held is not None:
+                    held.free()
+                held, first = cleaned, 0                     # the cleaned range is a capture of its own, from its sample 0
+                after = dev.corr_bank(held, chans, rows, 0, n, B, (0,))
+                for c, o, pb, pa in zip(part, obs, postcorr.tap_periods(before, 0, starts), postcorr.tap_periods(after, 0, starts)):
+                    mb, ma = float(np.mean(np.abs(pb) ** 2)) if pb.size else 0.0, float(np.mean(np.abs(pa) ** 2)) if pa.size else 0.0
+                    db = float(10.0 * np.log10(mb / ma)) if mb > 0.0 and ma > 0.0 else (float("inf") if mb > 0.0 else 0.0)
+                    removals.append(Removal(o.prn, int(c.code_index), o.doppler_hz, postcorr.cn0(pb, period_s), postcorr.cn0(pa, period_s), db))
+                seen.extend(obs)
+        except BaseException:
+            if held is not None:
+                held.free()
+            raise
+    return Removed(held, removals, records, seen)
+
+
+def _print_removals(title, rows):
+    print(f"{title}: {len(rows)}")
+    for r in rows:
+        print(f"  PRN {r.prn:2d}  code {r.code_index:5d}  Doppler {r.doppler_hz:+9.1f} Hz  C/N0 {r.cn0_before:5.1f} -> {r.cn0_after:5.1f} dB-Hz  "
+              f"suppression {r.suppression_db:5.1f} dB")
 
 
 def _print_candidates(title, rows):

@@ -901,6 +901,71 @@ int gj_corr_bank_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t fir
                      const int32_t* tap_offsets /* HOST array [n_taps], samples */, int n_taps,
                      int32_t* d_out /* [n_channels][gj_corr_blocks][n_taps][2]  I, Q */);
 
+/* ------------------------------------------------- counterfeit-signal subtraction ---- */
+/* The correlator run backwards: the replicas of up to 64 channels, each with one complex amplitude per block, rebuilt
+ * and subtracted from the capture: a cleaned capture, uint8 I/Q again (successive interference cancellation, open
+ * loop).  The terms are the correlator bank's: gj_corr_channel, C = GJ_CORR_COS_TABLE with S[i] = C[(i - 4) & 15], the
+ * chip rule at tap 0 (d = 0), I, Q = byte - 128 WHATEVER gj_set_unpack says, gj_corr_blocks.  gpsjam/postcorr.py
+ * (amplitudes) makes the amplitudes from the bank's prompts; gpsjam/spoof.py (remove) joins the pieces.
+ *
+ * For sample t = 0 .. n_samples-1 of the range and block m = t / B, B = block_samples:
+ *
+ *   a(ch, m)  = clamp(d_amp[ch][m][0..1], -GJ_SUB_MAX_AMP, +GJ_SUB_MAX_AMP)        int32 pairs (aI, aQ)
+ *   c, i      = the bank's chip (+-1) at tap 0 and its carrier index theta >> 28 of channel ch at sample t
+ *   R_I       = sum over ch of c * (aI*C[i] + aQ*S[i])
+ *   R_Q       = sum over ch of c * (aQ*C[i] - aI*S[i])         the replica a * c * (C - jS), scaled by 2^GJ_SUB_FRAC
+ *   d         = 32768 without GJ_SUB_DITHER; with it, per component (comp = 0 for I, 1 for Q):
+ *               k = 2*(first_sample + t) + comp  (uint64),   key = (uint32)k ^ ((uint32)(k >> 32) * 0x9e3779b9) ^ seed
+ *               h: v ^= v>>16; v *= 0x7feb352d; v ^= v>>15; v *= 0x846ca68b; v ^= v>>16  (uint32),   d = h(key) >> 16
+ *   q         = floor((R + d) / 65536)       mathematical floor: R may be negative
+ *   out byte  = clamp(in byte - q, 0, 255)
+ *
+ * |R| <= 64 * 2^19 * 46 = 1 543 503 872 and d < 65536: R + d stays inside int32, every value is an exact integer, and the
+ * bytes do not depend on tiling or order.  The bank's mixer turns the replica back: a sample that holds R / 2^16 alone
+ * adds a (C[i]^2 + S[i]^2) / 2^16 to the channel's prompt, 1042.5 a / 2^16 in the mean over the table, so the amplitude
+ * that takes a signal out is its own prompt sum over samples * 1042.5, times 2^16 (gpsjam.postcorr.amplitudes).
+ * The dither.  A 40 dB-Hz signal is about one LSB and each of its components less than half of one: rounding to
+ * nearest (d = 32768) then subtracts nothing at all.  With d uniform over 0 .. 65535 the expectation of q is R / 65536
+ * exactly.  d is a function of the ABSOLUTE sample index (as the blanker's odd mid-level is), the component and the
+ * seed: a call on a sub-range that starts at a block boundary m0*B, with the channels advanced by m0*B samples and
+ * d_amp offset by m0 blocks, writes the bytes the larger call writes there.
+ *
+ * d_amp: int32[n_channels][gj_corr_blocks(n_samples, B)][2].  Amplitudes are not checked: the clamp is part of the
+ * definition, so INT32_MIN is as good as -GJ_SUB_MAX_AMP.  d_out: 2*n_samples bytes, any alignment (two 16-byte stores per 16
+ * samples where it is 16-byte aligned).  d_blocks (optional, may be NULL; the bytes are the same) receives one record per
+ * GJ_SUB_BLOCK samples of the range, the last one ragged, whatever B is.
+ *
+ * Limits (GJ_ERR_UNSUPPORTED): block_samples a multiple of 16 in 16 .. GJ_CORR_MAX_BLOCK; n_channels
+ * 1 .. GJ_CORR_MAX_CHANNELS; n_samples 1 .. GJ_CORR_MAX_SAMPLES (t*code_step < 2^62).
+ * GJ_ERR_INVALID: a null ctx, d_iq, d_codes, d_channels, d_amp or d_out; an odd d_iq or d_codes, a d_channels
+ * that is not 8-byte aligned, a d_amp that is not 4-byte aligned, a d_blocks that is not 8-byte aligned; n_code_rows < 1;
+ * a flag bit other than GJ_SUB_DITHER; a range that runs past the capture; a d_out whose 2*n_samples bytes overlap
+ * d_iq[0, nbytes) anywhere (in place included).  A refused call enqueues nothing.
+ * The channel fields are in DEVICE memory, as the bank's: Device.subtract (gpsjam/__init__.py) checks them on the host
+ * before it uploads them and raises GJ_ERR_INVALID; and every workgroup of the kernel checks all of them before it reads
+ * a chip: if ANY channel has reserved != 0, a code_row outside 0 .. n_code_rows-1, code_phase >= 1023 * 2^32 or
+ * code_step >= GJ_CORR_MAX_CODE_STEP, the launch writes NOTHING, neither a byte nor a record.
+ * One launch on the context's stream; no workspace, no memset, no atomics: 0 bytes to gj_reserve, the call never
+ * allocates.  Every byte and every record is written by exactly one workgroup. */
+#define GJ_SUB_BLOCK 4096          /* samples per record */
+#define GJ_SUB_FRAC 16             /* fraction bits of an amplitude */
+#define GJ_SUB_MAX_AMP (1 << 19)   /* |aI|, |aQ| after the clamp: 8 LSB of replica per unit of the table */
+#define GJ_SUB_DITHER 1            /* flags */
+typedef struct gj_subtract_block { /* 24 bytes, all exact integers */
+    uint64_t total;      /* sum of (I - 128)^2 + (Q - 128)^2 over the block's input samples */
+    uint64_t removed;    /* sum of (in - out)^2 over both bytes of its samples, after the clamp */
+    int32_t n_clipped;   /* bytes that the clamp to 0 .. 255 changed */
+    int32_t reserved;    /* 0 */
+} gj_subtract_block;
+/* records of the subtraction: ceil(n_samples / GJ_SUB_BLOCK); pure host arithmetic, no context */
+size_t gj_subtract_blocks(size_t n_samples);
+int gj_subtract_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples,
+                    int block_samples, const int16_t* d_codes /* [n_code_rows][1023], +-1 */, int n_code_rows,
+                    const gj_corr_channel* d_channels, int n_channels,
+                    const int32_t* d_amp /* [n_channels][gj_corr_blocks(n_samples, block_samples)][2]  aI, aQ */,
+                    int flags, uint32_t seed, uint8_t* d_out /* [2*n_samples] */,
+                    gj_subtract_block* d_blocks /* [gj_subtract_blocks(n_samples)] or NULL */);
+
 /* ------------------------------------------------- per-stream result vector ---------- */
 /* What one rank sends to rank 0 (gpsjam/sharded.py):
  * double[40 + n_chunks + nperseg + 5*pair_capacity] =
