@@ -5,16 +5,13 @@
 // A workgroup of four waves owns tiles of k = floor(4096 / B) whole record blocks (k B <= 4096 samples).  Thread tid owns
 // the 16 consecutive samples 16 tid .. 16 tid + 15 of the tile; B is a multiple of 16 and a tile starts on a block, so a
 // thread's samples lie in ONE block.
-//   0. once per workgroup: every channel is checked (any bad field: the workgroup returns, nothing is written and no
-//      chip is read), the channels go to LDS, and the code row of every channel is packed to 1023 sign bits (32 words)
-//      with one ballot per 64 chips: 8 KiB for 64 channels, whatever the number of rows;
-//   1. per tile: the thread's 32 bytes come from the capture ONCE, as two 16-byte loads (2-byte aligned: first_sample
-//      may be odd), are unpacked to (I - 128, Q - 128) as two int16 in one word and stay in registers for every channel
-//      and tap: HBM traffic is one pass over the range per call.  Samples past n_samples are the sample zero;
+//   0. once per workgroup: the channels are checked, kept in LDS and their code rows packed to sign bits (replica.h);
+//   1. per tile: the thread's 32 bytes come from the capture ONCE (replica.h), are unpacked to (I - 128, Q - 128) as
+//      two int16 in one word and stay in registers for every channel and tap: HBM traffic is one pass over the range
+//      per call.  Samples past n_samples are the sample zero;
 //   2. per channel: the resampled code of samples tile - 64 .. tile + 4096 + 64 is made once, as +-1 int16, in LDS: a
-//      thread makes 18 consecutive entries, the first phase by one 64-bit multiply and a mod, the others by exact adds
-//      with one conditional subtraction of 1023 * 2^32 (code_step < 2^34 is far below it).  Every tap is then a
-//      whole-sample shift of these entries, the reference's code +- s[i] pointers;
+//      thread makes 18 consecutive entries, the first phase by one 64-bit multiply and a mod, the others by exact
+//      steps (replica.h).  Every tap is then a whole-sample shift of these entries, the reference's code +- s[i] pointers;
 //   3. the carrier: theta = carr_phase + t carr_step in uint32 (wraps as the definition's mod 2^32), the table entry
 //      (C, -S), (S, C) as one 8-byte LDS read, wI and wQ by one v_dot2_i32_i16 each.  |w| <= 5888 is an int16, so two
 //      samples' wI (and wQ) share a word;
@@ -30,31 +27,26 @@
 // last read.
 //
 // Widths.  |I - 128|, |Q - 128| <= 128 and |C[i]| + |S[i]| <= 46: |w| <= 5888.  A thread's sum holds 16 terms (94 208), a
-// record at most 4096: 24 117 248 < 2^31, the header's bound; every partial sum is bounded by the same figure.  Code
-// phase: t < 2^28 and code_step < 2^34 give t code_step < 2^62; with code_phase < 2^42 the sum stays below 2^63.  A
-// phase x is reduced as ((x >> 32) mod 1023) << 32 | low word: x >> 32 < 2^31, a 32-bit remainder by a constant.
+// record at most 4096: 24 117 248 < 2^31, the header's bound; every partial sum is bounded by the same figure.  The
+// channel fields, the code phase and its widths: replica.h.
 //
-// This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it.
-#include "gj_common.h"
+// This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it
+// but k_subtract.hip, which takes g.n_blocks from gj_corr_blocks.
+#include "replica.h"
 
 namespace gj {
 
-constexpr int kCorrThreads = 256;
-constexpr int kCorrRun = 16;                                         // samples of a thread
-constexpr int kCorrTileMax = kCorrThreads * kCorrRun;                // 4096
 constexpr int kCorrGuard = GJ_CORR_MAX_TAP_OFFSET;                   // code entries in front of the tile
 constexpr int kCorrWordsPerThread = 9;                               // 18 code entries
-constexpr int kCorrCodeWords = kCorrThreads * kCorrWordsPerThread;   // 2304 words of two entries
+constexpr int kCorrCodeWords = kReplicaThreads * kCorrWordsPerThread;  // 2304 words of two entries
 constexpr int kCorrCodeLds = kCorrCodeWords + kCorrCodeWords / 8;    // rows of 8 words skewed by one word each
 constexpr int kCorrFieldsMax = 2 * GJ_CORR_MAX_TAPS;
-constexpr unsigned long long kCorrPeriod = (unsigned long long)GJ_CORR_CODE_LEN << 32;
 
-static_assert(GJ_CORR_MAX_BLOCK == kCorrTileMax, "one full block per tile at the most");
-static_assert(sizeof(gj_corr_channel) == 32, "the header's layout");
+static_assert(GJ_CORR_MAX_BLOCK == kReplicaTile, "one full block per tile at the most");
 // the last entry a tap reads: sample 4095 under offset +64, plus the odd shift's extra word
-static_assert((kCorrTileMax - 1 + 2 * kCorrGuard) / 2 + 1 < kCorrCodeWords, "every tap's reads stay inside the entries made");
+static_assert((kReplicaTile - 1 + 2 * kCorrGuard) / 2 + 1 < kCorrCodeWords, "every tap's reads stay inside the entries made");
 static_assert(4096ll * 128 * 46 < (1ll << 31), "a record fits int32");
-static_assert(64ull * GJ_CORR_MAX_CODE_STEP < kCorrPeriod, "the guard's phase is less than one code period");
+static_assert(64ull * GJ_CORR_MAX_CODE_STEP < kReplicaPeriod, "the guard's phase is less than one code period");
 
 struct CorrGeom {
     unsigned long long n_samples, n_blocks, n_tiles;
@@ -64,10 +56,6 @@ struct CorrGeom {
     int group;                   // G: largest power of two <= 64 that divides block_threads
     int n_code_rows, n_channels, n_taps;
     int tap[GJ_CORR_MAX_TAPS];
-};
-
-struct __attribute__((packed, aligned(2))) CorrChunk16 {
-    unsigned x, y, z, w;
 };
 
 // bytes (I, Q) in the low half of `pair` -> I - 128 in bits 0..15, Q - 128 in bits 16..31
@@ -80,11 +68,6 @@ __device__ __forceinline__ int corr_dot2(unsigned a, unsigned b, int acc) {
     int r;
     asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(acc));
     return r;
-}
-
-// x mod 1023 * 2^32 for x < 2^63
-__device__ __forceinline__ unsigned long long corr_mod_period(unsigned long long x) {
-    return ((unsigned long long)((unsigned)(x >> 32) % (unsigned)GJ_CORR_CODE_LEN) << 32) | (x & 0xffffffffull);
 }
 
 __device__ __forceinline__ int corr_code_slot(int word) { return word + (word >> 3); }
@@ -102,14 +85,14 @@ __device__ __forceinline__ int corr_group_sum(int v, int G) {
     }
 }
 
-__global__ __launch_bounds__(kCorrThreads) void corr_bank_kernel(const uint8_t* __restrict__ iq, CorrGeom g,
-                                                                 const int16_t* __restrict__ codes,
-                                                                 const gj_corr_channel* __restrict__ channels,
-                                                                 int32_t* __restrict__ out) {
+__global__ __launch_bounds__(kReplicaThreads) void corr_bank_kernel(const uint8_t* __restrict__ iq, CorrGeom g,
+                                                                    const int16_t* __restrict__ codes,
+                                                                    const gj_corr_channel* __restrict__ channels,
+                                                                    int32_t* __restrict__ out) {
     __shared__ gj_corr_channel chan[GJ_CORR_MAX_CHANNELS];
     __shared__ unsigned code_bits[GJ_CORR_MAX_CHANNELS][32];         // bit c of word w: chip 32 w + c is -1
     __shared__ unsigned code_lds[kCorrCodeLds];                      // two +-1 int16 entries per word, rows skewed
-    __shared__ int sums[kCorrThreads * kCorrFieldsMax];              // [group of threads][field]
+    __shared__ int sums[kReplicaThreads * kCorrFieldsMax];           // [group of threads][field]
     __shared__ uint2 mix[16];                                        // (C, -S), (S, C) as int16 pairs
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -119,8 +102,7 @@ __global__ __launch_bounds__(kCorrThreads) void corr_bank_kernel(const uint8_t* 
     int bad = 0;
     if (tid < g.n_channels) {
         const gj_corr_channel c = channels[tid];
-        bad = c.reserved != 0 || c.code_row < 0 || c.code_row >= g.n_code_rows || c.code_phase >= kCorrPeriod ||
-              c.code_step >= GJ_CORR_MAX_CODE_STEP;
+        bad = GJ_REPLICA_CHANNEL_BAD(c, g.n_code_rows);
         chan[tid] = c;
     }
     if (tid < 16) {
@@ -134,15 +116,7 @@ __global__ __launch_bounds__(kCorrThreads) void corr_bank_kernel(const uint8_t* 
         mix[tid] = uint2{((unsigned)c & 0xffffu) | ((unsigned)(-s) << 16), ((unsigned)s & 0xffffu) | ((unsigned)c << 16)};
     }
     if (__syncthreads_or(bad)) return;
-    for (int item = wave; item < g.n_channels * 16; item += kCorrThreads / 64) {
-        const int ch = item >> 4, chip = (item & 15) * 64 + lane;
-        const int v = chip < GJ_CORR_CODE_LEN ? (int)codes[(size_t)chan[ch].code_row * GJ_CORR_CODE_LEN + chip] : 0;
-        const unsigned long long m = __ballot(v < 0);
-        if (lane == 0) {
-            code_bits[ch][2 * (item & 15)] = (unsigned)m;
-            code_bits[ch][2 * (item & 15) + 1] = (unsigned)(m >> 32);
-        }
-    }
+    replica_pack_codes(codes, chan, code_bits, g.n_channels, wave, lane);
     __syncthreads();
 
     const int tile_samples = g.tile_blocks * g.block_samples;
@@ -151,22 +125,21 @@ __global__ __launch_bounds__(kCorrThreads) void corr_bank_kernel(const uint8_t* 
 
     for (unsigned long long tile = blockIdx.x; tile < g.n_tiles; tile += gridDim.x) {
         const unsigned long long t_tile = tile * (unsigned long long)tile_samples;
-        const long long t0 = (long long)t_tile + kCorrRun * tid;    // this thread's first sample
+        const long long t0 = (long long)t_tile + kReplicaRun * tid; // this thread's first sample
 
         // ---- 1. the thread's samples
-        unsigned x[kCorrRun];
+        unsigned x[kReplicaRun];
 #pragma unroll
-        for (int s = 0; s < kCorrRun; ++s) x[s] = 0u;
-        if (kCorrRun * tid < tile_samples) {
-            if (t0 + kCorrRun <= n) {
-                const CorrChunk16 lo = *reinterpret_cast<const CorrChunk16*>(iq + 2 * t0);
-                const CorrChunk16 hi = *reinterpret_cast<const CorrChunk16*>(iq + 2 * t0 + 16);
-                const unsigned raw[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        for (int s = 0; s < kReplicaRun; ++s) x[s] = 0u;
+        if (kReplicaRun * tid < tile_samples) {
+            if (t0 + kReplicaRun <= n) {
+                unsigned raw[kReplicaRun / 2];
+                replica_load_run(iq + 2 * t0, raw);
 #pragma unroll
-                for (int s = 0; s < kCorrRun; ++s) x[s] = corr_unpack(raw[s >> 1] >> (16 * (s & 1)));
+                for (int s = 0; s < kReplicaRun; ++s) x[s] = corr_unpack(raw[s >> 1] >> (16 * (s & 1)));
             } else {
 #pragma unroll
-                for (int s = 0; s < kCorrRun; ++s)
+                for (int s = 0; s < kReplicaRun; ++s)
                     if (t0 + s < n) x[s] = corr_unpack((unsigned)*reinterpret_cast<const uint16_t*>(iq + 2 * (t0 + s)));
             }
         }
@@ -177,20 +150,17 @@ __global__ __launch_bounds__(kCorrThreads) void corr_bank_kernel(const uint8_t* 
             // ---- 2. the resampled code: entry e is sample t_tile - 64 + e
             {
                 // phase of entry 0: one period is added so that the guard's 64 steps can be taken off
-                const unsigned long long at_tile = corr_mod_period(c.code_phase + t_tile * c.code_step);
-                const unsigned long long entry0 = corr_mod_period(at_tile + kCorrPeriod - (unsigned long long)kCorrGuard * c.code_step);
+                const unsigned long long at_tile = replica_mod_period(c.code_phase + t_tile * c.code_step);
+                const unsigned long long entry0 = replica_mod_period(at_tile + kReplicaPeriod - (unsigned long long)kCorrGuard * c.code_step);
                 const int w0 = kCorrWordsPerThread * tid;
-                unsigned long long ph = corr_mod_period(entry0 + (unsigned long long)(2 * w0) * c.code_step);
+                unsigned long long ph = replica_mod_period(entry0 + (unsigned long long)(2 * w0) * c.code_step);
 #pragma unroll
                 for (int k = 0; k < kCorrWordsPerThread; ++k) {
                     unsigned word = 0;
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const unsigned chip = (unsigned)(ph >> 32);
-                        const unsigned neg = (code_bits[ch][chip >> 5] >> (chip & 31)) & 1u;
-                        word |= (neg ? 0xffffu : 1u) << (16 * h);
-                        ph += c.code_step;
-                        if (ph >= kCorrPeriod) ph -= kCorrPeriod;
+                        word |= (replica_chip_neg(code_bits[ch], ph) ? 0xffffu : 1u) << (16 * h);
+                        ph = replica_step(ph, c.code_step);
                     }
                     if (w0 + k < code_words) code_lds[corr_code_slot(w0 + k)] = word;
                 }
@@ -198,11 +168,11 @@ __global__ __launch_bounds__(kCorrThreads) void corr_bank_kernel(const uint8_t* 
             __syncthreads();
 
             // ---- 3. the carrier
-            unsigned wi[kCorrRun / 2], wq[kCorrRun / 2];
+            unsigned wi[kReplicaRun / 2], wq[kReplicaRun / 2];
             {
                 unsigned theta = c.carr_phase + (unsigned)t0 * c.carr_step;
 #pragma unroll
-                for (int p = 0; p < kCorrRun / 2; ++p) {
+                for (int p = 0; p < kReplicaRun / 2; ++p) {
                     int i2[2], q2[2];
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
@@ -222,18 +192,18 @@ __global__ __launch_bounds__(kCorrThreads) void corr_bank_kernel(const uint8_t* 
 #pragma unroll
             for (int j = 0; j < GJ_CORR_MAX_TAPS; ++j) {
                 if (j < g.n_taps) {
-                    const int e0 = kCorrRun * tid + kCorrGuard + g.tap[j];     // >= 0: |tap| <= 64
+                    const int e0 = kReplicaRun * tid + kCorrGuard + g.tap[j];     // >= 0: |tap| <= 64
                     const int wb = e0 >> 1;
-                    unsigned cw[kCorrRun / 2 + 1];
+                    unsigned cw[kReplicaRun / 2 + 1];
 #pragma unroll
-                    for (int k = 0; k <= kCorrRun / 2; ++k) cw[k] = code_lds[corr_code_slot(wb + k)];
+                    for (int k = 0; k <= kReplicaRun / 2; ++k) cw[k] = code_lds[corr_code_slot(wb + k)];
                     if (e0 & 1) {
 #pragma unroll
-                        for (int k = 0; k < kCorrRun / 2; ++k) cw[k] = (cw[k] >> 16) | (cw[k + 1] << 16);
+                        for (int k = 0; k < kReplicaRun / 2; ++k) cw[k] = (cw[k] >> 16) | (cw[k + 1] << 16);
                     }
                     int si = 0, sq = 0;
 #pragma unroll
-                    for (int p = 0; p < kCorrRun / 2; ++p) {
+                    for (int p = 0; p < kReplicaRun / 2; ++p) {
                         si = corr_dot2(wi[p], cw[p], si);
                         sq = corr_dot2(wq[p], cw[p], sq);
                     }
@@ -244,7 +214,7 @@ __global__ __launch_bounds__(kCorrThreads) void corr_bank_kernel(const uint8_t* 
             }
             __syncthreads();
             const int groups_per_block = g.block_threads / g.group;
-            for (int r = tid; r < g.tile_blocks * fields; r += kCorrThreads) {
+            for (int r = tid; r < g.tile_blocks * fields; r += kReplicaThreads) {
                 const int b = r / fields, f = r - b * fields;
                 const unsigned long long block = tile * (unsigned long long)g.tile_blocks + (unsigned)b;
                 if (block < g.n_blocks) {
@@ -276,28 +246,22 @@ int gj_corr_bank_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t fir
     if (!ctx) return GJ_ERR_INVALID;
     Guard lock(ctx);
     if (!d_iq || !d_codes || !d_channels || !tap_offsets || !d_out) return fail(ctx, GJ_ERR_INVALID, "null buffer");
-    if ((reinterpret_cast<uintptr_t>(d_iq) | reinterpret_cast<uintptr_t>(d_codes)) & 1)
-        return fail(ctx, GJ_ERR_INVALID, "the capture and the codes must be 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_channels) & 7) return fail(ctx, GJ_ERR_INVALID, "channels must be 8-byte aligned");
+    if (int rc = replica_check_alignment(ctx, d_iq, d_codes, d_channels)) return rc;
     if (reinterpret_cast<uintptr_t>(d_out) & 3) return fail(ctx, GJ_ERR_INVALID, "records must be 4-byte aligned");
     if (n_code_rows < 1) return fail(ctx, GJ_ERR_INVALID, "n_code_rows %d", n_code_rows);
-    if (block_samples < 16 || block_samples > GJ_CORR_MAX_BLOCK || block_samples % 16)
-        return fail(ctx, GJ_ERR_UNSUPPORTED, "block_samples %d (a multiple of 16 in 16 .. %d)", block_samples, GJ_CORR_MAX_BLOCK);
+    if (int rc = replica_check_block(ctx, block_samples)) return rc;
     if (n_taps < 1 || n_taps > GJ_CORR_MAX_TAPS) return fail(ctx, GJ_ERR_UNSUPPORTED, "n_taps %d (1 .. %d)", n_taps, GJ_CORR_MAX_TAPS);
     for (int j = 0; j < n_taps; ++j)
         if (tap_offsets[j] < -GJ_CORR_MAX_TAP_OFFSET || tap_offsets[j] > GJ_CORR_MAX_TAP_OFFSET)
             return fail(ctx, GJ_ERR_UNSUPPORTED, "tap offset %d (|d| <= %d)", (int)tap_offsets[j], GJ_CORR_MAX_TAP_OFFSET);
-    if (n_channels < 1 || n_channels > GJ_CORR_MAX_CHANNELS)
-        return fail(ctx, GJ_ERR_UNSUPPORTED, "n_channels %d (1 .. %d)", n_channels, GJ_CORR_MAX_CHANNELS);
-    if (n_samples < 1 || n_samples > GJ_CORR_MAX_SAMPLES)
-        return fail(ctx, GJ_ERR_UNSUPPORTED, "n_samples %zu (1 .. %llu)", n_samples, (unsigned long long)GJ_CORR_MAX_SAMPLES);
+    if (int rc = replica_check_counts(ctx, n_channels, n_samples)) return rc;
     if (first_sample > nbytes / 2 || n_samples > nbytes / 2 - first_sample)
         return fail(ctx, GJ_ERR_INVALID, "samples %zu .. +%zu run past the capture's %zu", first_sample, n_samples, nbytes / 2);
     CorrGeom g;
     g.n_samples = n_samples;
     g.block_samples = block_samples;
-    g.tile_blocks = kCorrTileMax / block_samples;
-    g.block_threads = block_samples / kCorrRun;
+    g.tile_blocks = kReplicaTile / block_samples;
+    g.block_threads = block_samples / kReplicaRun;
     g.group = 1;
     while (g.group < 64 && g.block_threads % (2 * g.group) == 0) g.group *= 2;
     g.n_blocks = gj_corr_blocks(n_samples, block_samples);
@@ -306,11 +270,8 @@ int gj_corr_bank_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t fir
     g.n_channels = n_channels;
     g.n_taps = n_taps;
     for (int j = 0; j < GJ_CORR_MAX_TAPS; ++j) g.tap[j] = j < n_taps ? tap_offsets[j] : 0;
-    // every workgroup resident at once (three per CU: the kernel's registers allow three waves per SIMD), so that the
-    // code rows are packed once per slot
-    const unsigned long long slots = 3ull * (unsigned)(ctx->num_cus > 0 ? ctx->num_cus : 1);
-    const unsigned grid = (unsigned)(g.n_tiles < slots ? g.n_tiles : slots);
-    hipLaunchKernelGGL(corr_bank_kernel, dim3(grid), dim3(kCorrThreads), 0, ctx->stream, d_iq + 2 * first_sample, g, d_codes,
+    const unsigned grid = replica_grid(ctx, 3, g.n_tiles);   // the kernel's registers allow three waves per SIMD
+    hipLaunchKernelGGL(corr_bank_kernel, dim3(grid), dim3(kReplicaThreads), 0, ctx->stream, d_iq + 2 * first_sample, g, d_codes,
                        d_channels, d_out);
     GJ_LAUNCH_CHECK(ctx);
     return GJ_OK;

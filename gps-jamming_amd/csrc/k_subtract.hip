@@ -7,15 +7,12 @@
 // A workgroup of four waves owns tiles of 4096 samples, one record each, whatever B is.  Thread tid owns the 16
 // consecutive samples 16 tid .. 16 tid + 15 of the tile; B is a multiple of 16 and a tile starts on a multiple of 16,
 // so a thread's samples lie in ONE block: one amplitude pair per channel and thread.
-//   0. once per workgroup: every channel is checked (any bad field: the workgroup returns, nothing is written and no
-//      chip is read), the channels go to LDS, and the code row of every channel is packed to 1023 sign bits (32 words)
-//      with one ballot per 64 chips, as the bank does;
-//   1. per tile: the thread's 32 bytes come from the capture ONCE, as two 16-byte loads (2-byte aligned: first_sample
-//      may be odd);
+//   0. once per workgroup: the channels are checked, kept in LDS and their code rows packed to sign bits (replica.h);
+//   1. per tile: the thread's 32 bytes come from the capture ONCE (replica.h);
 //   2. per channel: the amplitude pair of the thread's block, clamped; the first code phase by one 64-bit multiply and
-//      a mod, the others by exact adds with one conditional subtraction of 1023 * 2^32; the chip's sign picks +-a, and
-//      the table entry (C, S) at theta >> 28 turns it: four multiply-adds into the sample's two accumulators.  Only
-//      tap 0 exists: no LDS code table, no barrier per channel;
+//      a mod, the others by exact steps; the chip's sign picks +-a, and the table entry (C, S) at theta >> 28 turns
+//      it: four multiply-adds into the sample's two accumulators.  Only tap 0 exists: no LDS code table, no barrier
+//      per channel;
 //   3. per sample and component: d (32768, or the hash of the absolute index), q = (R + d) >> 16 (arithmetic: the
 //      floor), the byte less q, clamped; the 32 bytes leave as two 16-byte stores where d_out is 16-byte aligned and
 //      the run is whole, byte by byte otherwise;
@@ -23,24 +20,19 @@
 //      per wave and field, and thread 0 adds the four and stores the record: no atomics, no workspace.
 //
 // Widths.  |a| <= 2^19 after the clamp and |C[i]| + |S[i]| <= 46: a channel adds at most 2^19 * 46 to |R|, 64 channels
-// 1 543 503 872, and with d <= 65535 on top R + d <= 1 543 569 407 < 2^31: int32 is exact, partial sums included.  The
-// code phase is the bank's: t < 2^28 and code_step < 2^34 give t code_step < 2^62; with code_phase < 2^42 below 2^63.
-// A tile's total is at most 4096 * 2 * 128^2 = 2^27 and its removed at most 4096 * 2 * 255^2 = 532 684 800: uint32.
+// 1 543 503 872, and with d <= 65535 on top R + d <= 1 543 569 407 < 2^31: int32 is exact, partial sums included.  A
+// tile's total is at most 4096 * 2 * 128^2 = 2^27 and its removed at most 4096 * 2 * 255^2 = 532 684 800: uint32.  The
+// channel fields, the code phase and its widths: replica.h.
 //
 // This is a translation unit of its own with its own extern "C" entry points: none of the other sources refers to it.
-#include "gj_common.h"
+#include "replica.h"
 
 namespace gj {
 
-constexpr int kSubThreads = 256;
-constexpr int kSubWaves = kSubThreads / 64;
-constexpr int kSubRun = 16;                                          // samples of a thread
-constexpr int kSubTile = kSubThreads * kSubRun;                      // 4096
-constexpr unsigned long long kSubPeriod = (unsigned long long)GJ_CORR_CODE_LEN << 32;
+constexpr int kSubWaves = kReplicaThreads / 64;
 
-static_assert(kSubTile == GJ_SUB_BLOCK, "one record per tile");
-static_assert(GJ_CORR_MAX_BLOCK % kSubRun == 0 && kSubTile % kSubRun == 0, "a thread's samples lie in one block");
-static_assert(sizeof(gj_corr_channel) == 32 && sizeof(gj_subtract_block) == 24, "the header's layouts");
+static_assert(kReplicaTile == GJ_SUB_BLOCK, "one record per tile");
+static_assert(sizeof(gj_subtract_block) == 24, "the header's layout");
 // |R| <= channels * max amplitude * max(|C| + |S|), and the dither adds less than 2^GJ_SUB_FRAC
 static_assert((long long)GJ_CORR_MAX_CHANNELS * GJ_SUB_MAX_AMP * 46 + (1ll << GJ_SUB_FRAC) - 1 < (1ll << 31), "R + d fits int32");
 static_assert(GJ_SUB_FRAC == 16, "d is the hash's upper half");
@@ -54,15 +46,6 @@ struct SubGeom {
     unsigned seed;
     int out_aligned;             // d_out is 16-byte aligned
 };
-
-struct __attribute__((packed, aligned(2))) SubChunk16 {
-    unsigned x, y, z, w;
-};
-
-// x mod 1023 * 2^32 for x < 2^63
-__device__ __forceinline__ unsigned long long sub_mod_period(unsigned long long x) {
-    return ((unsigned long long)((unsigned)(x >> 32) % (unsigned)GJ_CORR_CODE_LEN) << 32) | (x & 0xffffffffull);
-}
 
 __device__ __forceinline__ int sub_clamp_amp(int v) { return v < -GJ_SUB_MAX_AMP ? -GJ_SUB_MAX_AMP : (v > GJ_SUB_MAX_AMP ? GJ_SUB_MAX_AMP : v); }
 
@@ -78,11 +61,11 @@ __device__ __forceinline__ int sub_dither(unsigned long long sample, unsigned co
     return (int)(v >> 16);
 }
 
-__global__ __launch_bounds__(kSubThreads) void subtract_kernel(const uint8_t* __restrict__ iq, SubGeom g,
-                                                               const int16_t* __restrict__ codes,
-                                                               const gj_corr_channel* __restrict__ channels,
-                                                               const int32_t* __restrict__ amp, uint8_t* __restrict__ out,
-                                                               gj_subtract_block* __restrict__ blocks) {
+__global__ __launch_bounds__(kReplicaThreads) void subtract_kernel(const uint8_t* __restrict__ iq, SubGeom g,
+                                                                   const int16_t* __restrict__ codes,
+                                                                   const gj_corr_channel* __restrict__ channels,
+                                                                   const int32_t* __restrict__ amp, uint8_t* __restrict__ out,
+                                                                   gj_subtract_block* __restrict__ blocks) {
     __shared__ gj_corr_channel chan[GJ_CORR_MAX_CHANNELS];
     __shared__ unsigned code_bits[GJ_CORR_MAX_CHANNELS][32];         // bit c of word w: chip 32 w + c is -1
     __shared__ int2 mix[16];                                         // (C, S)
@@ -94,8 +77,7 @@ __global__ __launch_bounds__(kSubThreads) void subtract_kernel(const uint8_t* __
     int bad = 0;
     if (tid < g.n_channels) {
         const gj_corr_channel c = channels[tid];
-        bad = c.reserved != 0 || c.code_row < 0 || c.code_row >= g.n_code_rows || c.code_phase >= kSubPeriod ||
-              c.code_step >= GJ_CORR_MAX_CODE_STEP;
+        bad = GJ_REPLICA_CHANNEL_BAD(c, g.n_code_rows);
         chan[tid] = c;
     }
     if (tid < 16) {
@@ -109,72 +91,60 @@ __global__ __launch_bounds__(kSubThreads) void subtract_kernel(const uint8_t* __
         mix[tid] = int2{c, s};
     }
     if (__syncthreads_or(bad)) return;
-    for (int item = wave; item < g.n_channels * 16; item += kSubWaves) {
-        const int ch = item >> 4, chip = (item & 15) * 64 + lane;
-        const int v = chip < GJ_CORR_CODE_LEN ? (int)codes[(size_t)chan[ch].code_row * GJ_CORR_CODE_LEN + chip] : 0;
-        const unsigned long long m = __ballot(v < 0);
-        if (lane == 0) {
-            code_bits[ch][2 * (item & 15)] = (unsigned)m;
-            code_bits[ch][2 * (item & 15) + 1] = (unsigned)(m >> 32);
-        }
-    }
+    replica_pack_codes(codes, chan, code_bits, g.n_channels, wave, lane);
     __syncthreads();
 
     const long long n = (long long)g.n_samples;
     const uint8_t* const src = iq + 2 * g.first_sample;
 
     for (unsigned long long tile = blockIdx.x; tile < g.n_tiles; tile += gridDim.x) {
-        const long long t0 = (long long)(tile * (unsigned long long)kSubTile) + kSubRun * tid;   // this thread's first sample
-        const int nv = t0 >= n ? 0 : (n - t0 >= kSubRun ? kSubRun : (int)(n - t0));              // its samples inside the range
+        const long long t0 = (long long)(tile * (unsigned long long)kReplicaTile) + kReplicaRun * tid;   // this thread's first sample
+        const int nv = t0 >= n ? 0 : (n - t0 >= kReplicaRun ? kReplicaRun : (int)(n - t0));             // its samples inside the range
         unsigned total = 0, removed = 0, clipped = 0;
 
         if (nv > 0) {
             // ---- 1. the thread's bytes
-            unsigned raw[kSubRun / 2];
-            if (nv == kSubRun) {
-                const SubChunk16 lo = *reinterpret_cast<const SubChunk16*>(src + 2 * t0);
-                const SubChunk16 hi = *reinterpret_cast<const SubChunk16*>(src + 2 * t0 + 16);
-                raw[0] = lo.x, raw[1] = lo.y, raw[2] = lo.z, raw[3] = lo.w, raw[4] = hi.x, raw[5] = hi.y, raw[6] = hi.z, raw[7] = hi.w;
-            } else {
+            unsigned raw[kReplicaRun / 2];
+            if (nv == kReplicaRun)
+                replica_load_run(src + 2 * t0, raw);
+            else {
 #pragma unroll
-                for (int p = 0; p < kSubRun / 2; ++p) raw[p] = 0u;
+                for (int p = 0; p < kReplicaRun / 2; ++p) raw[p] = 0u;
 #pragma unroll
-                for (int s = 0; s < kSubRun; ++s)
+                for (int s = 0; s < kReplicaRun; ++s)
                     if (s < nv) raw[s >> 1] |= (unsigned)*reinterpret_cast<const uint16_t*>(src + 2 * (t0 + s)) << (16 * (s & 1));
             }
 
             // ---- 2. the replicas of every channel, added up
-            int ri[kSubRun], rq[kSubRun];
+            int ri[kReplicaRun], rq[kReplicaRun];
 #pragma unroll
-            for (int s = 0; s < kSubRun; ++s) ri[s] = rq[s] = 0;
+            for (int s = 0; s < kReplicaRun; ++s) ri[s] = rq[s] = 0;
             const unsigned long long block = (unsigned)t0 / (unsigned)g.block_samples;          // t0 < 2^28
             for (int ch = 0; ch < g.n_channels; ++ch) {
                 const gj_corr_channel c = chan[ch];
                 const int32_t* const a = amp + 2 * ((unsigned long long)ch * g.n_blocks + block);
                 const int a_i = sub_clamp_amp(a[0]), a_q = sub_clamp_amp(a[1]);
                 const unsigned* const bits = code_bits[ch];
-                unsigned long long ph = sub_mod_period(c.code_phase + (unsigned long long)t0 * c.code_step);
+                unsigned long long ph = replica_mod_period(c.code_phase + (unsigned long long)t0 * c.code_step);
                 unsigned theta = c.carr_phase + (unsigned)t0 * c.carr_step;
 #pragma unroll
-                for (int s = 0; s < kSubRun; ++s) {
-                    const unsigned chip = (unsigned)(ph >> 32);
-                    const bool neg = (bits[chip >> 5] >> (chip & 31)) & 1u;
+                for (int s = 0; s < kReplicaRun; ++s) {
+                    const bool neg = replica_chip_neg(bits, ph);
                     const int s_i = neg ? -a_i : a_i, s_q = neg ? -a_q : a_q;
                     const int2 m = mix[theta >> 28];
                     ri[s] += s_i * m.x + s_q * m.y;
                     rq[s] += s_q * m.x - s_i * m.y;
-                    ph += c.code_step;
-                    if (ph >= kSubPeriod) ph -= kSubPeriod;
+                    ph = replica_step(ph, c.code_step);
                     theta += c.carr_step;
                 }
             }
 
             // ---- 3. down to LSB, off the bytes
-            unsigned o[kSubRun / 2];
+            unsigned o[kReplicaRun / 2];
 #pragma unroll
-            for (int p = 0; p < kSubRun / 2; ++p) o[p] = 0u;
+            for (int p = 0; p < kReplicaRun / 2; ++p) o[p] = 0u;
 #pragma unroll
-            for (int s = 0; s < kSubRun; ++s) {
+            for (int s = 0; s < kReplicaRun; ++s) {
                 const unsigned long long sample = g.first_sample + (unsigned long long)t0 + (unsigned)s;
 #pragma unroll
                 for (int comp = 0; comp < 2; ++comp) {
@@ -193,12 +163,12 @@ __global__ __launch_bounds__(kSubThreads) void subtract_kernel(const uint8_t* __
                 }
             }
             uint8_t* const dst = out + 2 * t0;
-            if (nv == kSubRun && g.out_aligned) {
+            if (nv == kReplicaRun && g.out_aligned) {
                 reinterpret_cast<uint4*>(dst)[0] = uint4{o[0], o[1], o[2], o[3]};
                 reinterpret_cast<uint4*>(dst)[1] = uint4{o[4], o[5], o[6], o[7]};
             } else {   // the ragged end, or an output that is not 16-byte aligned
 #pragma unroll
-                for (int i = 0; i < 2 * kSubRun; ++i)
+                for (int i = 0; i < 2 * kReplicaRun; ++i)
                     if (i < 2 * nv) dst[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
             }
         }
@@ -234,37 +204,28 @@ int gj_subtract_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t firs
     if (!ctx) return GJ_ERR_INVALID;
     Guard lock(ctx);
     if (!d_iq || !d_codes || !d_channels || !d_amp || !d_out) return fail(ctx, GJ_ERR_INVALID, "null buffer");
-    if ((reinterpret_cast<uintptr_t>(d_iq) | reinterpret_cast<uintptr_t>(d_codes)) & 1)
-        return fail(ctx, GJ_ERR_INVALID, "the capture and the codes must be 2-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_channels) & 7) return fail(ctx, GJ_ERR_INVALID, "channels must be 8-byte aligned");
+    if (int rc = replica_check_alignment(ctx, d_iq, d_codes, d_channels)) return rc;
     if (reinterpret_cast<uintptr_t>(d_amp) & 3) return fail(ctx, GJ_ERR_INVALID, "amplitudes must be 4-byte aligned");
     if (reinterpret_cast<uintptr_t>(d_blocks) & 7) return fail(ctx, GJ_ERR_INVALID, "records must be 8-byte aligned");
     if (n_code_rows < 1) return fail(ctx, GJ_ERR_INVALID, "n_code_rows %d", n_code_rows);
     if (flags & ~GJ_SUB_DITHER) return fail(ctx, GJ_ERR_INVALID, "unknown flags 0x%x", (unsigned)flags);
-    if (block_samples < 16 || block_samples > GJ_CORR_MAX_BLOCK || block_samples % 16)
-        return fail(ctx, GJ_ERR_UNSUPPORTED, "block_samples %d (a multiple of 16 in 16 .. %d)", block_samples, GJ_CORR_MAX_BLOCK);
-    if (n_channels < 1 || n_channels > GJ_CORR_MAX_CHANNELS)
-        return fail(ctx, GJ_ERR_UNSUPPORTED, "n_channels %d (1 .. %d)", n_channels, GJ_CORR_MAX_CHANNELS);
-    if (n_samples < 1 || n_samples > GJ_CORR_MAX_SAMPLES)
-        return fail(ctx, GJ_ERR_UNSUPPORTED, "n_samples %zu (1 .. %llu)", n_samples, (unsigned long long)GJ_CORR_MAX_SAMPLES);
+    if (int rc = replica_check_block(ctx, block_samples)) return rc;
+    if (int rc = replica_check_counts(ctx, n_channels, n_samples)) return rc;
     if (int rc = check_range_and_output(ctx, d_iq, nbytes, first_sample, n_samples, d_out)) return rc;
     SubGeom g;
     g.first_sample = first_sample;
     g.n_samples = n_samples;
     g.block_samples = block_samples;
-    g.n_blocks = n_samples / (size_t)block_samples + (n_samples % (size_t)block_samples != 0);   // gj_corr_blocks
+    g.n_blocks = gj_corr_blocks(n_samples, block_samples);
     g.n_tiles = gj_subtract_blocks(n_samples);
     g.n_code_rows = n_code_rows;
     g.n_channels = n_channels;
     g.dither = (flags & GJ_SUB_DITHER) != 0;
     g.seed = seed;
     g.out_aligned = (reinterpret_cast<uintptr_t>(d_out) & 15) == 0;
-    // every workgroup resident at once (four per CU: the kernel's 124 registers allow four waves per SIMD), so that the
-    // code rows are packed once per slot
-    const unsigned long long slots = 4ull * (unsigned)(ctx->num_cus > 0 ? ctx->num_cus : 1);
-    const unsigned grid = (unsigned)(g.n_tiles < slots ? g.n_tiles : slots);
-    hipLaunchKernelGGL(subtract_kernel, dim3(grid), dim3(kSubThreads), 0, ctx->stream, d_iq, g, d_codes, d_channels, d_amp, d_out,
-                       d_blocks);
+    const unsigned grid = replica_grid(ctx, 4, g.n_tiles);   // the kernel's 124 registers allow four waves per SIMD
+    hipLaunchKernelGGL(subtract_kernel, dim3(grid), dim3(kReplicaThreads), 0, ctx->stream, d_iq, g, d_codes, d_channels, d_amp,
+                       d_out, d_blocks);
     GJ_LAUNCH_CHECK(ctx);
     return GJ_OK;
 }

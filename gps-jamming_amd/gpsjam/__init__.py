@@ -846,6 +846,25 @@ class Device:
             rec = d_rec.download(dtype, n_records)
             return Capture.from_device(self, d_out, 2 * n_samples), rec
 
+    def _replica_inputs(self, temps, capture, channels, codes, first_sample: int, n_samples, block_samples: int):
+        """What ``corr_bank`` and ``subtract`` do before they part: the capture resident, ``n_samples`` defaulted to the
+        rest of it, the code rows on the device (``(buffer, rows)`` as it is, a host int16[rows][1023] uploaded into a buffer
+        that the ExitStack ``temps`` frees), the channels checked on the host as CORR_CHANNEL_DTYPE records, and the count of
+        their blocks: ``(cap, n_samples, d_codes, n_rows, rec, blocks)``.  The records are NOT uploaded here: the
+        subtraction puts its amplitudes on the device first, whose size it learns from these."""
+        cap = temps.enter_context(self._resident(capture))
+        n_samples = max(0, cap.nsamples - first_sample) if n_samples is None else int(n_samples)
+        if isinstance(codes, tuple):
+            d_codes, n_rows = codes[0], int(codes[1])
+        else:
+            host = np.ascontiguousarray(codes, np.int16)
+            if host.ndim != 2 or host.shape[1] != _ffi.GJ_CORR_CODE_LEN:
+                raise ValueError(f"codes must be int16[rows][{_ffi.GJ_CORR_CODE_LEN}]")
+            n_rows = int(host.shape[0])
+            d_codes = temps.enter_context(DevBuf(self, max(host.nbytes, 2))).upload(host)
+        rec = _corr_channels(channels, n_rows)
+        return cap, n_samples, d_codes, n_rows, rec, corr_blocks(n_samples, block_samples)
+
     def probe_busy_dev(self, milliseconds: float):
         """Keep this context's stream (and its hardware queue) busy for a while with one spinning wave (gj_probe_busy_dev):
         the stream-overlap probe of gpsjam/streams.py."""
@@ -1333,18 +1352,8 @@ class Device:
         first_sample, block_samples = int(first_sample), int(block_samples)
         taps = tuple(int(d) for d in taps)
         with contextlib.ExitStack() as temps:
-            cap = temps.enter_context(self._resident(capture))
-            n_samples = max(0, cap.nsamples - first_sample) if n_samples is None else int(n_samples)
-            if isinstance(codes, tuple):
-                d_codes, n_rows = codes[0], int(codes[1])
-            else:
-                host = np.ascontiguousarray(codes, np.int16)
-                if host.ndim != 2 or host.shape[1] != _ffi.GJ_CORR_CODE_LEN:
-                    raise ValueError(f"codes must be int16[rows][{_ffi.GJ_CORR_CODE_LEN}]")
-                n_rows = int(host.shape[0])
-                d_codes = temps.enter_context(DevBuf(self, max(host.nbytes, 2))).upload(host)
-            rec = _corr_channels(channels, n_rows)
-            blocks = corr_blocks(n_samples, block_samples)
+            cap, n_samples, d_codes, n_rows, rec, blocks = self._replica_inputs(temps, capture, channels, codes, first_sample,
+                                                                                n_samples, block_samples)
             d_ch = temps.enter_context(DevBuf(self, max(rec.nbytes, 32))).upload(rec)
             d_out = temps.enter_context(DevBuf(self, 8 * max(rec.size * blocks * len(taps), 1)))
             self._count("corr_bank")
@@ -1365,18 +1374,8 @@ class Device:
         SUB_DTYPE record per SUB_BLOCK samples."""
         first_sample, block_samples = int(first_sample), int(block_samples)
         with contextlib.ExitStack() as temps:
-            cap = temps.enter_context(self._resident(capture))
-            n_samples = max(0, cap.nsamples - first_sample) if n_samples is None else int(n_samples)
-            if isinstance(codes, tuple):
-                d_codes, n_rows = codes[0], int(codes[1])
-            else:
-                host = np.ascontiguousarray(codes, np.int16)
-                if host.ndim != 2 or host.shape[1] != _ffi.GJ_CORR_CODE_LEN:
-                    raise ValueError(f"codes must be int16[rows][{_ffi.GJ_CORR_CODE_LEN}]")
-                n_rows = int(host.shape[0])
-                d_codes = temps.enter_context(DevBuf(self, max(host.nbytes, 2))).upload(host)
-            rec = _corr_channels(channels, n_rows)
-            blocks = corr_blocks(n_samples, block_samples)
+            cap, n_samples, d_codes, n_rows, rec, blocks = self._replica_inputs(temps, capture, channels, codes, first_sample,
+                                                                                n_samples, block_samples)
             d_amp = self._on_device(temps, amplitudes, np.int32, 2 * rec.size * blocks, "amplitudes",
                                     f"{rec.size} channels of {blocks} blocks take {2 * rec.size * blocks}")
             d_ch = temps.enter_context(DevBuf(self, max(rec.nbytes, 32))).upload(rec)

@@ -6,7 +6,9 @@ post-correlation and spoofing tests.  Not a test module: tests/test_corr_host.py
     chip = floor((code_phase + (t + d) code_step) / 2^32) mod 1023;  c = codes[code_row][chip]
     record (channel, block m, tap j) = (sum wI c, sum wQ c) over t in [m B, (m + 1) B)
 
-``brute`` is the definition sample by sample with Python ints; ``bank`` the same in numpy int64 for long ranges.
+``brute`` is the definition sample by sample with Python ints; ``bank`` the same in numpy int64 for long ranges.  The
+field check, the carrier index and the chip index stand once, for both and for tests/subtract_restatement.py: the same
+operators are exact on a Python int and floor and wrap alike on an int64 array.
 Everything is exact: the GPU is held to every bit of every record.  The float chain (gpsjam/postcorr.py,
 gpsjam/spoof.py) is NOT restated: the tests feed it these integers.
 """
@@ -33,20 +35,37 @@ def blocks(n, B):
     return -(-int(n) // int(B))
 
 
+def check_channels(codes, channels):
+    """Every field of every channel inside the bounds of gj_corr_channel."""
+    for (code_phase, code_step, carr_phase, carr_step, row, reserved) in channels:
+        assert reserved == 0 and 0 <= row < len(codes) and 0 <= code_phase < PERIOD and 0 <= code_step < MAX_CODE_STEP
+        assert 0 <= carr_phase < 2 ** 32 and 0 <= carr_step < 2 ** 32
+
+
+def carrier_index(carr_phase, carr_step, t):
+    """i = ((carr_phase + t carr_step) mod 2^32) >> 28 of sample t: a Python int, or an int64 array (t carr_step < 2^60)."""
+    return ((int(carr_phase) + t * int(carr_step)) & 0xFFFFFFFF) >> 28
+
+
+def chip_index(code_phase, code_step, t):
+    """The chip of sample t, tap offset included (t < 0 at a range's start; the arithmetic shift is the floor): a Python
+    int, or an int64 array (|sum| < 2^63)."""
+    return ((int(code_phase) + t * int(code_step)) >> 32) % CODE_LEN
+
+
 def brute(raw, first, n, B, codes, channels, taps):
     """The definition with Python ints: nested lists [channel][block][tap] = [I, Q]."""
     raw = np.asarray(raw, np.uint8)
+    check_channels(codes, channels)
     out = []
-    for (code_phase, code_step, carr_phase, carr_step, row, reserved) in channels:
-        assert reserved == 0 and 0 <= row < len(codes) and 0 <= code_phase < PERIOD and 0 <= code_step < MAX_CODE_STEP
+    for (code_phase, code_step, carr_phase, carr_step, row, _) in channels:
         rec = [[[0, 0] for _ in taps] for _ in range(blocks(n, B))]
         for t in range(n):
             I, Q = int(raw[2 * (first + t)]) - 128, int(raw[2 * (first + t) + 1]) - 128
-            i = ((carr_phase + t * carr_step) % 2 ** 32) >> 28
+            i = carrier_index(carr_phase, carr_step, t)
             wI, wQ = COS[i] * I - SIN[i] * Q, SIN[i] * I + COS[i] * Q
             for j, d in enumerate(taps):
-                chip = ((code_phase + (t + d) * code_step) // 2 ** 32) % CODE_LEN
-                c = int(codes[row][chip])
+                c = int(codes[row][chip_index(code_phase, code_step, t + int(d))])
                 rec[t // B][j][0] += wI * c
                 rec[t // B][j][1] += wQ * c
         out.append(rec)
@@ -61,10 +80,7 @@ def bank(raw, first, n, B, codes, channels, taps):
     codes = np.asarray(codes, np.int64)
     cos, sin = np.array(COS, np.int64), np.array(SIN, np.int64)
     out = np.zeros((len(channels), blocks(n, B), len(taps), 2), np.int64)
-    for ch in channels:
-        code_phase, code_step, carr_phase, carr_step, row, reserved = ch
-        assert reserved == 0 and 0 <= row < len(codes) and 0 <= code_phase < PERIOD and 0 <= code_step < MAX_CODE_STEP
-        assert 0 <= carr_phase < 2 ** 32 and 0 <= carr_step < 2 ** 32
+    check_channels(codes, channels)
     piece = B * max(1, (1 << 20) // B)
     for t0 in range(0, n, piece):
         t1 = min(n, t0 + piece)
@@ -72,12 +88,11 @@ def bank(raw, first, n, B, codes, channels, taps):
         t = np.arange(t0, t1, dtype=np.int64)
         starts = np.arange(0, t1 - t0, B)
         m0 = t0 // B
-        for k, (code_phase, code_step, carr_phase, carr_step, row, reserved) in enumerate(channels):
-            i = ((int(carr_phase) + t * int(carr_step)) & 0xFFFFFFFF) >> 28           # t carr_step < 2^60
+        for k, (code_phase, code_step, carr_phase, carr_step, row, _) in enumerate(channels):
+            i = carrier_index(carr_phase, carr_step, t)
             wI, wQ = cos[i] * I - sin[i] * Q, sin[i] * I + cos[i] * Q
             for j, d in enumerate(taps):
-                chip = ((int(code_phase) + (t + int(d)) * int(code_step)) >> 32) % CODE_LEN   # arithmetic shift = floor; < 2^63
-                c = codes[row][chip]
+                c = codes[row][chip_index(code_phase, code_step, t + int(d))]
                 out[k, m0:m0 + starts.size, j, 0] = np.add.reduceat(wI * c, starts)
                 out[k, m0:m0 + starts.size, j, 1] = np.add.reduceat(wQ * c, starts)
     assert np.abs(out).max() <= RECORD_BOUND

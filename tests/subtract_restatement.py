@@ -59,24 +59,17 @@ def dither(first, n, seed):
     return (v >> np.uint64(16)).astype(np.int64)
 
 
-def check_channels(codes, channels):
-    for (code_phase, code_step, carr_phase, carr_step, row, reserved) in channels:
-        assert reserved == 0 and 0 <= row < len(codes) and 0 <= code_phase < cr.PERIOD and 0 <= code_step < cr.MAX_CODE_STEP
-        assert 0 <= carr_phase < 2 ** 32 and 0 <= carr_step < 2 ** 32
-
-
 def brute(raw, first, n, B, codes, channels, amps, flags=0, seed=0):
     """The definition with Python ints: (bytes list[2 n], records list of (total, removed, n_clipped))."""
     raw = np.asarray(raw, np.uint8)
-    check_channels(codes, channels)
+    cr.check_channels(codes, channels)
     out, rec = [], [[0, 0, 0] for _ in range(blocks(n))]
     for t in range(n):
         R = [0, 0]
         for ch, (code_phase, code_step, carr_phase, carr_step, row, _) in enumerate(channels):
             aI, aQ = (max(-MAX_AMP, min(MAX_AMP, int(v))) for v in amps[ch][t // B])
-            i = ((carr_phase + t * carr_step) % 2 ** 32) >> 28
-            chip = ((code_phase + t * code_step) // 2 ** 32) % cr.CODE_LEN
-            c = -1 if int(codes[row][chip]) < 0 else 1
+            i = cr.carrier_index(carr_phase, carr_step, t)
+            c = -1 if int(codes[row][cr.chip_index(code_phase, code_step, t)]) < 0 else 1
             R[0] += c * (aI * cr.COS[i] + aQ * cr.SIN[i])
             R[1] += c * (aQ * cr.COS[i] - aI * cr.SIN[i])
         for comp in (0, 1):
@@ -96,7 +89,7 @@ def brute(raw, first, n, B, codes, channels, amps, flags=0, seed=0):
 
 def replica(first, n, B, codes, channels, amps):
     """int64[n][2]: (R_I, R_Q) of every sample of the range."""
-    check_channels(codes, channels)
+    cr.check_channels(codes, channels)
     amps = np.clip(np.asarray(amps, np.int64).reshape(len(channels), -1, 2), -MAX_AMP, MAX_AMP)
     assert amps.shape[1] == cr.blocks(n, B), "one amplitude pair per channel and block"
     code_sign = np.where(np.asarray(codes, np.int64) < 0, -1, 1)
@@ -107,8 +100,8 @@ def replica(first, n, B, codes, channels, amps):
         t = np.arange(t0, min(n, t0 + piece), dtype=np.int64)
         m = t // B
         for ch, (code_phase, code_step, carr_phase, carr_step, row, _) in enumerate(channels):
-            i = ((int(carr_phase) + t * int(carr_step)) & M32) >> 28                       # t carr_step < 2^60
-            c = code_sign[row][((int(code_phase) + t * int(code_step)) >> 32) % cr.CODE_LEN]   # < 2^63
+            i = cr.carrier_index(carr_phase, carr_step, t)
+            c = code_sign[row][cr.chip_index(code_phase, code_step, t)]
             aI, aQ = amps[ch, m, 0], amps[ch, m, 1]
             R[t, 0] += c * (aI * cos[i] + aQ * sin[i])
             R[t, 1] += c * (aQ * cos[i] - aI * sin[i])
