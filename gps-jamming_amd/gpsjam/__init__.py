@@ -825,6 +825,15 @@ class Device:
             with Capture(self, raw) as cap:
                 yield cap
 
+    def _residents(self, temps, *raws):
+        """``_resident`` of every input in order, entered into the ExitStack ``temps``: the list of their ``Capture``s.  An
+        input that IS an earlier one (the same object) gets that one's, so host bytes given twice are uploaded once."""
+        caps = []
+        for k, raw in enumerate(raws):
+            earlier = next((caps[j] for j in range(k) if raws[j] is raw), None)
+            caps.append(temps.enter_context(self._resident(raw)) if earlier is None else earlier)
+        return caps
+
     def _on_device(self, temps, values, dtype, count: int, name: str, expected: str):
         """``values`` on the device: a device buffer (DevBuf, address, torch tensor) as it is, whatever it holds, or a host
         array of exactly ``count`` values, uploaded as ``dtype`` into a buffer that the ExitStack ``temps`` frees."""
@@ -1175,8 +1184,7 @@ class Device:
         nfft, frames_per_row, first_a, first_b = int(nfft), int(frames_per_row), int(first_a), int(first_b)
         hop = nfft if hop is None else int(hop)
         with contextlib.ExitStack() as temps:
-            cap_a = temps.enter_context(self._resident(a))
-            cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
+            cap_a, cap_b = self._residents(temps, a, b)
             n_rows, empty = _rows_to_compute(n_rows, csd_rows, (cap_a.nbytes, first_a, cap_b.nbytes, first_b), nfft, hop, frames_per_row)
             if empty is not None:
                 return CrossSpectrum(empty, empty, empty, empty, nfft, hop, frames_per_row, first_a, first_b)
@@ -1242,13 +1250,20 @@ class Device:
         w = np.asarray(weights)
         if w.ndim not in (1, 2) or w.shape[-1] != nfft or w.size == 0:
             raise ValueError(f"weights must be complex64[{nfft}] or [n_sets][{nfft}], not {w.shape}")
-        w = np.ascontiguousarray(w.reshape(-1, nfft), np.complex64)
+        return self._cancel("cancel", (a, b), (first_a, first_b), w.reshape(-1, nfft), threshold, nfft, n_samples, frames_per_set,
+                            self.cancel_dev)
+
+    def _cancel(self, name, raws, firsts, weights, threshold, nfft: int, n_samples, frames_per_set, launch):
+        """The one body of ``cancel`` and ``cancel2`` behind their weights' shape check: main and its auxiliaries ``raws``
+        resident, n_samples and frames_per_set defaulted, the threshold and ``weights`` ([n_sets][...], one row per set)
+        on the device, and ``launch`` -- the caller's ``*_dev`` -- on (capture, nbytes, first) of every input and the
+        arguments the two entry points share.  Device memory is taken in the order threshold, weights, output, records."""
+        w = np.ascontiguousarray(weights, np.complex64)
         n_sets = w.shape[0]
         with contextlib.ExitStack() as temps:
-            cap_a = temps.enter_context(self._resident(a))
-            cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
+            caps = self._residents(temps, *raws)
             if n_samples is None:
-                n_samples = max(0, min(cap_a.nsamples - first_a, cap_b.nsamples - first_b))
+                n_samples = max(0, min(cap.nsamples - first for cap, first in zip(caps, firsts)))
             n_samples = int(n_samples)
             frames = excise_frames(n_samples, nfft)
             if frames_per_set is None:
@@ -1257,11 +1272,11 @@ class Device:
                 frames_per_set = max(frames, 1)
             thr = np.full(nfft, np.inf, np.float32) if threshold is None else threshold
             thr = self._on_device(temps, thr, np.float32, nfft, "threshold", f"nfft is {nfft}")
-            d_w = self._on_device(temps, w.view(np.float32), np.float32, 2 * n_sets * nfft, "weights", "")
-            self._count("cancel")
-            return self._cleaned(n_samples, frames, CANCEL_DTYPE, lambda d_out, d_rec: self.cancel_dev(
-                cap_a, cap_a.nbytes, first_a, cap_b, cap_b.nbytes, first_b, n_samples, nfft, d_w, frames_per_set, n_sets,
-                thr, d_out, d_rec))
+            d_w = self._on_device(temps, w.view(np.float32), np.float32, 2 * w.size, "weights", "")
+            self._count(name)
+            inputs = [v for cap, first in zip(caps, firsts) for v in (cap, cap.nbytes, first)]
+            return self._cleaned(n_samples, frames, CANCEL_DTYPE, lambda d_out, d_rec: launch(
+                *inputs, n_samples, nfft, d_w, frames_per_set, n_sets, thr, d_out, d_rec))
 
     def cancel2(self, a, b, c, weights, threshold=None, nfft: int = 1024, first_a: int = 0, first_b: int = 0,
                 first_c: int = 0, n_samples: Optional[int] = None, frames_per_set: Optional[int] = None):
@@ -1276,27 +1291,8 @@ class Device:
         w = np.asarray(weights)
         if w.ndim not in (2, 3) or w.shape[-2:] != (2, nfft) or w.size == 0:
             raise ValueError(f"weights must be complex64[2][{nfft}] or [n_sets][2][{nfft}], not {w.shape}")
-        w = np.ascontiguousarray(w.reshape(-1, 2, nfft), np.complex64)
-        n_sets = w.shape[0]
-        with contextlib.ExitStack() as temps:
-            cap_a = temps.enter_context(self._resident(a))
-            cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
-            cap_c = cap_a if c is a else cap_b if c is b else temps.enter_context(self._resident(c))
-            if n_samples is None:
-                n_samples = max(0, min(cap_a.nsamples - first_a, cap_b.nsamples - first_b, cap_c.nsamples - first_c))
-            n_samples = int(n_samples)
-            frames = excise_frames(n_samples, nfft)
-            if frames_per_set is None:
-                if n_sets > 1:
-                    raise ValueError(f"{n_sets} weight sets need frames_per_set")
-                frames_per_set = max(frames, 1)
-            thr = np.full(nfft, np.inf, np.float32) if threshold is None else threshold
-            thr = self._on_device(temps, thr, np.float32, nfft, "threshold", f"nfft is {nfft}")
-            d_w = self._on_device(temps, w.view(np.float32), np.float32, 4 * n_sets * nfft, "weights", "")
-            self._count("cancel2")
-            return self._cleaned(n_samples, frames, CANCEL_DTYPE, lambda d_out, d_rec: self.cancel2_dev(
-                cap_a, cap_a.nbytes, first_a, cap_b, cap_b.nbytes, first_b, cap_c, cap_c.nbytes, first_c, n_samples, nfft,
-                d_w, frames_per_set, n_sets, thr, d_out, d_rec))
+        return self._cancel("cancel2", (a, b, c), (first_a, first_b, first_c), w.reshape(-1, 2 * nfft), threshold, nfft, n_samples,
+                            frames_per_set, self.cancel2_dev)
 
     def blank(self, raw, threshold: float, window: int = 16, guard: int = 8, first_sample: int = 0,
               n_samples: Optional[int] = None):
@@ -1323,8 +1319,7 @@ class Device:
         FINE_BLOCK samples alone.  What a sub-sample delay is estimated from: ``gpsjam.tdoa.fine_lag``."""
         lag_center, half_width, first_a, first_b = int(lag_center), int(half_width), int(first_a), int(first_b)
         with contextlib.ExitStack() as temps:
-            cap_a = temps.enter_context(self._resident(a))
-            cap_b = cap_a if b is a else temps.enter_context(self._resident(b))
+            cap_a, cap_b = self._residents(temps, a, b)
             if n_samples is None:
                 n_samples = max(0, min(cap_a.nsamples - first_a, cap_b.nsamples - first_b))
             n_samples, n_lags = int(n_samples), 2 * max(half_width, 0) + 1

@@ -144,9 +144,7 @@ def spectral_matrix(dev, main, aux_b, aux_c, lags=(0, 0), nfft: int = 256, frame
     nfft, m = int(nfft), int(frames_per_row)
     hop = nfft if hop is None else int(hop)
     with contextlib.ExitStack() as temps:
-        cap_a = temps.enter_context(dev._resident(main))
-        cap_b = cap_a if aux_b is main else temps.enter_context(dev._resident(aux_b))
-        cap_c = cap_a if aux_c is main else cap_b if aux_c is aux_b else temps.enter_context(dev._resident(aux_c))
+        cap_a, cap_b, cap_c = dev._residents(temps, main, aux_b, aux_c)
         if isinstance(lags, str):
             if lags != "k5":
                 raise ValueError(f'lags must be two integers or "k5", not {lags!r}')
@@ -244,7 +242,8 @@ def scan(dev, a, b, lag=0, fs: float = 2.048e6, nfft: int = 256, frames_per_row:
     """``dev.cross_spectrum`` over the whole pair, ``detect``, ``bands``, and each band's delay.  The pair is aligned
     by the integer ``lag`` first (samples by which b lags a): a positive lag advances first_b, a negative one first_a.
     ``lag="k5"`` takes K5's integer lag of the first K5_SAMPLES samples."""
-    with dev._resident(a) as cap_a, (dev._resident(b) if b is not a else contextlib.nullcontext(cap_a)) as cap_b:
+    with contextlib.ExitStack() as temps:
+        cap_a, cap_b = dev._residents(temps, a, b)
         lag = _k5_lag(dev, cap_a, cap_b) if lag == "k5" else int(lag)
         result = dev.cross_spectrum(cap_a, cap_b, nfft=nfft, hop=hop, frames_per_row=frames_per_row,
                                     first_a=max(-lag, 0), first_b=max(lag, 0))

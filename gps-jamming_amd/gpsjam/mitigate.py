@@ -278,6 +278,29 @@ class CleanedSpatial(NamedTuple):
     note: str
 
 
+def _copy_of_main(cancel, cap, n_aux: int, threshold, nfft: int, scan):
+    """The fields the two spatial results share when nothing was flagged: zero weights of ``cancel``'s rank, ``cancel`` run
+    with main in the place of every auxiliary, and the note that says so."""
+    zero = np.zeros((1, nfft) if n_aux == 1 else (1, n_aux, nfft), np.complex64)
+    cleaned, rec = cancel(*[cap] * (1 + n_aux), zero, threshold, nfft=nfft)
+    return cleaned, rec, zero, scan, [], [], False, "nothing coherent was flagged: a copy of main"
+
+
+def _suppression_db(rec, weights, frames_per_set: int, cancelled, nfft: int) -> List[float]:
+    """Per cancelled band 10 log10(sum total_in / sum total) of the records ``rec`` over the frames whose weight set is
+    not zero inside the band; NaN unless both sums are positive.  ``weights``: [n_sets][n_aux][nfft]."""
+    sets = np.minimum(np.arange(rec.size) // frames_per_set, weights.shape[0] - 1)
+    t_in, t_out = rec["total_in"].astype(np.float64), rec["total"].astype(np.float64)
+    shifted = _bands.shifted_order(nfft)
+    suppression = []
+    for bd in cancelled:
+        at = int(np.flatnonzero(shifted == bd.first_bin)[0])
+        active = np.any(weights[:, :, shifted[at:at + bd.n_bins]] != 0, axis=(1, 2))[sets]
+        num, den = t_in[active].sum(), t_out[active].sum()
+        suppression.append(float(10.0 * np.log10(num / den)) if num > 0 and den > 0 else float("nan"))
+    return suppression
+
+
 def clean_spatial(dev, main, aux, nfft: int = 1024, frames_per_row: int = 256, p_fa: float = 1e-6, lag="k5",
                   threshold=None, fs: float = 2.048e6) -> CleanedSpatial:
     """``main`` with what it shares with ``aux`` cancelled bin by bin (gj_cancel_dev).  ``main`` and ``aux``: resident
@@ -293,29 +316,20 @@ def clean_spatial(dev, main, aux, nfft: int = 1024, frames_per_row: int = 256, p
     With nothing flagged the result is a copy of the whole of ``main`` and ``cancelled`` is False."""
     from . import coherence
     nfft, m = int(nfft), int(frames_per_row)
-    with dev._resident(main) as cap_a, (dev._resident(aux) if aux is not main else contextlib.nullcontext(cap_a)) as cap_b:
+    with contextlib.ExitStack() as temps:
+        cap_a, cap_b = dev._residents(temps, main, aux)
         if excise_frames(cap_a.nsamples, nfft) == 0:
             raise ValueError(f"the capture holds {cap_a.nsamples} samples, fewer than one frame of {nfft}")
         found = coherence.scan(dev, cap_a, cap_b, lag=lag, fs=fs, nfft=nfft, frames_per_row=m, p_fa=p_fa)
         cells = coherence.detect_cells(found.result, p_fa)
         if not cells.flagged.any():
-            zero = np.zeros((1, nfft), np.complex64)
-            cleaned, rec = dev.cancel(cap_a, cap_a, zero, threshold, nfft=nfft)
-            return CleanedSpatial(cleaned, rec, zero, found, [], [], False, "nothing coherent was flagged: a copy of main")
+            return CleanedSpatial(*_copy_of_main(dev.cancel, cap_a, 1, threshold, nfft, found))
         weights = coherence.cancel_weights(found.result, cells, per_row=True)
         cleaned, rec = dev.cancel(cap_a, cap_b, weights, threshold, nfft=nfft, first_a=found.result.first_a,
                                   first_b=found.result.first_b, frames_per_set=2 * m)
     union = coherence.Detection(cells.flagged.any(axis=0), cells.threshold, cells.p_fa)
     cancelled = coherence.bands(found.result, union, fs)
-    sets = np.minimum(np.arange(rec.size) // (2 * m), weights.shape[0] - 1)
-    t_in, t_out = rec["total_in"].astype(np.float64), rec["total"].astype(np.float64)
-    shifted = _bands.shifted_order(nfft)
-    suppression = []
-    for bd in cancelled:
-        at = int(np.flatnonzero(shifted == bd.first_bin)[0])
-        active = np.any(weights[:, shifted[at:at + bd.n_bins]] != 0, axis=1)[sets]
-        num, den = t_in[active].sum(), t_out[active].sum()
-        suppression.append(float(10.0 * np.log10(num / den)) if num > 0 and den > 0 else float("nan"))
+    suppression = _suppression_db(rec, weights[:, None], 2 * m, cancelled, nfft)
     return CleanedSpatial(cleaned, rec, weights, found, cancelled, suppression, True, "")
 
 
@@ -351,9 +365,7 @@ def clean_spatial2(dev, main, aux_b, aux_c, nfft: int = 1024, frames_per_row: in
     from . import coherence
     nfft, m = int(nfft), int(frames_per_row)
     with contextlib.ExitStack() as temps:
-        cap_a = temps.enter_context(dev._resident(main))
-        cap_b = cap_a if aux_b is main else temps.enter_context(dev._resident(aux_b))
-        cap_c = cap_a if aux_c is main else cap_b if aux_c is aux_b else temps.enter_context(dev._resident(aux_c))
+        cap_a, cap_b, cap_c = dev._residents(temps, main, aux_b, aux_c)
         if excise_frames(cap_a.nsamples, nfft) == 0:
             raise ValueError(f"the capture holds {cap_a.nsamples} samples, fewer than one frame of {nfft}")
         mat = coherence.spectral_matrix(dev, cap_a, cap_b, cap_c, lags=lags, nfft=nfft, frames_per_row=m)
@@ -365,25 +377,14 @@ def clean_spatial2(dev, main, aux_b, aux_c, nfft: int = 1024, frames_per_row: in
         cells_b, cells_c = coherence.detect_cells(mat.ab, p_fa), coherence.detect_cells(mat.ac, p_fa)
         flagged = cells_b.flagged | cells_c.flagged
         if not flagged.any():
-            zero = np.zeros((1, 2, nfft), np.complex64)
-            cleaned, rec = dev.cancel2(cap_a, cap_a, cap_a, zero, threshold, nfft=nfft)
-            return CleanedSpatial2(cleaned, rec, zero, scans[0], [], [], False, "nothing coherent was flagged: a copy of main",
-                                   scans[1], scans[2])
+            return CleanedSpatial2(*_copy_of_main(dev.cancel2, cap_a, 2, threshold, nfft, scans[0]), scans[1], scans[2])
         weights = coherence.cancel_weights2(mat, flagged)
         cleaned, rec = dev.cancel2(cap_a, cap_b, cap_c, weights, threshold, nfft=nfft, first_a=mat.ab.first_a,
                                    first_b=mat.ab.first_b, first_c=mat.ac.first_b, frames_per_set=2 * m)
     union = coherence.Detection(flagged.any(axis=0), cells_b.threshold, cells_b.p_fa)
     msc = np.fmax(mat.ab.msc, mat.ac.msc)                     # a band's median MSC: the better auxiliary's, cell by cell
     cancelled = [coherence.Band(*run) for _, *run in _bands.runs(union.flagged, msc, fs)]
-    sets = np.minimum(np.arange(rec.size) // (2 * m), weights.shape[0] - 1)
-    t_in, t_out = rec["total_in"].astype(np.float64), rec["total"].astype(np.float64)
-    shifted = _bands.shifted_order(nfft)
-    suppression = []
-    for bd in cancelled:
-        at = int(np.flatnonzero(shifted == bd.first_bin)[0])
-        active = np.any(weights[:, :, shifted[at:at + bd.n_bins]] != 0, axis=(1, 2))[sets]
-        num, den = t_in[active].sum(), t_out[active].sum()
-        suppression.append(float(10.0 * np.log10(num / den)) if num > 0 and den > 0 else float("nan"))
+    suppression = _suppression_db(rec, weights, 2 * m, cancelled, nfft)
     return CleanedSpatial2(cleaned, rec, weights, scans[0], cancelled, suppression, True, "", scans[1], scans[2])
 
 
@@ -428,6 +429,21 @@ def clean_spoofed(dev, a, b, k: int = 2, search=None, tol: float = 0.15, min_com
         if own:
             search.close()
     return CleanedSpoofed(out_a.capture, out_b.capture, report, out_a.removals, out_b.removals, out_a.records, out_b.records)
+
+
+def _write(capture: Capture, path) -> None:
+    """A result's capture written to ``path`` and freed, whatever the writing does."""
+    try:
+        capture.download().tofile(path)
+    finally:
+        capture.free()
+
+
+def _print_bands(res) -> None:
+    """One line per cancelled band of a spatial result, with the suppression measured in it."""
+    for bd, db in zip(res.bands, res.suppression_db):
+        print(f"  {bd.freq_lo_hz / 1e3:9.1f} .. {bd.freq_hi_hz / 1e3:9.1f} kHz  ({bd.n_bins} bins)  median MSC {bd.median_msc:.3f}  "
+              f"suppression {db:.1f} dB")
 
 
 def main(argv=None) -> int:
@@ -503,15 +519,10 @@ def main(argv=None) -> int:
             with dev.capture(args.input) as cap, dev.capture(args.spatial) as aux_b, dev.capture(args.spatial2) as aux_c:
                 res = clean_spatial2(dev, cap, aux_b, aux_c, nfft=args.nfft, frames_per_row=args.frames_per_row, p_fa=args.p_fa,
                                      lags=lags, fs=args.fs)
-                try:
-                    res.capture.download().tofile(args.output)
-                finally:
-                    res.capture.free()
+                _write(res.capture, args.output)
         print(f"{args.output}: {res.records.size} frames of {args.nfft} points, aligned by {res.scan.lag} and {res.scan_c.lag}, "
               + (f"{len(res.bands)} band(s) cancelled with two auxiliaries" if res.cancelled else res.note))
-        for bd, db in zip(res.bands, res.suppression_db):
-            print(f"  {bd.freq_lo_hz / 1e3:9.1f} .. {bd.freq_hi_hz / 1e3:9.1f} kHz  ({bd.n_bins} bins)  median MSC {bd.median_msc:.3f}  "
-                  f"suppression {db:.1f} dB")
+        _print_bands(res)
         return 0
     if args.spatial:
         lag = "k5" if args.lag == "k5" else int(args.lag)
@@ -519,25 +530,17 @@ def main(argv=None) -> int:
             with dev.capture(args.input) as cap, dev.capture(args.spatial) as aux:
                 res = clean_spatial(dev, cap, aux, nfft=args.nfft, frames_per_row=args.frames_per_row, p_fa=args.p_fa, lag=lag,
                                     fs=args.fs)
-                try:
-                    res.capture.download().tofile(args.output)
-                finally:
-                    res.capture.free()
+                _write(res.capture, args.output)
         print(f"{args.output}: {res.records.size} frames of {args.nfft} points, aligned by {res.scan.lag}, "
               + (f"{len(res.bands)} band(s) cancelled" if res.cancelled else res.note))
-        for bd, db in zip(res.bands, res.suppression_db):
-            print(f"  {bd.freq_lo_hz / 1e3:9.1f} .. {bd.freq_hi_hz / 1e3:9.1f} kHz  ({bd.n_bins} bins)  median MSC {bd.median_msc:.3f}  "
-                  f"suppression {db:.1f} dB")
+        _print_bands(res)
         return 0
     if args.pulsed:
         rise_db = 6.0 if args.rise_db is None else args.rise_db
         with Device(args.device) as dev:
             with dev.capture(args.input) as cap:
                 res = clean_pulsed(dev, cap, window=args.window, guard=args.guard, rise_db=rise_db)
-                try:
-                    res.capture.download().tofile(args.output)
-                finally:
-                    res.capture.free()
+                _write(res.capture, args.output)
         print(f"{args.output}: window {args.window}, guard {args.guard}, threshold {res.threshold:.4g} LSB^2 with the floor from the "
               f"{res.floor_from}, {100.0 * res.blanked_share:.2f} % of the samples blanked on {int(res.records['n_rising'].sum())} "
               f"rising edges, {100.0 * res.removed_share:.2f} % of the power removed")
@@ -547,10 +550,7 @@ def main(argv=None) -> int:
     with Device(args.device) as dev:
         with dev.capture(args.input) as cap:
             res = (clean_swept if args.swept else clean)(dev, cap, nfft=args.nfft, rise_db=args.rise_db, fs=args.fs)
-            try:
-                res.capture.download().tofile(args.output)
-            finally:
-                res.capture.free()
+            _write(res.capture, args.output)
     print(f"{args.output}: {res.records.size} frames of {args.nfft} points, floor from the {res.floor_from}, "
           f"{100.0 * res.removed_share:.2f} % of the power removed")
     if args.swept:

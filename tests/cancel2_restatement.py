@@ -6,12 +6,13 @@ restatement (tests/cancel_restatement.py) already states is taken from there.
     A_f, B_f, C_f = fft(w * x[s_f : s_f + N]) of captures a, b, c at first_a, first_b, first_c;  s_f = f N/2
     Y_f     = (A_f - W1[set(f)] * B_f) - W2[set(f)] * C_f,   set(f) = min(f // frames_per_set, n_sets - 1)
     P_f, the mask, y_f, the overlap-add, the bytes and the records: cancel_restatement's, total_in being A's power
+
+cancel2 and cancel2_loop are cr.cancel_aux and cr.cancel_aux_loop with two auxiliaries.
 """
 import functools
 import math
 
 import numpy as np
-import scipy.fft
 
 import cancel_restatement as cr
 import csd_restatement as cs
@@ -56,65 +57,17 @@ def _weights(weights, nfft):
 
 def cancel2(raw_a, raw_b, raw_c, weights, thr, nfft, first_a=0, first_b=0, first_c=0, n_samples=None, frames_per_set=None,
             offset=127.5, scale=1.0 / 127.5, single=False):
-    """The definition on the bytes of the triple.  weights: complex[2][nfft] or [n_sets][2][nfft]; thr None: +inf.
-    single=True: the transforms, both predictions and both subtractions in complex64, everything else alike."""
-    raw_a, raw_b, raw_c = (np.asarray(r, np.uint8) for r in (raw_a, raw_b, raw_c))
-    if n_samples is None:
-        n_samples = min(raw_a.size // 2 - first_a, raw_b.size // 2 - first_b, raw_c.size // 2 - first_c)
-    h = nfft // 2
-    w = _weights(weights, nfft)
-    thr = np.full(nfft, np.inf) if thr is None else np.asarray(thr, np.float32).astype(np.float64)
-    A = cr.frame_spectra(raw_a, nfft, first_a, n_samples, offset, single)
-    B = cr.frame_spectra(raw_b, nfft, first_b, n_samples, offset, single)
-    Cc = cr.frame_spectra(raw_c, nfft, first_c, n_samples, offset, single)
-    nf = A.shape[0]
-    fps = nf if frames_per_set is None else int(frames_per_set)
-    assert fps >= 1 and (frames_per_set is not None or w.shape[0] == 1)
-    wf = w[set_of(nf, fps, w.shape[0])]
-    if not single:
-        wf = wf.astype(np.complex128)
-    Y = (A - wf[:, 0] * B) - wf[:, 1] * Cc
-    assert Y.dtype == (np.complex64 if single else np.complex128)
-    s2 = scale * scale
-    P = (np.abs(Y.astype(np.complex128)) ** 2) * s2
-    with np.errstate(invalid="ignore"):
-        cut = P > thr[None, :]               # strict; False against NaN
-    y = scipy.fft.ifft(np.where(cut, 0, Y).astype(Y.dtype), axis=1).astype(np.complex128)
-    rec = np.zeros(nf, RECORD64)
-    rec["total_in"] = ((np.abs(A.astype(np.complex128)) ** 2) * s2).sum(axis=1)
-    rec["total"], rec["removed"], rec["n_excised"] = P.sum(axis=1), np.where(cut, P, 0.0).sum(axis=1), cut.sum(axis=1)
-    t = (y[:-1, h:] + y[1:, :h]).reshape(-1)                     # samples [h, F h)
-    value = np.empty(2 * t.size)
-    value[0::2], value[1::2] = t.real + offset, t.imag + offset
-    out = raw_a[2 * first_a:2 * (first_a + n_samples)].copy()
-    out[2 * h:2 * h + value.size] = np.clip(np.rint(value.astype(np.float32)), 0, 255).astype(np.uint8)
-    return Cancelled(out, rec, value, P, cut, nfft)
+    """The definition on the bytes of the triple: cr.cancel_aux with two auxiliaries.  weights: complex[2][nfft] or
+    [n_sets][2][nfft]; thr None: +inf.  single=True: the transforms, both predictions and both subtractions in complex64."""
+    return cr.cancel_aux(raw_a, first_a, [(raw_b, first_b), (raw_c, first_c)], _weights(weights, nfft), thr, nfft, n_samples,
+                         frames_per_set, offset, scale, single)
 
 
 def cancel2_loop(raw_a, raw_b, raw_c, weights, thr, nfft, first_a, first_b, first_c, n_samples, frames_per_set, offset=127.5,
                  scale=1.0 / 127.5):
     """The same definition frame by frame with numpy's own transforms: (out, records)."""
-    h, w = nfft // 2, _weights(weights, nfft).astype(np.complex128)
-    xa, xb, xc = (er.unpack_lsb(np.asarray(r, np.uint8)[2 * f0:2 * (f0 + n_samples)], offset)
-                  for r, f0 in ((raw_a, first_a), (raw_b, first_b), (raw_c, first_c)))
-    win = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(nfft) / nfft)
-    thr = np.asarray(thr, np.float32).astype(np.float64)
-    acc = np.zeros(n_samples, np.complex128)
-    rec, f = [], 0
-    while f * h + nfft <= n_samples:
-        a, b, c = (np.fft.fft(win * x[f * h:f * h + nfft]) for x in (xa, xb, xc))
-        w1, w2 = w[min(f // frames_per_set, w.shape[0] - 1)]
-        y = (a - w1 * b) - w2 * c
-        p = (y.real ** 2 + y.imag ** 2) * scale * scale
-        keep = ~(p > thr)
-        rec.append((float(np.sum(np.abs(a) ** 2) * scale * scale), float(p.sum()), float(p[~keep].sum()), int(np.sum(~keep))))
-        acc[f * h:f * h + nfft] += np.fft.ifft(np.where(keep, y, 0))
-        f += 1
-    out = np.asarray(raw_a, np.uint8)[2 * first_a:2 * (first_a + n_samples)].copy()
-    body = np.empty(2 * (f - 1) * h)
-    body[0::2], body[1::2] = acc[h:f * h].real + offset, acc[h:f * h].imag + offset
-    out[2 * h:2 * f * h] = np.clip(np.rint(body.astype(np.float32)), 0, 255).astype(np.uint8)
-    return out, np.array(rec, RECORD64)
+    return cr.cancel_aux_loop(raw_a, first_a, [(raw_b, first_b), (raw_c, first_c)], _weights(weights, nfft), thr, nfft, n_samples,
+                              frames_per_set, offset, scale)
 
 
 def solve2(sbb, scc, sab, sac, sbc):

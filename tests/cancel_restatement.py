@@ -9,6 +9,9 @@ tests/cancel/test_round6_gpu.py import it.
     y_f     = ifft(Y_f where P_f <= thr else 0)
     y[t]    = y_{f-1}[t - s_{f-1}] + y_f[t - s_f];  u = clip(rint(float32(y + offset)), 0, 255) on samples [N/2, F N/2);
               the other samples are capture a's
+
+cancel_aux states it once for a list of auxiliaries, Y_f = (A_f - W_1 X_1f) - W_2 X_2f ..., for this canceller and the
+three-antenna one (tests/cancel2_restatement.py); everything from P_f on is the excisor's own text (er.finish).
 """
 import functools
 import math
@@ -76,52 +79,53 @@ def frame_spectra(raw, nfft, first, n_samples, offset=127.5, single=False):
     return scipy.fft.fft(seg.astype(np.complex64) if single else seg, axis=1)
 
 
-def cancel(raw_a, raw_b, weights, thr, nfft, first_a=0, first_b=0, n_samples=None, frames_per_set=None, offset=127.5,
-           scale=1.0 / 127.5, single=False):
-    """The definition on the bytes of the pair.  weights: complex[nfft] or [n_sets][nfft]; thr None: +inf.  single=True:
-    the transforms, the prediction and the subtraction in complex64, everything else alike."""
-    raw_a, raw_b = np.asarray(raw_a, np.uint8), np.asarray(raw_b, np.uint8)
+def cancel_aux(raw_a, first_a, aux, weights, thr, nfft, n_samples=None, frames_per_set=None, offset=127.5, scale=1.0 / 127.5,
+               single=False):
+    """The definition for any number of auxiliaries: aux = [(raw, first), ...], weights complex[n_sets][n_aux][nfft] (or
+    anything that reshapes to it); thr None: +inf.  Y = A, then Y = Y - W_i X_i for i in order.  single=True: the
+    transforms, every prediction and every subtraction in complex64, everything else alike (er.finish)."""
+    ins = [(np.asarray(raw, np.uint8), first) for raw, first in [(raw_a, first_a), *aux]]
     if n_samples is None:
-        n_samples = min(raw_a.size // 2 - first_a, raw_b.size // 2 - first_b)
-    h = nfft // 2
-    w = np.asarray(weights, np.complex64).reshape(-1, nfft)           # the library takes float32 pairs
-    thr = np.full(nfft, np.inf) if thr is None else np.asarray(thr, np.float32).astype(np.float64)
-    A = frame_spectra(raw_a, nfft, first_a, n_samples, offset, single)
-    B = frame_spectra(raw_b, nfft, first_b, n_samples, offset, single)
+        n_samples = min(raw.size // 2 - first for raw, first in ins)
+    w = np.asarray(weights, np.complex64).reshape(-1, len(aux), nfft)     # the library takes float32 pairs
+    A, *X = (frame_spectra(raw, nfft, first, n_samples, offset, single) for raw, first in ins)
     nf = A.shape[0]
     fps = nf if frames_per_set is None else int(frames_per_set)
     assert fps >= 1 and (frames_per_set is not None or w.shape[0] == 1)
     wf = w[set_of(nf, fps, w.shape[0])]
-    Y = A - (wf if single else wf.astype(np.complex128)) * B
+    if not single:
+        wf = wf.astype(np.complex128)
+    Y = A
+    for i, Xi in enumerate(X):
+        Y = Y - wf[:, i] * Xi
     assert Y.dtype == (np.complex64 if single else np.complex128)
-    s2 = scale * scale
-    P = (np.abs(Y.astype(np.complex128)) ** 2) * s2
-    with np.errstate(invalid="ignore"):
-        cut = P > thr[None, :]               # strict; False against NaN
-    y = scipy.fft.ifft(np.where(cut, 0, Y).astype(Y.dtype), axis=1).astype(np.complex128)
+    P, cut, sums, value, out = er.finish(Y, ins[0][0][2 * first_a:2 * (first_a + n_samples)], thr, nfft, offset, scale)
     rec = np.zeros(nf, RECORD64)
-    rec["total_in"] = ((np.abs(A.astype(np.complex128)) ** 2) * s2).sum(axis=1)
-    rec["total"], rec["removed"], rec["n_excised"] = P.sum(axis=1), np.where(cut, P, 0.0).sum(axis=1), cut.sum(axis=1)
-    t = (y[:-1, h:] + y[1:, :h]).reshape(-1)                     # samples [h, F h)
-    value = np.empty(2 * t.size)
-    value[0::2], value[1::2] = t.real + offset, t.imag + offset
-    out = raw_a[2 * first_a:2 * (first_a + n_samples)].copy()
-    out[2 * h:2 * h + value.size] = np.clip(np.rint(value.astype(np.float32)), 0, 255).astype(np.uint8)
+    rec["total_in"] = ((np.abs(A.astype(np.complex128)) ** 2) * (scale * scale)).sum(axis=1)
+    rec["total"], rec["removed"], rec["n_excised"] = sums
     return Cancelled(out, rec, value, P, cut, nfft)
 
 
-def cancel_loop(raw_a, raw_b, weights, thr, nfft, first_a, first_b, n_samples, frames_per_set, offset=127.5, scale=1.0 / 127.5):
+def cancel(raw_a, raw_b, weights, thr, nfft, first_a=0, first_b=0, n_samples=None, frames_per_set=None, offset=127.5,
+           scale=1.0 / 127.5, single=False):
+    """The definition on the bytes of the pair: cancel_aux with one auxiliary.  weights: complex[nfft] or [n_sets][nfft]."""
+    return cancel_aux(raw_a, first_a, [(raw_b, first_b)], weights, thr, nfft, n_samples, frames_per_set, offset, scale, single)
+
+
+def cancel_aux_loop(raw_a, first_a, aux, weights, thr, nfft, n_samples, frames_per_set, offset=127.5, scale=1.0 / 127.5):
     """The same definition frame by frame with numpy's own transforms: (out, records)."""
-    h, w = nfft // 2, np.asarray(weights, np.complex64).reshape(-1, nfft).astype(np.complex128)
-    xa = er.unpack_lsb(np.asarray(raw_a, np.uint8)[2 * first_a:2 * (first_a + n_samples)], offset)
-    xb = er.unpack_lsb(np.asarray(raw_b, np.uint8)[2 * first_b:2 * (first_b + n_samples)], offset)
+    h, w = nfft // 2, np.asarray(weights, np.complex64).reshape(-1, len(aux), nfft).astype(np.complex128)
+    xs = [er.unpack_lsb(np.asarray(raw, np.uint8)[2 * first:2 * (first + n_samples)], offset)
+          for raw, first in [(raw_a, first_a), *aux]]
     win = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(nfft) / nfft)
     thr = np.asarray(thr, np.float32).astype(np.float64)
     acc = np.zeros(n_samples, np.complex128)
     rec, f = [], 0
     while f * h + nfft <= n_samples:
-        a, b = np.fft.fft(win * xa[f * h:f * h + nfft]), np.fft.fft(win * xb[f * h:f * h + nfft])
-        y = a - w[min(f // frames_per_set, w.shape[0] - 1)] * b
+        a, *others = (np.fft.fft(win * x[f * h:f * h + nfft]) for x in xs)
+        y = a
+        for wi, xi in zip(w[min(f // frames_per_set, w.shape[0] - 1)], others):
+            y = y - wi * xi
         p = (y.real ** 2 + y.imag ** 2) * scale * scale
         keep = ~(p > thr)
         rec.append((float(np.sum(np.abs(a) ** 2) * scale * scale), float(p.sum()), float(p[~keep].sum()), int(np.sum(~keep))))
@@ -132,6 +136,10 @@ def cancel_loop(raw_a, raw_b, weights, thr, nfft, first_a, first_b, n_samples, f
     body[0::2], body[1::2] = acc[h:f * h].real + offset, acc[h:f * h].imag + offset
     out[2 * h:2 * f * h] = np.clip(np.rint(body.astype(np.float32)), 0, 255).astype(np.uint8)
     return out, np.array(rec, RECORD64)
+
+
+def cancel_loop(raw_a, raw_b, weights, thr, nfft, first_a, first_b, n_samples, frames_per_set, offset=127.5, scale=1.0 / 127.5):
+    return cancel_aux_loop(raw_a, first_a, [(raw_b, first_b)], weights, thr, nfft, n_samples, frames_per_set, offset, scale)
 
 
 # ---------------------------------------------------------------------------------------------------- parity inputs

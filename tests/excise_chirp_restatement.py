@@ -82,7 +82,6 @@ def excise_chirp(raw, thr, rates, nfft, first_sample=0, n_samples=None, offset=1
     assert nf >= 1 and first_sample + n_samples <= raw.size // 2 and len(rates) == nf
     src = raw[2 * first_sample:2 * (first_sample + n_samples)]
     x = er.unpack_lsb(src, offset)
-    thr = np.asarray(thr, np.float32).astype(np.float64)
     idx = (h * np.arange(nf))[:, None] + np.arange(nfft)[None, :]
     seg = x[idx] * er.hann(nfft)[None, :]
     c = np.stack([factors(q, nfft, single) for q in rates])
@@ -90,17 +89,9 @@ def excise_chirp(raw, thr, rates, nfft, first_sample=0, n_samples=None, offset=1
         seg = seg.astype(np.complex64)
     X = scipy.fft.fft(seg * c, axis=1)
     assert X.dtype == (np.complex64 if single else np.complex128)
-    P = (np.abs(X.astype(np.complex128)) ** 2) * (scale * scale)
-    with np.errstate(invalid="ignore"):
-        cut = P > thr[None, :]               # strict; False against NaN
-    Y = (scipy.fft.ifft(np.where(cut, 0, X).astype(X.dtype), axis=1) * np.conj(c)).astype(np.complex128)
+    P, _, sums, value, out = er.finish(X, src, thr, nfft, offset, scale, rechirp=np.conj(c))
     rec = np.zeros(nf, er.RECORD64)
-    rec["total"], rec["removed"], rec["n_excised"] = P.sum(axis=1), np.where(cut, P, 0.0).sum(axis=1), cut.sum(axis=1)
-    y = (Y[:-1, h:] + Y[1:, :h]).reshape(-1)                     # samples [h, F h)
-    value = np.empty(2 * y.size)
-    value[0::2], value[1::2] = y.real + offset, y.imag + offset
-    out = src.copy()
-    out[2 * h:2 * h + value.size] = np.clip(np.rint(value.astype(np.float32)), 0, 255).astype(np.uint8)
+    rec["total"], rec["removed"], rec["n_excised"] = sums
     return er.Excised(out, rec, value, P, nfft)
 
 

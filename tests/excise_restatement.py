@@ -75,6 +75,29 @@ class Excised:
         return self.records.size * self.nfft    # one past the last excised byte (sample F N/2)
 
 
+def finish(Y, src, thr, nfft, offset, scale, rechirp=None):
+    """What the excisors and the cancellers do alike behind their spectra Y[F][nfft] (complex64 or complex128; the inverse
+    keeps that precision): the powers, the mask against `thr` (None: +inf), the inverse, the overlap-add and the bytes
+    over a copy of `src`, the bytes of the range.  `rechirp`: factors[F][nfft] that every frame is multiplied with between
+    the inverse and the overlap-add, in Y's precision.  Returns (P, cut, sums, value, out); sums = (total, removed,
+    n_excised) per frame, for the caller's own record type."""
+    h = nfft // 2
+    thr = np.full(nfft, np.inf) if thr is None else np.asarray(thr, np.float32).astype(np.float64)
+    P = (np.abs(Y.astype(np.complex128)) ** 2) * (scale * scale)
+    with np.errstate(invalid="ignore"):
+        cut = P > thr[None, :]               # strict; False against NaN
+    y = scipy.fft.ifft(np.where(cut, 0, Y).astype(Y.dtype), axis=1)
+    if rechirp is not None:
+        y = y * rechirp
+    y = y.astype(np.complex128)
+    t = (y[:-1, h:] + y[1:, :h]).reshape(-1)                     # samples [h, F h)
+    value = np.empty(2 * t.size)
+    value[0::2], value[1::2] = t.real + offset, t.imag + offset
+    out = src.copy()
+    out[2 * h:2 * h + value.size] = np.clip(np.rint(value.astype(np.float32)), 0, 255).astype(np.uint8)
+    return P, cut, (P.sum(axis=1), np.where(cut, P, 0.0).sum(axis=1), cut.sum(axis=1)), value, out
+
+
 def excise(raw, thr, nfft, first_sample=0, n_samples=None, offset=127.5, scale=1.0 / 127.5, single=False):
     """The definition on the bytes `raw`.  single=True: the transforms in complex64 (scipy.fft keeps the input's
     precision), everything else alike."""
@@ -86,23 +109,13 @@ def excise(raw, thr, nfft, first_sample=0, n_samples=None, offset=127.5, scale=1
     assert nf >= 1 and first_sample + n_samples <= raw.size // 2
     src = raw[2 * first_sample:2 * (first_sample + n_samples)]
     x = unpack_lsb(src, offset)
-    thr = np.asarray(thr, np.float32).astype(np.float64)
     idx = (h * np.arange(nf))[:, None] + np.arange(nfft)[None, :]
     seg = x[idx] * hann(nfft)[None, :]
     if single:
         seg = seg.astype(np.complex64)
-    X = scipy.fft.fft(seg, axis=1)
-    P = (np.abs(X.astype(np.complex128)) ** 2) * (scale * scale)
-    with np.errstate(invalid="ignore"):
-        cut = P > thr[None, :]               # strict; False against NaN
-    Y = scipy.fft.ifft(np.where(cut, 0, X).astype(X.dtype), axis=1).astype(np.complex128)
+    P, _, sums, value, out = finish(scipy.fft.fft(seg, axis=1), src, thr, nfft, offset, scale)
     rec = np.zeros(nf, RECORD64)
-    rec["total"], rec["removed"], rec["n_excised"] = P.sum(axis=1), np.where(cut, P, 0.0).sum(axis=1), cut.sum(axis=1)
-    y = (Y[:-1, h:] + Y[1:, :h]).reshape(-1)                     # samples [h, F h)
-    value = np.empty(2 * y.size)
-    value[0::2], value[1::2] = y.real + offset, y.imag + offset
-    out = src.copy()
-    out[2 * h:2 * h + value.size] = np.clip(np.rint(value.astype(np.float32)), 0, 255).astype(np.uint8)
+    rec["total"], rec["removed"], rec["n_excised"] = sums
     return Excised(out, rec, value, P, nfft)
 
 

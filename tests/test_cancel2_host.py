@@ -388,6 +388,55 @@ class _PairLib(HostLib):
         return 0
 
 
+class _CountingLib(_PairLib):
+    """The double with every entry point that cross_spectrum, cancel, cancel2 and xcorr_fine reach, which also keeps the
+    size of every upload in ``uploads``."""
+
+    def __init__(self):
+        super().__init__()
+        self.uploads = []
+
+    def gj_upload(self, ctx, data, nbytes, ref):
+        self.uploads.append(int(nbytes))
+        return super().gj_upload(ctx, data, nbytes, ref)
+
+    def gj_xcorr_fine_dev(self, *args):                             # the sums are not what the test below reads
+        return 0
+
+
+def test_an_input_given_twice_is_resident_once():
+    """Device._residents under the four wrappers that take several captures, at the smallest valid shape: the same object
+    in every place is uploaded once and freed, equal but distinct arrays once each, a caller's Capture never uploaded and
+    never freed, and a freed Capture in any place is the one ValueError with nothing allocated."""
+    nfft, n = 16, 64
+    dev = host_lib.host_device(_CountingLib())
+    lib = dev._lib
+    raw = c2.parity_triple()[0][:2 * n]
+    twin = raw.copy()
+    calls = {                                                       # name -> (captures it takes, the call)
+        "cross_spectrum": (2, lambda x, y: dev.cross_spectrum(x, y, nfft=nfft, frames_per_row=2)),
+        "cancel": (2, lambda x, y: dev.cancel(x, y, np.zeros(nfft), nfft=nfft)[0].free()),
+        "cancel2": (3, lambda x, y, z: dev.cancel2(x, y, z, np.zeros((2, nfft)), nfft=nfft)[0].free()),
+        "xcorr_fine": (2, lambda x, y: dev.xcorr_fine(x, y, half_width=2)),
+    }
+    for name, (places, call) in calls.items():
+        lib.uploads.clear()
+        call(*[raw] * places)
+        assert lib.uploads == [2 * n] and not lib.mem, f"{name}: one object in every place is uploaded once, and freed"
+        call(*[raw, twin, raw][:places])
+        assert lib.uploads == [2 * n] * 3 and not lib.mem, f"{name}: equal but distinct arrays are uploaded once each"
+        assert dev.kernel_calls[name] == 2
+        with gpsjam.Capture(dev, raw) as cap:
+            lib.uploads.clear()
+            call(*[cap] * places)
+            assert lib.uploads == [] and cap.ptr and set(lib.mem) == {cap.ptr}, f"{name}: a caller's capture is left alone"
+            for k in range(places):
+                host_lib.check_freed(dev, raw, lambda dead: call(*[dead if j == k else cap for j in range(places)]))
+            assert lib.uploads == [2 * n] * places, "check_freed's own captures, and nothing else"
+        assert not lib.mem
+    dev._ctx = None
+
+
 def test_clean_spatial2_with_nothing_flagged_returns_a_copy(host_dev):
     lib = host_dev._lib
     a, b, c = _spatial_triple(jam_rows=())
