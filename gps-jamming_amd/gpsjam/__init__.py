@@ -32,7 +32,8 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "BLANK_DTYPE", "BLANK_BLOCK", "blank_blocks", "FINE_BLOCK", "FINE_MAX_HALF", "fine_blocks", "FineCorr",
            "CrossSpectrum", "csd_rows", "CANCEL_DTYPE", "CORR_MAX_BLOCK", "CORR_CHANNEL_DTYPE", "corr_blocks", "CorrBank",
            "ACQ_MAX_PEAKS", "ACQ_PEAK_DTYPE", "ACQ_FLOOR_DTYPE", "SUB_BLOCK", "SUB_DTYPE", "SUB_FRAC", "SUB_MAX_AMP",
-           "subtract_blocks"]
+           "subtract_blocks", "ALIGN_BLOCK", "ALIGN_DTYPE", "ALIGN_PHASES", "ALIGN_TAPS", "ALIGN_ROT_LEN", "AlignParams",
+           "align_blocks"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -262,6 +263,32 @@ def subtract_blocks(n_samples: int) -> int:
     if not 0 <= int(n_samples) < 2 ** 64:
         return 0
     return int(_ffi.load().gj_subtract_blocks(int(n_samples)))
+
+
+ALIGN_BLOCK = _ffi.GJ_ALIGN_BLOCK
+ALIGN_PHASES = _ffi.GJ_ALIGN_PHASES
+ALIGN_TAPS = _ffi.GJ_ALIGN_TAPS
+ALIGN_ROT_LEN = _ffi.GJ_ALIGN_ROT_LEN
+ALIGN_DTYPE = np.dtype([("power_out", np.uint64), ("n_clipped", np.int32), ("n_edge", np.int32)])
+AlignParams = _ffi.AlignParams
+
+
+def align_blocks(n_out: int) -> int:
+    """Records of the pair alignment over n_out output samples: one per ALIGN_BLOCK samples, the last one ragged
+    (gj_align_blocks)."""
+    if not 0 <= int(n_out) < 2 ** 64:
+        return 0
+    return int(_ffi.load().gj_align_blocks(int(n_out)))
+
+
+def _align_params(params) -> "_ffi.AlignParams":
+    """An ``AlignParams`` as it is; ``(pos0, pos_step, rot_phase, rot_step)`` made into one (the phases modulo 2^32)."""
+    if isinstance(params, _ffi.AlignParams):
+        return params
+    pos0, pos_step, rot_phase, rot_step = (int(v) for v in params)
+    if not -2 ** 63 <= pos0 < 2 ** 63 or not 0 <= pos_step < 2 ** 64:
+        raise GpsJamError(-5, "unsupported: a position outside 64 bits")
+    return _ffi.AlignParams(pos0, pos_step, rot_phase & 0xFFFFFFFF, rot_step & 0xFFFFFFFF, 0)
 
 
 ACQ_MAX_PEAKS = _ffi.GJ_ACQ_MAX_PEAKS
@@ -1379,6 +1406,26 @@ class Device:
                 cap, cap.nbytes, first_sample, n_samples, block_samples, d_codes, n_rows, d_ch, rec.size, d_amp,
                 _ffi.GJ_SUB_DITHER if dither else 0, seed, d_out, d_rec))
 
+    def align(self, capture, params, taps, rot, n_out: Optional[int] = None):
+        """Pair alignment (gj_align_dev): ``n_out`` samples (default: as many as ``capture`` holds) read from ``capture``
+        along the time base and the phase of ``params`` -- an ``AlignParams`` or ``(pos0, pos_step, rot_phase, rot_step)``,
+        what ``gpsjam.align.params`` makes of a lag, a drift and an offset -- through the polyphase rows ``taps``
+        (int16[ALIGN_PHASES][ALIGN_TAPS], ``gpsjam.align.taps``) and the turn ``rot`` (int16[ALIGN_ROT_LEN],
+        ``gpsjam.align.rot_table``), each on the host (uploaded) or in a device buffer.  ``capture``: host bytes
+        (uploaded once) or a resident ``Capture``.  Returns ``(aligned, records)``: a resident ``Capture`` of its own
+        (the caller frees it) and one ALIGN_DTYPE record per ALIGN_BLOCK samples.  The arguments are checked by the
+        library: a refusal raises ``GpsJamError``."""
+        params = _align_params(params)
+        with contextlib.ExitStack() as temps:
+            cap = temps.enter_context(self._resident(capture))
+            n_out = cap.nsamples if n_out is None else int(n_out)
+            d_taps = self._on_device(temps, taps, np.int16, ALIGN_PHASES * ALIGN_TAPS, "taps",
+                                     f"{ALIGN_PHASES} rows of {ALIGN_TAPS} take {ALIGN_PHASES * ALIGN_TAPS}")
+            d_rot = self._on_device(temps, rot, np.int16, ALIGN_ROT_LEN, "rot", f"one turn takes {ALIGN_ROT_LEN}")
+            self._count("align")
+            return self._cleaned(max(n_out, 0), align_blocks(max(n_out, 0)), ALIGN_DTYPE, lambda d_out, d_rec: self.align_dev(
+                cap, cap.nbytes, params, d_taps, d_rot, n_out, d_out, d_rec))
+
     def acq_peaks(self, power, k: int = 2, guard: int = 4, shape=None):
         """The K-peak search (gj_acq_peaks_dev) over power surfaces double[n_prn][n_freq][nsamp]: per PRN the ``k``
         largest peaks under successive exclusion of the columns within ``guard`` (circular) of a peak already taken, and
@@ -1437,6 +1484,14 @@ class Device:
                                               int(block_samples), _ptr(d_codes), int(n_code_rows), _ptr(d_channels),
                                               int(n_channels), _ptr(d_amp), int(flags), int(seed) & 0xFFFFFFFF, _ptr(d_out),
                                               _ptr(d_blocks) or None))
+
+    def align_dev(self, d_iq, nbytes, params, d_taps, d_rot, n_out, d_out, d_blocks=None):
+        """gj_align_dev: 2 * n_out aligned bytes into d_out and, if asked for, one 16-byte record (ALIGN_DTYPE) per
+        ALIGN_BLOCK samples into d_blocks, on the context's stream."""
+        if not 0 <= int(n_out) < 2 ** 64 or not 0 <= int(nbytes) < 2 ** 64:
+            raise GpsJamError(-5, "unsupported: a size outside 64 bits")
+        self._check(self._lib.gj_align_dev(self._ctx, _ptr(d_iq), int(nbytes), _align_params(params), _ptr(d_taps), _ptr(d_rot),
+                                           int(n_out), _ptr(d_out), _ptr(d_blocks) or None))
 
     def xcorr_fine_dev(self, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, lag_center, half_width, d_total,
                        d_blocks=None):

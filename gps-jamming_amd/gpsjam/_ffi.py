@@ -167,6 +167,17 @@ class SubtractBlock(C.Structure):
     _fields_ = [("total", C.c_uint64), ("removed", C.c_uint64), ("n_clipped", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AlignParams(C.Structure):
+    """gj_align_params: the time base and the phase of one gj_align_dev call, passed by value (include/gpsjam.h)."""
+    _fields_ = [("pos0", C.c_int64), ("pos_step", C.c_uint64), ("rot_phase", C.c_uint32), ("rot_step", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+class AlignBlock(C.Structure):
+    """gj_align_block: one GJ_ALIGN_BLOCK-sample record of the pair alignment (include/gpsjam.h)."""
+    _fields_ = [("power_out", C.c_uint64), ("n_clipped", C.c_int32), ("n_edge", C.c_int32)]
+
+
 GJ_CP_ODD_CHUNK_ZERO = 1
 GJ_WELCH_SHIFT = 1
 GJ_MAX_ANTENNAS = 16
@@ -191,6 +202,12 @@ GJ_SUB_BLOCK = 4096
 GJ_SUB_FRAC = 16
 GJ_SUB_MAX_AMP = 1 << 19
 GJ_SUB_DITHER = 1
+GJ_ALIGN_PHASES = 256
+GJ_ALIGN_TAPS = 16
+GJ_ALIGN_ROT_LEN = 1024
+GJ_ALIGN_BLOCK = 4096
+GJ_ALIGN_MAX_DRIFT = 1 << 24
+GJ_ALIGN_MAX_SAMPLES = 1 << 28
 GJ_CORR_COS_TABLE = (32, 30, 23, 12, 0, -12, -23, -30, -32, -30, -23, -12, 0, 12, 23, 30)
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
@@ -315,6 +332,8 @@ SIGNATURES = {
     "gj_corr_bank_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
     "gj_subtract_blocks": (_sz, [_sz]),
     "gj_subtract_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _i, _vp, _i, _vp, _i, C.c_uint32, _vp, _vp]),
+    "gj_align_blocks": (_sz, [_sz]),
+    "gj_align_dev": (_i, [_vp, _vp, _sz, AlignParams, _vp, _vp, _sz, _vp, _vp]),
     "gj_pack_result_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gj_synth_u8_dev": (_i, [_vp, C.POINTER(SynthParams), C.c_int64, _sz, _vp]),
 }

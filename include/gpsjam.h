@@ -966,6 +966,66 @@ int gj_subtract_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t firs
                     int flags, uint32_t seed, uint8_t* d_out /* [2*n_samples] */,
                     gj_subtract_block* d_blocks /* [gj_subtract_blocks(n_samples)] or NULL */);
 
+/* ------------------------------------------------- pair alignment --------------------- */
+/* One uint8 I/Q capture written from another along a linear time base and a linear phase: antenna b brought onto
+ * antenna a's clock, for receivers that each run on a crystal of their own (the crystal sets the sample clock AND the
+ * tuner: 1 ppm is a slip of 20 samples over 10 s and 1575 Hz at L1).  The capture is resampled by a polyphase FIR,
+ * rotated, and rounded ONCE; every step from the byte to the byte is integer arithmetic.  gpsjam/align.py makes the
+ * tables and the parameters (taps, rot_table, params), estimates lag, drift and offset of a pair (estimate) and joins
+ * the pieces (to).
+ *
+ * I, Q are taken as u = 2*byte - 255 WHATEVER gj_set_unpack says, and u is ZERO outside samples 0 .. nbytes/2 - 1 of
+ * the source.  With P = GJ_ALIGN_PHASES = 256, T = GJ_ALIGN_TAPS = 16, GJ_ALIGN_ROT_LEN = 1024, for n = 0 .. n_out-1:
+ *
+ *   pos   = pos0 + n*pos_step + 2^23          int64, Q31.32 source samples; mathematical floor below
+ *   k     = floor(pos / 2^32),   p = (pos mod 2^32) >> 24
+ *   yI    = sum_{j=0..15} taps[p][j] * uI[k - 7 + j]            (yQ likewise)    |y| <= 16*255*32768 < 2^31
+ *   theta = (rot_phase + n*rot_step) mod 2^32,   i = ((theta + 2^21) >> 22) & 1023
+ *   c = rot[i],  s = rot[(i - 256) & 1023]
+ *   zI = yI*c - yQ*s,   zQ = yI*s + yQ*c                        int64: y times (c + js)
+ *   out byte = clamp(floor(z / 2^29) + 128, 0, 255)
+ *
+ * taps (int16[256][16], unit gain 16384: row p interpolates at k + p/256, tap 7 on sample k) and rot (int16[1024],
+ * 16384 cos(2 pi i / 1024)) are the CALLER's device tables, as d_codes is the bank's: the bytes depend on no libm.
+ * Any int16 values are accepted: the widths above hold at the full range.  With row 0 of taps the delta at j = 7,
+ * rot[0] = 16384, pos0 = 0, pos_step = 2^32 and rot_phase = rot_step = 0 the call is the identity, byte for byte:
+ * z = u * 2^28 and floor((2b - 255) / 2) + 128 = b.  pos and theta are functions of n alone: a call on n = n1 ..
+ * with pos0 + n1*pos_step and rot_phase + n1*rot_step in their places writes the bytes the larger call writes there.
+ *
+ * d_out: 2*n_out bytes, any alignment (16-byte stores where it is 16-byte aligned).  d_blocks (optional, may be NULL;
+ * the bytes are the same) receives one record per GJ_ALIGN_BLOCK output samples, the last one ragged.
+ *
+ * Limits (GJ_ERR_UNSUPPORTED): |pos_step - 2^32| <= GJ_ALIGN_MAX_DRIFT = 2^24 (3900 ppm: no anti-alias stage is needed,
+ * and the source span of GJ_ALIGN_BLOCK outputs is bounded); n_out 1 .. GJ_ALIGN_MAX_SAMPLES; |pos0| < 2^60.
+ * GJ_ERR_INVALID: a null ctx, d_iq, d_taps, d_rot or d_out; an odd d_iq; a d_taps or d_rot that is not 4-byte aligned;
+ * a d_blocks that is not 8-byte aligned; reserved != 0; a d_out whose 2*n_out bytes overlap d_iq[0, nbytes) anywhere.
+ * A refused call enqueues nothing.  One launch on the context's stream; no workspace, no memset, no atomics: the call
+ * never allocates.  Every byte and every record is written by exactly one workgroup. */
+#define GJ_ALIGN_PHASES 256            /* rows of taps: sub-sample positions */
+#define GJ_ALIGN_TAPS 16               /* taps per row */
+#define GJ_ALIGN_ROT_LEN 1024          /* entries of rot: one turn */
+#define GJ_ALIGN_BLOCK 4096            /* output samples per record */
+#define GJ_ALIGN_MAX_DRIFT (1 << 24)   /* |pos_step - 2^32| */
+#define GJ_ALIGN_MAX_SAMPLES (1 << 28) /* n_out */
+typedef struct gj_align_params {       /* 32 bytes, passed by value */
+    int64_t pos0;        /* source position of output sample 0, Q31.32 samples */
+    uint64_t pos_step;   /* source samples per output sample, Q32.32 */
+    uint32_t rot_phase;  /* phase of output sample 0, 2^32 per turn */
+    uint32_t rot_step;   /* phase per output sample */
+    uint64_t reserved;   /* 0 */
+} gj_align_params;
+typedef struct gj_align_block {        /* 16 bytes, all exact integers */
+    uint64_t power_out;  /* sum of (2*out - 255)^2 over both bytes of the block's output samples */
+    int32_t n_clipped;   /* bytes that the clamp to 0 .. 255 changed */
+    int32_t n_edge;      /* samples with at least one tap outside the source */
+} gj_align_block;
+/* records of the alignment: ceil(n_out / GJ_ALIGN_BLOCK); pure host arithmetic, no context */
+size_t gj_align_blocks(size_t n_out);
+int gj_align_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, gj_align_params params,
+                 const int16_t* d_taps /* [GJ_ALIGN_PHASES][GJ_ALIGN_TAPS] */, const int16_t* d_rot /* [GJ_ALIGN_ROT_LEN] */,
+                 size_t n_out, uint8_t* d_out /* [2*n_out] */,
+                 gj_align_block* d_blocks /* [gj_align_blocks(n_out)] or NULL */);
+
 /* ------------------------------------------------- per-stream result vector ---------- */
 /* What one rank sends to rank 0 (gpsjam/sharded.py):
  * double[40 + n_chunks + nperseg + 5*pair_capacity] =
