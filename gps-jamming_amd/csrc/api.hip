@@ -648,6 +648,7 @@ int gj_pack_result_dev(gj_ctx* ctx, size_t n_chunks, const float* d_power, const
         return fail(ctx, GJ_ERR_INVALID, "null buffer");
     if (n_pairs < 0 || n_pairs > pair_capacity) return fail(ctx, GJ_ERR_INVALID, "n_pairs %d exceeds the capacity %d", n_pairs, pair_capacity);
     if (n_pairs && (!d_pairs || !d_lags || !d_peaks || !d_margins)) return fail(ctx, GJ_ERR_INVALID, "null pair buffer");
+    if (nperseg < 16 || nperseg > 4096 || (nperseg & (nperseg - 1))) return fail(ctx, GJ_ERR_UNSUPPORTED, "nperseg %d", nperseg);
     return launch_pack_result(ctx, n_chunks, d_power, d_stats, d_amp, d_onset, d_psd, rows, nperseg, rank, n_pairs,
                               pair_capacity, d_pairs, d_lags, d_peaks, d_margins, d_out);
 }

@@ -280,6 +280,9 @@ __device__ unsigned block_select(const unsigned (&reg)[kThrPerThread], const flo
 // whole 256-thread workgroup; `sh` is the workgroup's scratch
 __device__ __forceinline__ void power_threshold_body(const float* __restrict__ power, size_t n, float pct, float ratio,
                                                      float* __restrict__ stats, uint8_t* __restrict__ mask, ThrShared& sh) {
+    // numpy rounds every operation of its rule on its own: no product may be fused with the sum or difference behind it
+    // (virtual index and its fraction, the lerp), in any of the three kernels this body is compiled into
+#pragma clang fp contract(off)
     const int tid = threadIdx.x;
     const bool cached = n <= (size_t)kThrCache;
     if (tid == 0) { sh.nan_flag = 0; sh.above = 0; sh.count_le = 0; sh.next_key = 0xffffffffu; }

@@ -1043,7 +1043,8 @@ int gj_align_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, gj_align_param
  * the float32 power map, the mean over the rows of the PSD waterfall, and the pairs THIS stream
  * solved as {i, j, lag, peak, margin} each (d_pairs = {i0,j0,i1,j1,...} and the outputs of
  * gj_xcorr_slots_dev, all DEVICE arrays), zero-padded to pair_capacity -- packed by one kernel
- * from device-resident outputs (no host synchronisation). */
+ * from device-resident outputs (no host synchronisation).  nperseg: power of two, 16..4096, as K2 takes it
+ * (GJ_ERR_UNSUPPORTED otherwise, nothing is written); rows may be 0 (d_psd NULL): the spectrum is then zero. */
 #define GJ_RESULT_HEADER 40
 #define GJ_RESULT_PAIR_FIELDS 5
 int gj_pack_result_dev(gj_ctx* ctx, size_t n_chunks, const float* d_power, const float* d_stats,
