@@ -9,8 +9,8 @@ tests/test_align_host.py holds to a per-sample Python-int loop).  Everything the
 EVERY byte and EVERY record is equal, bit for bit.  Every call writes into sentinel-filled buffers whose 256 bytes in
 front of and behind the call's output must stay untouched.  The figures of the end-to-end test are held to what
 tests/test_align_host.py measures on the CPU with the same host code on restated integers.  No capture here is longer
-than 2^16 samples; n_out = 2^28, the limit itself, is not run (its output alone is 512 MiB): the 64-bit products of the
-position are covered by the "far" cases, whose pos0 is the limit's."""
+than 2^16 samples: the 64-bit products of the position are covered by the "far" cases, whose pos0 is the limit's.  More
+tiles than workgroups, and n_out = 2^28, the limit itself, run in tests/tile_loops/."""
 import numpy as np
 import pytest
 

@@ -11,7 +11,7 @@ so EVERY byte and EVERY record is equal, bit for bit.  Every call writes into se
 front of and behind the call's output must stay untouched.  The float figures of the end-to-end test are held to what
 tests/test_subtract_host.py measures on the CPU with the same host code on restated integers.  A range that starts
 above sample 2^31 is not run here (no fixture holds such a capture cheaply): the 64-bit dither key is covered on the
-CPU."""
+CPU, and on the GPU in tests/tile_loops/."""
 import numpy as np
 import pytest
 
