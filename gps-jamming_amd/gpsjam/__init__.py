@@ -33,7 +33,8 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "CrossSpectrum", "csd_rows", "CANCEL_DTYPE", "CORR_MAX_BLOCK", "CORR_CHANNEL_DTYPE", "corr_blocks", "CorrBank",
            "ACQ_MAX_PEAKS", "ACQ_PEAK_DTYPE", "ACQ_FLOOR_DTYPE", "SUB_BLOCK", "SUB_DTYPE", "SUB_FRAC", "SUB_MAX_AMP",
            "subtract_blocks", "ALIGN_BLOCK", "ALIGN_DTYPE", "ALIGN_PHASES", "ALIGN_TAPS", "ALIGN_ROT_LEN", "AlignParams",
-           "align_blocks"]
+           "align_blocks", "TRACK_MAX_CHANNELS", "TRACK_MAX_EPOCHS", "TRACK_MAX_GAIN", "TRACK_STATE_DTYPE", "TRACK_EPOCH_DTYPE",
+           "TrackParams"]
 
 _default = None
 _default_lock = __import__("threading").Lock()
@@ -289,6 +290,44 @@ def _align_params(params) -> "_ffi.AlignParams":
     if not -2 ** 63 <= pos0 < 2 ** 63 or not 0 <= pos_step < 2 ** 64:
         raise GpsJamError(-5, "unsupported: a position outside 64 bits")
     return _ffi.AlignParams(pos0, pos_step, rot_phase & 0xFFFFFFFF, rot_step & 0xFFFFFFFF, 0)
+
+
+TRACK_MAX_CHANNELS = _ffi.GJ_TRACK_MAX_CHANNELS
+TRACK_MAX_EPOCHS = _ffi.GJ_TRACK_MAX_EPOCHS
+TRACK_MAX_GAIN = _ffi.GJ_TRACK_MAX_GAIN
+TRACK_STATE_DTYPE = np.dtype([("ch", CORR_CHANNEL_DTYPE), ("carr_nco", np.int64), ("start", np.uint32), ("e_prev", np.int32),
+                              ("c_prev", np.int32), ("primed", np.int32), ("reserved", np.int32, (2,))])      # gj_track_state
+TRACK_EPOCH_DTYPE = np.dtype([("early", np.int32, (2,)), ("prompt", np.int32, (2,)), ("late", np.int32, (2,)),
+                              ("carr_phase", np.uint32), ("carr_step", np.uint32), ("code_phase", np.uint64),
+                              ("code_step", np.uint64), ("e", np.int32), ("c", np.int32)])                     # gj_track_epoch
+TrackParams = _ffi.TrackParams
+
+
+def _track_params(params) -> "_ffi.TrackParams":
+    """A ``TrackParams`` as it is; ``(spacing, aid_div, pll_p, pll_i, fll, dll_p, dll_i)`` made into one."""
+    if isinstance(params, _ffi.TrackParams):
+        return params
+    v = [int(x) for x in params]
+    if len(v) != 7 or any(not -2 ** 31 <= x < 2 ** 31 for x in v):
+        raise GpsJamError(-5, "unsupported: params are (spacing, aid_div, pll_p, pll_i, fll, dll_p, dll_i) in int32")
+    return _ffi.TrackParams(*v, 0)
+
+
+def _track_states(states) -> np.ndarray:
+    """The states of ``Device.track`` as TRACK_STATE_DTYPE records: such records as they are, or rows of thirteen integers
+    in the struct's order (code_phase, code_step, carr_phase, carr_step, code_row, 0, carr_nco, start, e_prev, c_prev,
+    primed, 0, 0)."""
+    if isinstance(states, np.ndarray) and states.dtype == TRACK_STATE_DTYPE:
+        return np.ascontiguousarray(states).reshape(-1).copy()
+    rows = [tuple(int(v) for v in s) for s in states]
+    lo = (0, 0, 0, 0, -2 ** 31, -2 ** 31, -2 ** 63, 0, -2 ** 31, -2 ** 31, -2 ** 31, -2 ** 31, -2 ** 31)
+    hi = (2 ** 64, 2 ** 64, 2 ** 32, 2 ** 32, 2 ** 31, 2 ** 31, 2 ** 63, 2 ** 32, 2 ** 31, 2 ** 31, 2 ** 31, 2 ** 31, 2 ** 31)
+    rec = np.zeros(len(rows), TRACK_STATE_DTYPE)
+    for k, r in enumerate(rows):
+        if len(r) != 13 or any(not a <= v < b for v, a, b in zip(r, lo, hi)):
+            raise GpsJamError(-1, f"invalid argument: a state is thirteen integers in the order of gj_track_state, not {r}")
+        rec[k] = (r[:6], r[6], r[7], r[8], r[9], r[10], r[11:13])
+    return rec
 
 
 ACQ_MAX_PEAKS = _ffi.GJ_ACQ_MAX_PEAKS
@@ -1406,6 +1445,45 @@ class Device:
                 cap, cap.nbytes, first_sample, n_samples, block_samples, d_codes, n_rows, d_ch, rec.size, d_amp,
                 _ffi.GJ_SUB_DITHER if dither else 0, seed, d_out, d_rec))
 
+    def track(self, capture, states, codes, params, first_sample: int = 0, n_samples: Optional[int] = None,
+              block_samples: int = 2048, n_epochs: Optional[int] = None):
+        """Closed-loop tracking (gj_track_dev): every channel of ``states`` runs its DLL / FLL / PLL over ``n_epochs``
+        epochs of ``block_samples`` samples inside samples first_sample .. + n_samples of ``capture`` (default: to the
+        end), one workgroup per channel, one launch.  ``capture`` and ``codes`` as in ``corr_bank``; ``states``:
+        TRACK_STATE_DTYPE records or rows of thirteen integers in that order, what ``gpsjam.track.states`` makes of an
+        acquisition; ``params``: a ``TrackParams`` or (spacing, aid_div, pll_p, pll_i, fll, dll_p, dll_i), what
+        ``gpsjam.track.gains`` makes of loop bandwidths; ``n_epochs``: default the most that every channel's ``start``
+        leaves room for.  The states are checked HERE, on the host, before they are uploaded (GJ_ERR_INVALID), as the
+        bank's channels are.  Returns ``(records, states)``: TRACK_EPOCH_DTYPE[n_channels][n_epochs] and the states
+        behind the last epoch, with which a next call goes on."""
+        first_sample, block_samples = int(first_sample), int(block_samples)
+        params = _track_params(params)
+        rec = _track_states(states)
+        with contextlib.ExitStack() as temps:
+            cap, n_samples, d_codes, n_rows, _, _ = self._replica_inputs(temps, capture, rec["ch"], codes, first_sample,
+                                                                         n_samples, block_samples)
+            if n_epochs is None:
+                room = n_samples - (int(rec["start"].max()) if rec.size else 0)
+                n_epochs = min(max(room, 0) // block_samples, TRACK_MAX_EPOCHS) if block_samples > 0 else 0
+            n_epochs = int(n_epochs)
+            for k, s in enumerate(rec):
+                what = None
+                if s["reserved"].any():
+                    what = "reserved must be 0"
+                elif int(s["primed"]) not in (0, 1):
+                    what = f"primed {int(s['primed'])} is neither 0 nor 1"
+                elif int(s["start"]) + n_epochs * block_samples > n_samples:
+                    what = f"{n_epochs} epochs of {block_samples} samples from start {int(s['start'])} run past the range's {n_samples}"
+                if what:
+                    raise GpsJamError(-1, f"invalid argument: state {k}: {what}")
+            d_st = temps.enter_context(DevBuf(self, max(rec.nbytes, 64))).upload(rec)
+            d_out = temps.enter_context(DevBuf(self, TRACK_EPOCH_DTYPE.itemsize * max(rec.size * max(n_epochs, 0), 1)))
+            self._count("track")
+            self.track_dev(cap, cap.nbytes, first_sample, n_samples, block_samples, n_epochs, d_codes, n_rows, d_st, rec.size,
+                           params, d_out)
+            out = d_out.download(TRACK_EPOCH_DTYPE, rec.size * n_epochs).reshape(rec.size, n_epochs)
+            return out, d_st.download(TRACK_STATE_DTYPE, rec.size)
+
     def align(self, capture, params, taps, rot, n_out: Optional[int] = None):
         """Pair alignment (gj_align_dev): ``n_out`` samples (default: as many as ``capture`` holds) read from ``capture``
         along the time base and the phase of ``params`` -- an ``AlignParams`` or ``(pos0, pos_step, rot_phase, rot_step)``,
@@ -1475,6 +1553,16 @@ class Device:
         self._check(self._lib.gj_corr_bank_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples),
                                                int(block_samples), _ptr(d_codes), int(n_code_rows), _ptr(d_channels),
                                                int(n_channels), arr, len(taps), _ptr(d_out)))
+
+    def track_dev(self, d_iq, nbytes, first_sample, n_samples, block_samples, n_epochs, d_codes, n_code_rows, d_states,
+                  n_channels, params, d_out):
+        """gj_track_dev: one 56-byte record (TRACK_EPOCH_DTYPE) per channel and epoch into d_out and the 64-byte states
+        (TRACK_STATE_DTYPE) in d_states advanced in place, on the context's stream."""
+        args = [int(v) for v in (block_samples, n_epochs, n_code_rows, n_channels)]
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in args):
+            raise GpsJamError(-5, "unsupported: an argument outside int32")
+        self._check(self._lib.gj_track_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples), args[0], args[1],
+                                           _ptr(d_codes), args[2], _ptr(d_states), args[3], _track_params(params), _ptr(d_out)))
 
     def subtract_dev(self, d_iq, nbytes, first_sample, n_samples, block_samples, d_codes, n_code_rows, d_channels, n_channels,
                      d_amp, flags, seed, d_out, d_blocks=None):

@@ -173,6 +173,24 @@ class AlignParams(C.Structure):
                 ("reserved", C.c_uint64)]
 
 
+class TrackState(C.Structure):
+    """gj_track_state: one channel's loop state, in and out of gj_track_dev (include/gpsjam.h)."""
+    _fields_ = [("ch", CorrChannel), ("carr_nco", C.c_int64), ("start", C.c_uint32), ("e_prev", C.c_int32), ("c_prev", C.c_int32),
+                ("primed", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class TrackParams(C.Structure):
+    """gj_track_params: spacing, aiding and loop gains of one gj_track_dev call, passed by value (include/gpsjam.h)."""
+    _fields_ = [("spacing", C.c_int32), ("aid_div", C.c_int32), ("pll_p", C.c_int32), ("pll_i", C.c_int32), ("fll", C.c_int32),
+                ("dll_p", C.c_int32), ("dll_i", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TrackEpoch(C.Structure):
+    """gj_track_epoch: one epoch's record of gj_track_dev (include/gpsjam.h)."""
+    _fields_ = [("early", C.c_int32 * 2), ("prompt", C.c_int32 * 2), ("late", C.c_int32 * 2), ("carr_phase", C.c_uint32),
+                ("carr_step", C.c_uint32), ("code_phase", C.c_uint64), ("code_step", C.c_uint64), ("e", C.c_int32), ("c", C.c_int32)]
+
+
 class AlignBlock(C.Structure):
     """gj_align_block: one GJ_ALIGN_BLOCK-sample record of the pair alignment (include/gpsjam.h)."""
     _fields_ = [("power_out", C.c_uint64), ("n_clipped", C.c_int32), ("n_edge", C.c_int32)]
@@ -209,6 +227,13 @@ GJ_ALIGN_BLOCK = 4096
 GJ_ALIGN_MAX_DRIFT = 1 << 24
 GJ_ALIGN_MAX_SAMPLES = 1 << 28
 GJ_CORR_COS_TABLE = (32, 30, 23, 12, 0, -12, -23, -30, -32, -30, -23, -12, 0, 12, 23, 30)
+GJ_TRACK_MAX_CHANNELS = 4096
+GJ_TRACK_MAX_EPOCHS = 1 << 17
+GJ_TRACK_MAX_GAIN = 1 << 30
+GJ_TRACK_PLL_SHIFT = 32
+GJ_TRACK_DLL_SHIFT = 24
+GJ_TRACK_ATAN_TABLE = (536870912, 316933406, 167458907, 85004756, 42667331, 21354465, 10679838, 5340245,
+                       2670163, 1335087, 667544, 333772, 166886, 83443, 41722, 20861)
 
 _vp, _sz, _i, _f, _d = C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_double
 _pf, _psz = C.POINTER(C.c_float), C.POINTER(C.c_size_t)
@@ -332,6 +357,7 @@ SIGNATURES = {
     "gj_corr_bank_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _i, _vp, _i, C.POINTER(C.c_int32), _i, _vp]),
     "gj_subtract_blocks": (_sz, [_sz]),
     "gj_subtract_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _i, _vp, _i, _vp, _i, C.c_uint32, _vp, _vp]),
+    "gj_track_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _i, _vp, _i, TrackParams, _vp]),
     "gj_align_blocks": (_sz, [_sz]),
     "gj_align_dev": (_i, [_vp, _vp, _sz, AlignParams, _vp, _vp, _sz, _vp, _vp]),
     "gj_pack_result_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -966,6 +966,95 @@ int gj_subtract_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t firs
                     int flags, uint32_t seed, uint8_t* d_out /* [2*n_samples] */,
                     gj_subtract_block* d_blocks /* [gj_subtract_blocks(n_samples)] or NULL */);
 
+/* ------------------------------------------------- closed-loop tracking: DLL / FLL / PLL per channel ---- */
+/* The reference's receiver loop (sdrtracking -> correlator -> pll / dll, sdrtrk.c) for up to GJ_TRACK_MAX_CHANNELS
+ * channels in one launch: every channel correlates one EPOCH of B = block_samples samples at early, prompt and late,
+ * makes a carrier and a code discriminator of the three sums, filters them and steers its own carrier and code NCO
+ * for the next epoch.  The loop is sequential per channel, the channels are independent: one workgroup each.  The
+ * terms are the correlator bank's (gj_corr_channel, GJ_CORR_COS_TABLE, the chip rule, I, Q = byte - 128 WHATEVER
+ * gj_set_unpack says); every step from the byte to the loop state is integer arithmetic.
+ *
+ * For channel ch with state S = d_states[ch] and epoch m = 0 .. n_epochs-1:
+ *
+ *   sums      (E, P, L) = the three records gj_corr_bank_dev defines for a call of n_samples = B that starts at sample
+ *             first_sample + S.start + m*B, with the channel S.ch (as it stands NOW) and the taps (+d, 0, -d),
+ *             d = params.spacing: local t = 0 .. B-1, the bank's carrier table, chip rule and unpacking
+ *   cordic    (I, Q) -> (angle, length), in int64, A = GJ_TRACK_ATAN_TABLE:
+ *             x = I * 2^8, y = Q * 2^8, z = 0;   if x < 0: (x, y) = (-x, -y)          the Costas fold
+ *             for k = 0 .. 15:  if y >= 0: (x, y, z) <- (x + (y >> k), y - (x >> k), z + A[k])
+ *                               else:      (x, y, z) <- (x - (y >> k), y + (x >> k), z - A[k])
+ *             >> is arithmetic (floor), both updates use the OLD x and y.  angle = z in 2^-32 cycles, |z| <= sum A =
+ *             1 191 629 338; length = x, about 421.6 |v|, below 2^34 for the bank's record bound.  I = Q = 0 gives
+ *             angle 0 and length 0, a rule of its own (the steps would turn a zero vector by the whole table)
+ *   discr.    e = angle(P);  mE = length(E), mL = length(L);
+ *             c = floor((mE - mL) * 2^16 / (mE + mL)), 0 where mE + mL = 0     (|E| - |L|) / (|E| + |L|) in Q16,
+ *                                                                              sdrtrk.c:99-100
+ *             if S.primed == 0:  e_prev = e, c_prev = c, primed = 1
+ *             f = e - e_prev;   f > 2^30: f = 2^31 - f;   f < -2^30: f = -2^31 - f
+ *   filters   dn = floor((pll_p*(e - e_prev) + pll_i*e + fll*f) / 2^GJ_TRACK_PLL_SHIFT)       int64, mathematical floor;
+ *             dc = floor((dll_p*(c - c_prev) + dll_i*c) / 2^GJ_TRACK_DLL_SHIFT)               |gain| <= 2^30: < 2^63
+ *   record    d_out[ch][m] = E, P, L, the four NCO fields of S.ch as the sums were made with them, e, c
+ *   advance   code_phase <- (code_phase + B*code_step) mod 1023 * 2^32;  carr_phase <- (carr_phase + B*carr_step) mod 2^32
+ *             (with the OLD steps)
+ *   steer     nco' = carr_nco - dn   (int64, wraps as two's complement);
+ *             aid  = aid_div ? floor(nco' / aid_div) - floor(carr_nco / aid_div) : 0
+ *             carr_step <- (carr_step - dn) mod 2^32;   code_step <- clamp(code_step + dc + aid, 0, GJ_CORR_MAX_CODE_STEP - 1)
+ *             carr_nco <- nco';  e_prev <- e;  c_prev <- c
+ *
+ * After the last epoch S is written back with start advanced by n_epochs*B.  Signs: a replica that is late gives
+ * c > 0 and (with positive dll gains) speeds the code up; a prompt whose angle grows lowers carr_step.
+ *
+ * Consequences.  Every value is an exact integer: the result does not depend on tiling or order, two calls give
+ * identical bits, and it is a function of the bytes alone.  All gains 0 and aid_div 0 give, for start 0, the bits of
+ * gj_corr_bank_dev with that constant channel, block_samples = B and taps (+d, 0, -d).  N epochs followed by M epochs
+ * from the written-back states give the bits of N + M epochs.
+ *
+ * Limits (GJ_ERR_UNSUPPORTED): block_samples a multiple of 16 in 16 .. GJ_CORR_MAX_BLOCK; n_epochs 1 .. GJ_TRACK_MAX_EPOCHS
+ * (the cap on how long one launch runs); n_channels 1 .. GJ_TRACK_MAX_CHANNELS; n_samples 1 .. GJ_CORR_MAX_SAMPLES;
+ * spacing 1 .. GJ_CORR_MAX_TAP_OFFSET; aid_div >= 0; every gain within +-GJ_TRACK_MAX_GAIN.
+ * GJ_ERR_INVALID: a null ctx, d_iq, d_codes, d_states or d_out; an odd d_iq or d_codes; a d_states or d_out that is
+ * not 8-byte aligned; n_code_rows < 1; params.reserved != 0; n_epochs*B > n_samples; a range that runs past the
+ * capture.  A refused call enqueues nothing.
+ * The states are in DEVICE memory, as the bank's channels: Device.track (gpsjam/__init__.py) checks them on the host
+ * before it uploads them and raises GJ_ERR_INVALID, and each workgroup checks ITS channel before it reads a chip.  A
+ * channel is bad where its ch is (the bank's rule: reserved != 0, a code_row outside 0 .. n_code_rows-1, code_phase >=
+ * 1023 * 2^32, code_step >= GJ_CORR_MAX_CODE_STEP), where a reserved word is not 0, where primed is neither 0 nor 1, or
+ * where start + n_epochs*B > n_samples.  A bad channel writes NOTHING: its records and its state stay as they were.
+ * The other channels run.
+ * One launch on the context's stream; no workspace, no memset, no atomics: 0 bytes to gj_reserve, the call never
+ * allocates.  Each record and each state is written by exactly one workgroup. */
+typedef struct gj_track_state {   /* 64 bytes, DEVICE memory, in/out */
+    gj_corr_channel ch;     /* the channel AT sample first_sample + start; the bank's bounds */
+    int64_t  carr_nco;      /* what the loop has added to carr_step so far (for the aiding); 0 to begin */
+    uint32_t start;         /* this channel's epoch 0 begins `start` samples after first_sample */
+    int32_t  e_prev, c_prev;/* last epoch's discriminators; 0 to begin */
+    int32_t  primed;        /* 0 to begin, 1 once e_prev / c_prev hold an epoch */
+    int32_t  reserved[2];   /* 0 */
+} gj_track_state;
+typedef struct gj_track_params {  /* 32 bytes, by value */
+    int32_t spacing;        /* d: early = tap +d, late = tap -d, whole samples, 1 .. GJ_CORR_MAX_TAP_OFFSET */
+    int32_t aid_div;        /* carrier aiding: code_step follows carr_nco / aid_div (1540 for L1 C/A); 0 = none; >= 0 */
+    int32_t pll_p, pll_i, fll, dll_p, dll_i;   /* |g| <= GJ_TRACK_MAX_GAIN */
+    int32_t reserved;       /* 0 */
+} gj_track_params;
+typedef struct gj_track_epoch {   /* 56 bytes, all exact integers */
+    int32_t  early[2], prompt[2], late[2];   /* I, Q */
+    uint32_t carr_phase, carr_step;          /* the state the sums were made with, at the epoch's first sample */
+    uint64_t code_phase, code_step;
+    int32_t  e, c;                           /* the two discriminators of this epoch */
+} gj_track_epoch;
+#define GJ_TRACK_MAX_CHANNELS 4096
+#define GJ_TRACK_MAX_EPOCHS (1 << 17)
+#define GJ_TRACK_MAX_GAIN (1 << 30)
+#define GJ_TRACK_PLL_SHIFT 32
+#define GJ_TRACK_DLL_SHIFT 24
+#define GJ_TRACK_ATAN_TABLE {536870912, 316933406, 167458907, 85004756, 42667331, 21354465, 10679838, 5340245, \
+                             2670163, 1335087, 667544, 333772, 166886, 83443, 41722, 20861}  /* round(atan(2^-k) / 2pi * 2^32) */
+int gj_track_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples, int block_samples,
+                 int n_epochs, const int16_t* d_codes /* [n_code_rows][1023], +-1 */, int n_code_rows,
+                 gj_track_state* d_states /* [n_channels], in/out */, int n_channels, gj_track_params params,
+                 gj_track_epoch* d_out /* [n_channels][n_epochs] */);
+
 /* ------------------------------------------------- pair alignment --------------------- */
 /* One uint8 I/Q capture written from another along a linear time base and a linear phase: antenna b brought onto
  * antenna a's clock, for receivers that each run on a crystal of their own (the crystal sets the sample clock AND the
