@@ -196,8 +196,14 @@ int gj_debug_set_wait_hook(gj_ctx* ctx, void (*hook)(void*, int), void* arg) {
 
 int gj_debug_inject(gj_ctx* ctx, int what, int count) {
     if (!ctx) return GJ_ERR_INVALID;
-    if (what != GJ_INJECT_OWNER_ALIVE || count < 0) return fail(ctx, GJ_ERR_INVALID, "unknown injection %d (count %d)", what, count);
+    const bool known = (what == GJ_INJECT_OWNER_ALIVE && count >= 0) || (what == GJ_INJECT_FILL_WORKSPACE && count >= 0 && count <= 255);
+    if (!known) return fail(ctx, GJ_ERR_INVALID, "unknown injection %d (count %d)", what, count);
     Guard g(ctx);
+    if (what == GJ_INJECT_FILL_WORKSPACE) {
+        // the whole current arena, in stream order: behind the kernels already queued on it, in front of the next call's
+        if (ctx->ws) GJ_HIP(ctx, hipMemsetAsync(ctx->ws, count, ctx->ws_bytes, ctx->stream));
+        return GJ_OK;
+    }
     ctx->inject_owner_alive = count;
     return GJ_OK;
 }

@@ -946,7 +946,8 @@ class Device:
         self._check(self._lib.gj_probe_busy_dev(self._ctx, float(milliseconds)))
 
     def debug_inject(self, what: int, count: int = 1):
-        """Fault injection for tests (gj_debug_inject; GJ_INJECT_OWNER_ALIVE = 1)."""
+        """Fault injection for tests (gj_debug_inject; GJ_INJECT_OWNER_ALIVE = 1; GJ_INJECT_FILL_WORKSPACE = 2 with the
+        fill byte as ``count``)."""
         self._check(self._lib.gj_debug_inject(self._ctx, int(what), int(count)))
 
     def debug_counters(self):

@@ -121,6 +121,13 @@ int gj_debug_counters(gj_ctx* ctx, int* lanes, int* lanes_busy, int* lanes_recla
  * sampled probe gave inside the thread-exit window.  A test uses it to show that a lane missed once is
  * still taken back at the next check-out or counters call. */
 #define GJ_INJECT_OWNER_ALIVE 1
+/* GJ_INJECT_FILL_WORKSPACE: `count` is a byte, 0..255 (anything else is GJ_ERR_INVALID).  Enqueues ONE memset of that
+ * byte over the whole of the context's current workspace arena, on the context's stream: behind everything already
+ * queued there, in front of the next call.  Without an arena it does nothing.  It touches neither the tables, nor the
+ * arrival counters, nor an arena that a growth has retired.  A test uses it to show that no kernel reads a workspace
+ * word that its own call has not written: 0xFF makes such a float a NaN and such a counter or flag all-ones, 0x7F a
+ * large finite float and a large positive int. */
+#define GJ_INJECT_FILL_WORKSPACE 2
 int gj_debug_inject(gj_ctx* ctx, int what, int count);
 
 /* Stream-overlap probe.  Keeps the context's stream busy for `milliseconds` (0..100; more is refused) with ONE wave

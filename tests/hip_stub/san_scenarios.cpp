@@ -277,6 +277,8 @@ static int scenario_workspace() {
                     }
                 }
                 if (rc != GJ_OK) { fprintf(stderr, "thread %d round %d: rc %d (%s)\n", t, r, rc, gj_last_error(ctx)); bad.fetch_add(1); }
+                // between two growing calls: one memset over the whole arena of the moment, under the lock like a launch
+                if (r % 10 == 4 && gj_debug_inject(ctx, GJ_INJECT_FILL_WORKSPACE, 0x7F) != GJ_OK) bad.fetch_add(1);
             }
             if (gj_free(ctx, d_pow) || gj_free(ctx, d_psd) || gj_free(ctx, d_amp) || gj_free(ctx, d_on) || gj_free(ctx, d_st)) bad.fetch_add(1);
         });
