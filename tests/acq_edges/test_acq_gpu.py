@@ -17,9 +17,6 @@ GATE (1 + r) (both terms off by GATE max: dr / r <= GATE + GATE r); cn0 = 10 log
 "step form" = acq_inv_kernel + acq_check_kernel (a power array is asked for), "single launch" = acq_inv_all_kernel +
 acq_summary_kernel (none is), "series" = the single launch with the epoch on grid.y.
 """
-import ctypes as C
-import math
-
 import numpy as np
 import pytest
 
@@ -29,9 +26,8 @@ from gpsjam import gnss
 
 pytestmark = pytest.mark.gpu
 
-REC = C.sizeof(gnss._AcqStruct)
-RECORD = np.dtype([(n, np.float64 if t is C.c_double else np.int32) for n, t in gnss._AcqStruct._fields_])
-assert RECORD.itemsize == REC
+REC, RECORD = ai.REC, ai.RECORD
+records, check_record, check_values, check_power = ai.records, ai.check_record, ai.check_values, ai.check_power
 
 
 def searcher(dev, case):
@@ -64,33 +60,6 @@ def series(dev, srch, cap, nbytes, first, stride, n_epochs):
         dev.synchronize()
         raw = d_out.download(np.uint8, REC * n_epochs * len(srch.prns)).tobytes()
     return [raw[e * REC * len(srch.prns):(e + 1) * REC * len(srch.prns)] for e in range(n_epochs)]
-
-
-def records(raw):
-    return np.frombuffer(raw, RECORD)
-
-
-def check_record(got, want, case, what):
-    """One record against the deciding step of the restatement (a clear case)."""
-    gate = case.gate
-    assert (int(got["code_index"]), int(got["freq_index"]), int(got["steps"]), bool(got["acquired"])) == \
-           (want["codei"], want["freqi"], want["steps"], want["acquired"]), (what, got, want["peakr"])
-    check_values(got, want, case, what)
-    r = want["peakr"]
-    assert abs(got["peak_ratio"] - r) <= gate * (1.0 + r) * r, (what, got["peak_ratio"], r)
-    assert abs(got["cn0"] - want["cn0"]) <= 10.0 / math.log(10.0) * gate * (1.0 + want["maxP"] / want["meanP"]), (what, got["cn0"], want["cn0"])
-
-
-def check_values(got, want, case, what):
-    tol = case.gate * want["maxP"]
-    for field, key in (("max_power", "maxP"), ("second_power", "maxP2"), ("mean_power", "meanP")):
-        assert abs(got[field] - want[key]) <= tol, (what, field, got[field], want[key], tol)
-
-
-def check_power(P, want, case, what):
-    err = float(np.max(np.abs(P - want["P"])) / want["P"].max())
-    assert err <= case.gate, (what, err, case.gate)
-    return err
 
 
 def check_clear_case(dev, case, cap, nbytes=None, skip=()):

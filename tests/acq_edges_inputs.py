@@ -12,7 +12,9 @@ and the peak ratio stays 1e-2 away from the threshold).  tests/test_acq_edges_ho
 prints the smallest margins.  Two exceptions: code index 0 of family (a), whose ratio is 1 by construction, and the PRNs
 of EXISTING_NOT_CLEAR in family (g), whose captures are tests/test_acq_gpu.py's and not this module's to choose.
 """
+import ctypes as C
 import functools
+import math
 
 import numpy as np
 
@@ -280,3 +282,57 @@ BIG = 2 ** 32 + 2 ** 20                           # one allocation, never filled
 FAR_SAMPLE = 2 ** 31                              # the capture is uploaded at byte 2^32 ...
 FAR_FIRST = FAR_SAMPLE + 1                        # ... and searched from its sample 1: byte 2^32 + 2
 FAR_STRIDE = 1500
+
+
+REC = C.sizeof(gnss._AcqStruct)
+
+
+RECORD = np.dtype([(n, np.float64 if t is C.c_double else np.int32) for n, t in gnss._AcqStruct._fields_])
+
+
+assert RECORD.itemsize == REC
+
+
+def records(raw):
+    return np.frombuffer(raw, RECORD)
+
+
+def check_record(got, want, case, what):
+    """One record against the deciding step of the restatement (a clear case)."""
+    gate = case.gate
+    assert (int(got["code_index"]), int(got["freq_index"]), int(got["steps"]), bool(got["acquired"])) == \
+           (want["codei"], want["freqi"], want["steps"], want["acquired"]), (what, got, want["peakr"])
+    check_values(got, want, case, what)
+    r = want["peakr"]
+    assert abs(got["peak_ratio"] - r) <= gate * (1.0 + r) * r, (what, got["peak_ratio"], r)
+    assert abs(got["cn0"] - want["cn0"]) <= 10.0 / math.log(10.0) * gate * (1.0 + want["maxP"] / want["meanP"]), (what, got["cn0"], want["cn0"])
+
+
+def check_values(got, want, case, what):
+    tol = case.gate * want["maxP"]
+    for field, key in (("max_power", "maxP"), ("second_power", "maxP2"), ("mean_power", "meanP")):
+        assert abs(got[field] - want[key]) <= tol, (what, field, got[field], want[key], tol)
+
+
+def check_power(P, want, case, what):
+    err = float(np.max(np.abs(P - want["P"])) / want["P"].max())
+    assert err <= case.gate, (what, err, case.gate)
+    return err
+
+
+def series_like(n, sats, fs=2.048e6, noise_sigma=12.0, seed=4, t0=0, burst=None):
+    """tests/acq_series' generator, writable: uint8 I/Q of samples t0 .. t0+n: C/A signals (prn, doppler_hz,
+    code_delay_samples, amplitude) + Gaussian noise, + 128.  burst = (first, end, sigma): extra noise on those samples."""
+    rng = np.random.default_rng(seed)
+    k = np.arange(t0, t0 + n)
+    z = rng.normal(0, noise_sigma, n) + 1j * rng.normal(0, noise_sigma, n)
+    if burst is not None:
+        lo, hi, sig = burst
+        m = (k >= lo) & (k < hi)
+        z[m] += rng.normal(0, sig, int(m.sum())) + 1j * rng.normal(0, sig, int(m.sum()))
+    for prn, dop, delay, amp in sats:
+        chip = ((k - delay) * 1.023e6 / fs) % 1023
+        z += amp * gnss.ca_code(prn)[chip.astype(np.int64)] * np.exp(-2j * np.pi * dop * (k / fs))
+    iq = np.empty(2 * n, np.float64)
+    iq[0::2], iq[1::2] = z.real, z.imag
+    return (np.clip(np.round(iq), -128, 127) + 128).astype(np.uint8)

@@ -6,7 +6,6 @@ single search it is checked against.  The package keeps the two modules apart.
 
 The series must equal a loop of single searches BYTE FOR BYTE (same arithmetic per epoch, same winner records); against
 the oracle the tolerances of test_acq_search_matches_oracle apply (parity behind the first FFT unpinned, as there)."""
-import ctypes as C
 import io
 import os
 import sys
@@ -15,7 +14,9 @@ from contextlib import redirect_stdout
 import numpy as np
 import pytest
 
+import acq_edges_inputs as ai
 from gpsjam import gnss
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
 from oracle import gpsjam_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -26,27 +27,8 @@ for p in (os.path.join(PKG, "skrypty"), os.path.join(PKG, "GpsJammerApp", "app")
     if p not in sys.path:
         sys.path.insert(0, p)
 
-REC = C.sizeof(gnss._AcqStruct)
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5    # include/gpsjam.h gj_status
+REC, gps_like = ai.REC, ai.series_like
 SATS = [(3, 1400.0, 517, 9.0), (17, -3000.0, 1201, 1.5), (25, 5230.0, 88, 3.0)]
-
-
-def gps_like(n, sats, fs=2.048e6, noise_sigma=12.0, seed=4, t0=0, burst=None):
-    """uint8 I/Q of samples t0 .. t0+n: C/A signals (prn, doppler_hz, code_delay_samples, amplitude) + Gaussian noise,
-    + 128.  burst = (first, end, sigma): extra noise on those samples."""
-    rng = np.random.default_rng(seed)
-    k = np.arange(t0, t0 + n)
-    z = rng.normal(0, noise_sigma, n) + 1j * rng.normal(0, noise_sigma, n)
-    if burst is not None:
-        lo, hi, sig = burst
-        m = (k >= lo) & (k < hi)
-        z[m] += rng.normal(0, sig, int(m.sum())) + 1j * rng.normal(0, sig, int(m.sum()))
-    for prn, dop, delay, amp in sats:
-        chip = ((k - delay) * 1.023e6 / fs) % 1023
-        z += amp * gnss.ca_code(prn)[chip.astype(np.int64)] * np.exp(-2j * np.pi * dop * (k / fs))
-    iq = np.empty(2 * n, np.float64)
-    iq[0::2], iq[1::2] = z.real, z.imag
-    return (np.clip(np.round(iq), -128, 127) + 128).astype(np.uint8)
 
 
 def series_raw(dev, srch, cap, first, stride, n_epochs, epl):

@@ -17,12 +17,11 @@ import pytest
 import align_restatement as ar
 import gpsjam
 from gpsjam import align, coherence
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, PAD, SENTINEL, Guarded, freed, refused
+from gpu_lib import run_align as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes on either side of the output
 
 
 @pytest.fixture(scope="module")
@@ -44,27 +43,6 @@ def d_tables(dev):
     for t, r in held.values():
         t.free()
         r.free()
-
-
-def run(dev, d_iq, nbytes, case, d_taps, d_rot, n_out, records=True, out_offset=0):
-    """(uint8[2 n_out], DTYPE[blocks] or None) through gj_align_dev into sentinel-filled buffers; ``out_offset``: bytes by
-    which d_out is moved off its 256-byte aligned place."""
-    size, rsize = 2 * n_out, 16 * ar.blocks(n_out)
-    out, d_rec = dev.alloc(PAD + out_offset + size + PAD), dev.alloc(PAD + rsize + PAD)
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        d_rec.upload(np.full(d_rec.nbytes, SENTINEL, np.uint8))
-        dev.align_dev(d_iq, nbytes, case, d_taps, d_rot, n_out, out.ptr + PAD + out_offset, d_rec.ptr + PAD if records else None)
-        got, got_rec = out.download(np.uint8), d_rec.download(np.uint8)
-    finally:
-        out.free()
-        d_rec.free()
-    lo = PAD + out_offset
-    assert np.all(got[:lo] == SENTINEL) and np.all(got[lo + size:] == SENTINEL), "bytes were written outside the call's output"
-    assert np.all(got_rec[:PAD] == SENTINEL) and np.all(got_rec[PAD + rsize:] == SENTINEL), "bytes were written outside the call's records"
-    if not records:
-        assert np.all(got_rec == SENTINEL), "no records were asked for"
-    return got[lo:lo + size], got_rec[PAD:PAD + rsize].view(gpsjam.ALIGN_DTYPE) if records else None
 
 
 def compare(dev, cap, raw, case, kind, d_tables, n_out, first=0, **how):
@@ -140,10 +118,8 @@ def test_refusals_write_nothing(dev, caps, d_tables):
     cap, raw = caps["random"], ar.parity_capture()
     d_taps, d_rot = d_tables["mid"]
     n = 2 * 4096 + 5
-    out, d_rec = dev.alloc(2 * n + PAD), dev.alloc(16 * 3 + PAD)
+    out, d_rec = Guarded(dev, 2 * n), Guarded(dev, 16 * 3)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        d_rec.upload(np.full(d_rec.nbytes, SENTINEL, np.uint8))
         I, U = GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
         P = gpsjam.AlignParams
         ok = dict(d_iq=cap, nbytes=cap.nbytes, params=P(3 << 32, ar.ONE + 99, 1, 2, 0), d_taps=d_taps, d_rot=d_rot, n=n, d_out=out, d_blocks=d_rec)
@@ -162,23 +138,21 @@ def test_refusals_write_nothing(dev, caps, d_tables):
                  (dict(params=P(1 << 60, ar.ONE, 0, 0, 0)), U), (dict(params=P(-(1 << 60), ar.ONE, 0, 0, 0)), U),
                  (dict(params=P(-(1 << 63), ar.ONE, 0, 0, 0)), U), (dict(params=P((1 << 63) - 1, ar.ONE, 0, 0, 0)), U),
                  (dict(n=0), U), (dict(n=2 ** 28 + 1), U), (dict(n=2 ** 63), U)]
-        for change, status in cases:
-            a = dict(ok, **change)
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.align_dev(a["d_iq"], a["nbytes"], a["params"], a["d_taps"], a["d_rot"], a["n"], a["d_out"], a["d_blocks"])
-            assert e.value.status == status, (change, e.value)
-            dev.synchronize()
-            assert np.all(out.download(np.uint8) == SENTINEL) and np.all(d_rec.download(np.uint8) == SENTINEL), change
+        def launch(a):
+            dev.align_dev(a["d_iq"], a["nbytes"], a["params"], a["d_taps"], a["d_rot"], a["n"], a["d_out"], a["d_blocks"])
+        for change, status in cases:                         # nothing written behind each one of them
+            refused(dev, launch, [((dict(ok, **change),), status)], out, d_rec)
         assert cap.download().tobytes() == raw.tobytes(), "the capture is as it was"
         # accepted: the limits themselves, and an output that ends where the source begins
         dev.align_dev(cap, cap.nbytes, P((1 << 60) - 1, ar.ONE + ar.MAX_DRIFT, 0, 0, 0), d_taps, d_rot, 1, out, None)
         dev.align_dev(cap, cap.nbytes, P(-(1 << 60) + 1, ar.ONE - ar.MAX_DRIFT, 0, 0, 0), d_taps, d_rot, 16, out.ptr + 64, d_rec)
         dev.align_dev(out.ptr + 96, 64, P(0, ar.ONE, 0, 0, 0), d_taps, d_rot, 16, out.ptr + 64, None)
         dev.synchronize()
-        assert np.all(out.download(np.uint8, out.nbytes - 96, 96) == SENTINEL) and np.all(d_rec.download(np.uint8, PAD, 16) == SENTINEL)
+        assert np.all(out.download(np.uint8, out.nbytes - 96 + PAD, 96) == SENTINEL) and np.all(d_rec.download(np.uint8, PAD, 16) == SENTINEL)
+        out.check_pads("output")
+        d_rec.check_pads("records")
     finally:
-        out.free()
-        d_rec.free()
+        freed(out, d_rec)
     # the next valid call gives the parity bytes, and a library refusal through the wrapper raises and leaves the capture alone
     compare(dev, cap, raw, ar.CASES["fastest step"], "mid", d_tables, n)
     with pytest.raises(gpsjam.GpsJamError) as e:

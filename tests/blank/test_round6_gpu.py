@@ -17,13 +17,12 @@ import blank_restatement as br
 import excise_restatement as er
 import gpsjam
 from gpsjam import gnss, mitigate
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, freed, refused
+from gpu_lib import run_blank as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
 REC = gpsjam.BLANK_DTYPE.itemsize
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind d_out[2 n_samples] and behind d_blocks[blocks]
 
 
 @pytest.fixture(scope="module")
@@ -31,34 +30,6 @@ def cap(dev):
     c = dev.capture(br.parity_capture())
     yield c
     c.free()
-
-
-def run(dev, d_iq, nbytes, first, n_samples, window, guard, threshold, want_blocks=True):
-    """(bytes[2 n_samples], records[blocks]) through gj_blank_dev into sentinel-filled buffers."""
-    nb = gpsjam.blank_blocks(n_samples)
-    out, rec = dev.alloc(2 * n_samples + PAD), dev.alloc(nb * REC + PAD)
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
-        dev.blank_dev(d_iq, nbytes, first, n_samples, window, guard, threshold, out, rec if want_blocks else None)
-        got, raw = out.download(np.uint8), rec.download(np.uint8)
-    finally:
-        out.free()
-        rec.free()
-    assert np.all(got[2 * n_samples:] == SENTINEL), "bytes were written behind d_out[2 n_samples]"
-    assert np.all(raw[(nb * REC if want_blocks else 0):] == SENTINEL), "records were written behind d_blocks[blocks]"
-    return got[:2 * n_samples], raw[:nb * REC].view(gpsjam.BLANK_DTYPE)
-
-
-def compare(got, rec, want, what):
-    """GPU bytes and records against a br.Blanked: all of them equal."""
-    assert got.size == want.out.size and rec.size == want.records.size, what
-    differ = int(np.sum(got != want.out))
-    print(f"{what}: {int(want.blanked.sum())} of {want.blanked.size} samples blanked on {int(want.records['n_rising'].sum())} rising edges, "
-          f"{differ} bytes differ")
-    for key in br.RECORD.names:
-        np.testing.assert_array_equal(rec[key], want.records[key], err_msg=f"{what} {key}")
-    assert differ == 0, (what, differ, np.flatnonzero(got != want.out)[:8])
 
 
 # ------------------------------------------------------------------------------------------------ 1. parity
@@ -70,7 +41,7 @@ def test_parity_with_the_restatement(dev, cap, window, guard):
             dev.set_unpack(offset, scale)
             want = br.parity_reference(window, guard, offset)
             got, rec = run(dev, cap, cap.nbytes, br.PARITY_FIRST, br.PARITY_SAMPLES, window, guard, br.PARITY_THRESHOLD)
-            compare(got, rec, want, (window, guard, offset))
+            br.compare(got, rec, want, (window, guard, offset))
     finally:
         dev.set_unpack()
     assert dev.get_unpack() == (127.5, 1.0 / 127.5)
@@ -96,8 +67,8 @@ def test_the_comparison_is_strict(dev):
         below = float(np.nextafter(np.float32(br.STRICT_THRESHOLD), np.float32(0)))
         lo_b, lo_r = run(dev, c, c.nbytes, 0, n, W, 0, below)
     want_at, want_lo = br.blank(raw, br.STRICT_THRESHOLD, W, 0), br.blank(raw, below, W, 0)
-    compare(at_b, at_r, want_at, "threshold = e / 4")
-    compare(lo_b, lo_r, want_lo, "one ulp below")
+    br.compare(at_b, at_r, want_at, "threshold = e / 4")
+    br.compare(lo_b, lo_r, want_lo, "one ulp below")
     assert not at_r["n_blanked"].any() and at_b.tobytes() == raw.tobytes(), "S = T everywhere in the interior: nothing is blanked"
     interior = slice(2 * W, 2 * (n - W))
     assert set(np.unique(lo_b[interior]).tolist()) == {127, 128} and int(lo_r["n_blanked"].sum()) == n - (W - 1)
@@ -111,7 +82,7 @@ def test_ranges_smaller_than_the_halo(dev, cap, n):
         for window, guard in ((1024, 1024), (16, 8)):
             want = br.blank(raw, br.PARITY_THRESHOLD, window, guard, first, n)
             got, rec = run(dev, cap, cap.nbytes, first, n, window, guard, br.PARITY_THRESHOLD)
-            compare(got, rec, want, (n, first, window, guard))
+            br.compare(got, rec, want, (n, first, window, guard))
 
 
 # ------------------------------------------------------------------------------------------------ 4. sub-range, repetition
@@ -159,17 +130,12 @@ def test_a_range_past_sample_2_31(dev, big):
         odd = br.blank(np.concatenate((np.zeros(2, np.uint8), raw)), br.PARITY_THRESHOLD, window, guard, 1, FAR_SAMPLES)
         assert odd.out.tobytes() != want.out.tobytes(), "the dither tells an odd first_sample from an even one"
         got, rec = run(dev, big, BIG, S0, FAR_SAMPLES, window, guard, br.PARITY_THRESHOLD)
-        compare(got, rec, odd, ("past 2^31", window, guard))
+        br.compare(got, rec, odd, ("past 2^31", window, guard))
     # one sample past the buffer's end: refused, nothing written
-    out = dev.alloc(2 * FAR_SAMPLES + PAD)
+    out = Guarded(dev, 2 * FAR_SAMPLES)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        for first in (BIG // 2 - FAR_SAMPLES + 1, BIG // 2):
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.blank_dev(big, BIG, first, FAR_SAMPLES, 16, 8, br.PARITY_THRESHOLD, out, None)
-            assert e.value.status == GJ_ERR_INVALID, (first, e.value)
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL)
+        refused(dev, dev.blank_dev, [((big, BIG, first, FAR_SAMPLES, 16, 8, br.PARITY_THRESHOLD, out, None), GJ_ERR_INVALID)
+                                     for first in (BIG // 2 - FAR_SAMPLES + 1, BIG // 2)], out)
     finally:
         out.free()
 
@@ -177,10 +143,8 @@ def test_a_range_past_sample_2_31(dev, big):
 # ------------------------------------------------------------------------------------------------ 6. refusals
 def test_refusals_enqueue_nothing(dev, cap):
     n, thr = 3 * 4096, br.PARITY_THRESHOLD
-    out, rec = dev.alloc(cap.nbytes + PAD), dev.alloc(8 * REC + PAD)
+    out, rec = Guarded(dev, cap.nbytes), Guarded(dev, 8 * REC)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
         cases = [  # d_iq, nbytes, first, n_samples, window, guard, threshold, d_out, d_blocks, status
             (cap, cap.nbytes, 0, n, 0, 8, thr, out, rec, GJ_ERR_UNSUPPORTED),
             (cap, cap.nbytes, 0, n, -16, 8, thr, out, rec, GJ_ERR_UNSUPPORTED),
@@ -204,38 +168,31 @@ def test_refusals_enqueue_nothing(dev, cap):
             (out, cap.nbytes, 0, n, 16, 8, thr, out.ptr + cap.nbytes - 1, rec, GJ_ERR_INVALID),
             (out.ptr + 512, 1024, 0, 256, 16, 8, thr, out.ptr + 1, rec, GJ_ERR_INVALID),
         ]
-        for d_iq, nbytes, first, ns, window, guard, t, d_out, d_rec, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.blank_dev(d_iq, nbytes, first, ns, window, guard, t, d_out, d_rec)
-            assert e.value.status == status, (nbytes, first, ns, window, guard, t, e.value)
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL)
+        refused(dev, dev.blank_dev, [(c[:-1], c[-1]) for c in cases], out, rec)
         # accepted: the whole capture; the output right behind the input's last byte; the limits; one sample
         dev.blank_dev(cap, cap.nbytes, 0, cap.nsamples, 1024, 1024, 0.0, out, rec)
         assert 4 * 4096 <= cap.nbytes
         dev.blank_dev(out, 2 * 4096, 0, 4096, 1, 0, thr, out.ptr + 2 * 4096, None)
         dev.blank_dev(cap, cap.nbytes, cap.nsamples - 1, 1, 16, 8, thr, out, rec)
         dev.synchronize()
-        assert np.all(out.download(np.uint8, PAD, cap.nbytes) == SENTINEL)
+        out.check_pads("output")
+        rec.check_pads("records")
     finally:
-        out.free()
-        rec.free()
+        freed(out, rec)
 
 
 def test_an_output_that_is_not_16_byte_aligned(dev, cap):
     """The kernel stores 16 bytes at a time into an aligned d_out and byte by byte into any other."""
     n = br.PARITY_SAMPLES
     want = br.parity_reference(16, 8)
-    out = dev.alloc(2 * n + 2 * PAD)
-    try:
-        for shift in (1, 2, 8):
-            out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-            dev.blank_dev(cap, cap.nbytes, br.PARITY_FIRST, n, 16, 8, br.PARITY_THRESHOLD, out.ptr + shift, None)
-            got = out.download(np.uint8)
-            assert got[shift:shift + 2 * n].tobytes() == want.out.tobytes(), shift
-            assert np.all(got[:shift] == SENTINEL) and np.all(got[shift + 2 * n:] == SENTINEL), shift
-    finally:
-        out.free()
+    for shift in (1, 2, 8):
+        out = Guarded(dev, 2 * n, offset=shift)
+        try:
+            dev.blank_dev(cap, cap.nbytes, br.PARITY_FIRST, n, 16, 8, br.PARITY_THRESHOLD, out, None)
+            assert out.read().tobytes() == want.out.tobytes(), shift
+            out.check_pads(f"output, {shift} bytes off alignment")
+        finally:
+            out.free()
 
 
 # ------------------------------------------------------------------------------------------------ 7. the Python layers
@@ -249,10 +206,10 @@ def test_device_blank_and_mitigate_clean_pulsed(dev, cap):
     try:
         assert isinstance(a, gpsjam.Capture) and a.nbytes == cap.nbytes and a.ptr != cap.ptr
         assert a.download().tobytes() == b.download().tobytes() and rec_a.tobytes() == rec_b.tobytes()
-        compare(a.download(), rec_a, want, "Device.blank")
+        br.compare(a.download(), rec_a, want, "Device.blank")
         part, rec_p = dev.blank(cap, br.PARITY_THRESHOLD, window=63, guard=1, first_sample=br.PARITY_FIRST, n_samples=br.PARITY_SAMPLES)
         assert part.nbytes == 2 * br.PARITY_SAMPLES
-        compare(part.download(), rec_p, br.parity_reference(63, 1), "Device.blank on a range")
+        br.compare(part.download(), rec_p, br.parity_reference(63, 1), "Device.blank on a range")
         part.free()
         # the resident result goes wherever a Capture goes
         ridge = dev.ridge(a, nfft=256)
@@ -281,11 +238,11 @@ def test_device_blank_and_mitigate_clean_pulsed(dev, cap):
         assert isinstance(quiet.capture, gpsjam.Capture) and quiet.capture.nbytes == jammed.size
         assert quiet.capture.download().tobytes() == host.capture.download().tobytes() and quiet.records.tobytes() == host.records.tobytes()
         assert quiet[2:] == host[2:]
-        compare(quiet.capture.download(), quiet.records, br.blank(jammed, quiet.threshold, 16, 8), "clean_pulsed, quiet part")
+        br.compare(quiet.capture.download(), quiet.records, br.blank(jammed, quiet.threshold, 16, 8), "clean_pulsed, quiet part")
         assert quiet.removed_share == int(quiet.records["removed"].sum()) / int(quiet.records["total"].sum())
         assert quiet.blanked_share == int(quiet.records["n_blanked"].sum()) / (jammed.size // 2)
         assert given.floor_from == "given" and given.threshold == 1234.5
-        compare(given.capture.download(), given.records, br.blank(jammed, 1234.5, 32, 4), "clean_pulsed, given")
+        br.compare(given.capture.download(), given.records, br.blank(jammed, 1234.5, 32, 4), "clean_pulsed, given")
     finally:
         for r in (quiet, host, given):
             r.capture.free()
@@ -308,7 +265,7 @@ def test_device_blank_and_mitigate_clean_pulsed(dev, cap):
               f"blanked share {low.blanked_share:.4f}")
         assert low.floor_from == "low percentile" and low.threshold == float(np.float32(floor * 10.0 ** 0.6))
         assert floor == pytest.approx(float(np.percentile(power, 25.0)), rel=1e-6) and -0.5 < 10 * math.log10(floor / true) < 0.0
-        compare(low.capture.download(), low.records, br.blank(always, low.threshold, 16, 8), "clean_pulsed, low percentile")
+        br.compare(low.capture.download(), low.records, br.blank(always, low.threshold, 16, 8), "clean_pulsed, low percentile")
         assert 0.25 < low.blanked_share < 0.4
     finally:
         low.capture.free()

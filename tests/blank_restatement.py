@@ -201,3 +201,14 @@ def e2e_blanked_share(records, n_samples):
 def e2e_residual_db(cn0, cn0_free, share):
     """What is left of the C/N0 loss once the samples that were blanked are accounted for."""
     return cn0 - cn0_free - 10.0 * math.log10(1.0 - share)
+
+
+def compare(got, rec, want, what):
+    """GPU bytes and records against a Blanked: all of them equal."""
+    assert got.size == want.out.size and rec.size == want.records.size, what
+    differ = int(np.sum(got != want.out))
+    print(f"{what}: {int(want.blanked.sum())} of {want.blanked.size} samples blanked on {int(want.records['n_rising'].sum())} rising edges, "
+          f"{differ} bytes differ")
+    for key in RECORD.names:
+        np.testing.assert_array_equal(rec[key], want.records[key], err_msg=f"{what} {key}")
+    assert differ == 0, (what, differ, np.flatnonzero(got != want.out)[:8])

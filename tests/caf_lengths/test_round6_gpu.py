@@ -23,14 +23,14 @@ import pytest
 
 import caf_lengths_inputs as ci
 import caf_restatement as caf
-import test_gpu_parity as parity
+import k5_check
 from gpsjam import _ffi
-from xcorr_caf import test_round6_gpu as caf_t
+from gpu_lib import LAG_INVALID, SENTINEL, ResidentSlices as Resident, as_k5, make_slots
+from gpu_lib import caf_records as records
 
 pytestmark = pytest.mark.gpu
 
-Resident, records, make_slots, P7, REC = caf_t.Resident, caf_t.records, caf_t.make_slots, caf_t.P7, caf_t.REC
-SENTINEL = 0xA5
+P7 = caf.P7
 
 
 def ridge(bl: bytes, bp: bytes, n_pairs: int, n_bins: int):
@@ -67,13 +67,13 @@ def test_every_fft_length_under_edge_bins(dev, case):
 @pytest.mark.parametrize("which", [0, 1], ids=["bin=L1+1", "bin=-1"])
 @pytest.mark.parametrize("n", ci.PLANT_N)
 def test_peak_anywhere_in_the_lag_range_under_a_bin(dev, n, which):
-    """K5's planted bursts (test_gpu_parity.k5_planted at k5_edge_lags) through the search's own copy of the lag mapping:
+    """K5's planted bursts (test_gpu_k5_check.k5_planted at k5_edge_lags) through the search's own copy of the lag mapping:
     a burst of at most 16 samples is turned by a nearly constant phase, so the bin's answer is still the planted lag."""
     b = ci.plant_bins(n)[which]
     rng = np.random.default_rng(n + b)
     worst = [0.0, 0.0]
-    for lag in parity.k5_edge_lags(n):
-        s0, s1 = parity.k5_planted(n, lag, rng, width=1 if abs(lag) >= n - 2 else None)
+    for lag in k5_check.k5_edge_lags(n):
+        s0, s1 = k5_check.k5_planted(n, lag, rng, width=1 if abs(lag) >= n - 2 else None)
         Z0, Z1 = ci.spectrum(s0), ci.spectrum(s1)
         recs, lags, peaks = search(dev, [s0, s1], n, [(0, 1), (1, 0)], b, 1)
         for k, (ref, want_lag) in enumerate(((ci.bin_of_spectra(Z1, Z0, b, n), lag), (ci.bin_of_spectra(Z0, Z1, b, n), -lag))):
@@ -107,7 +107,7 @@ def test_a_bins_per_launch_request_above_the_counters_capacity(dev):
         res.close()
     recs = records(outs[0][0])
     lags, peaks = ridge(outs[0][1], outs[0][2], len(P7), nb)
-    assert all(r.lag != caf_t.INVALID and first <= r.bin < first + nb and r.reserved == 0.0 for r in recs)
+    assert all(r.lag != LAG_INVALID and first <= r.bin < first + nb and r.reserved == 0.0 for r in recs)
     # bin 0 of the ridge is K5, bit for bit, in every batching; the record's peak is its row's largest
     assert lags[:, -first].tobytes() == before[0] and peaks[:, -first].tobytes() == before[1]
     assert [r.peak for r in recs] == peaks.max(axis=1).tolist()
@@ -216,5 +216,5 @@ def test_the_tie_rule_on_a_pair_that_is_zero_everywhere(dev, n):
     # K5 on the same pair
     assert (np.frombuffer(k5[0], np.int32)[0], np.frombuffer(k5[1], np.float32)[0], np.frombuffer(k5[2], np.float32)[0]) == \
            (-(n - 1), 0.0, 0.0)
-    assert caf_t.as_k5(zero[0]) == k5 and records(zero[0])[0].bin == 0
+    assert as_k5(zero[0]) == k5 and records(zero[0])[0].bin == 0
     assert zero[1][:4] == k5[0] and zero[2][:4] == k5[1]

@@ -164,7 +164,7 @@ def length_reference(case: LengthCase, raws) -> caf.Surface:
 
 
 # ------------------------------------------------------------------ 2: planted peaks under a bin
-PLANT_N = [32768, (1 << 22) - 3]             # test_gpu_parity.K5_PLANT_N: L1 = 16 (L = 2n: a one-point padding band), L1 = 2048
+PLANT_N = [32768, (1 << 22) - 3]             # k5_check.K5_PLANT_N: L1 = 16 (L = 2n: a one-point padding band), L1 = 2048
 
 
 def plant_bins(n: int):

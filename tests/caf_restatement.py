@@ -126,3 +126,9 @@ def plain_lag(raw_j, raw_i) -> int:
     xj, xi = unpack(raw_j), unpack(raw_i)
     c = signal.correlate(xj, xi, mode="full")
     return int(np.argmax(np.abs(c))) - (xi.size - 1)
+
+
+P3 = [(0, 1), (0, 2), (1, 2)]
+
+
+P7 = P3 + [(1, 0), (2, 0), (0, 0), (2, 2)]     # more than 2 x antennas: K5's many-pair path

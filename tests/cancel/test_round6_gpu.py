@@ -17,16 +17,14 @@ import cancel_restatement as cr
 import excise_restatement as er
 import gpsjam
 import stft_scale_inputs as si
-from excise import test_round6_gpu as excise_t
 from gpsjam import gnss, mitigate
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, Resident, freed, refused, run_excise
+from gpu_lib import run_cancel as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
 REC = gpsjam.CANCEL_DTYPE.itemsize
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind d_out[2 n_samples] and behind d_frames[F]
-RTOL = 1e-5
+RTOL = cr.RTOL
 FA, FB, N = cr.PARITY_FIRST_A, cr.PARITY_FIRST_B, cr.PARITY_SAMPLES
 
 
@@ -38,24 +36,6 @@ def pair(dev):
     b.free()
 
 
-class Resident:
-    """Arrays resident once per (dtype, values)."""
-
-    def __init__(self, dev):
-        self.dev, self.bufs = dev, {}
-
-    def __call__(self, values, dtype=np.float32):
-        values = np.ascontiguousarray(values, dtype)
-        key = (np.dtype(dtype).str, values.tobytes())
-        if key not in self.bufs:
-            self.bufs[key] = self.dev.alloc(max(values.nbytes, 1)).upload(values.reshape(-1).view(np.uint8))
-        return self.bufs[key]
-
-    def free(self):
-        for b in self.bufs.values():
-            b.free()
-
-
 @pytest.fixture(scope="module")
 def res(dev):
     r = Resident(dev)
@@ -63,47 +43,9 @@ def res(dev):
     r.free()
 
 
-def run(dev, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, want_frames=True):
-    """(bytes[2 n_samples], records[F]) through gj_cancel_dev into sentinel-filled buffers."""
-    nf = gpsjam.excise_frames(n_samples, nfft)
-    out, rec = dev.alloc(2 * n_samples + PAD), dev.alloc(nf * REC + PAD)
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
-        dev.cancel_dev(d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, out,
-                       rec if want_frames else None)
-        got, raw = out.download(np.uint8), rec.download(np.uint8)
-    finally:
-        out.free()
-        rec.free()
-    assert np.all(got[2 * n_samples:] == SENTINEL), "bytes were written behind d_out[2 n_samples]"
-    assert np.all(raw[(nf * REC if want_frames else 0):] == SENTINEL), "records were written behind d_frames[F]"
-    return got[:2 * n_samples], raw[:nf * REC].view(gpsjam.CANCEL_DTYPE)
-
-
 def run_pair(dev, pair, nfft, d_w, frames_per_set, n_sets, d_thr, first_a=FA, first_b=FB, n_samples=N, want_frames=True):
     a, b = pair
     return run(dev, a, a.nbytes, first_a, b, b.nbytes, first_b, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, want_frames)
-
-
-def compare(got, rec, want, what):
-    """GPU bytes and records against a cr.Cancelled."""
-    assert rec.size == want.records.size and got.size == want.out.size, what
-    # the mask on every bin: per frame the count is equal, and no bin of the restatement is near its threshold, so a
-    # differing bin would have to be matched by another differing the other way at a margin of 1e-4 each
-    np.testing.assert_array_equal(rec["n_excised"], want.records["n_excised"], err_msg=str(what))
-    tin = want.records["total_in"]
-    for key in ("total_in", "total", "removed"):
-        err = float(np.max(np.abs(rec[key] - want.records[key]) / tin))
-        print(f"{what} {key}: {err:.2e} of total_in")
-        assert err <= RTOL, (what, key, err)
-    assert np.array_equal(got[:want.lo], want.out[:want.lo]) and np.array_equal(got[want.hi:], want.out[want.hi:]), (what, "edges")
-    body, ref = got[want.lo:want.hi].astype(np.int16), want.out[want.lo:want.hi].astype(np.int16)
-    clear = er.tie_distance(want.value) > cr.TIE_BAND
-    diff = np.abs(body - ref)
-    print(f"{what}: {int(np.sum(diff != 0))} of {diff.size} bytes differ, {int(np.sum(~clear))} lie in the tie band")
-    assert not diff[clear].any(), (what, int(np.sum(diff[clear] != 0)), "bytes differ outside the tie band")
-    assert diff.max(initial=0) <= 1, (what, int(diff.max()))
 
 
 # ------------------------------------------------------------------------------------------------ 1. parity
@@ -116,7 +58,7 @@ def test_parity_with_the_restatement(dev, pair, res, nfft):
             w = cr.parity_weights(nfft, offset)
             got, rec = run_pair(dev, pair, nfft, res(w.view(np.float32)), cr.PARITY_FRAMES_PER_SET, w.shape[0],
                                 res(cr.parity_threshold(nfft, scale)))
-            compare(got, rec, want, (nfft, offset))
+            cr.compare(got, rec, want, (nfft, offset))
             # removed is the sum of exactly the restatement's cut bins: with equal counts, a mask that differed in a
             # pair of bins would move `removed` by about a threshold's worth, far more than RTOL of a frame holds
             assert want.cut.any() and not want.cut.all()
@@ -133,7 +75,7 @@ def test_anchors_are_bit_exact(dev, pair, res, nfft):
     d_thr = res(cr.parity_threshold(nfft))
     zero, one = res(np.zeros(2 * nfft)), res(np.tile(np.float32([1.0, 0.0]), nfft))
     # W = 0: gj_excise_dev on capture a, whatever b is
-    ex_b, ex_r = excise_t.run(dev, a, a.nbytes, FA, N, nfft, d_thr)
+    ex_b, ex_r = run_excise(dev, a, a.nbytes, FA, N, nfft, d_thr)
     assert ex_r["n_excised"].any()
     for d_b, nbytes_b, first_b in ((b, b.nbytes, FB), (a, a.nbytes, 0)):
         got, rec = run(dev, a, a.nbytes, FA, d_b, nbytes_b, first_b, N, nfft, zero, 3, 1, d_thr)
@@ -271,14 +213,12 @@ def test_refusals_enqueue_nothing(dev, pair, res):
     n = 8 * 256
     t256, t16 = res(np.full(256, -1.0)), res(np.full(16, -1.0))
     w256 = res(np.zeros(2 * 2 * 256))
-    out, rec = dev.alloc(a.nbytes + PAD), dev.alloc(4096 * REC + PAD)
+    out, rec = Guarded(dev, a.nbytes), Guarded(dev, 4096 * REC)
 
     def args(d_a=a, nbytes_a=a.nbytes, first_a=0, d_b=b, nbytes_b=b.nbytes, first_b=0, n_samples=n, nfft=256, d_w=w256, fps=4, n_sets=2,
              d_thr=t256, d_out=out, d_rec=rec):
         return (d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n_samples, nfft, d_w, fps, n_sets, d_thr, d_out, d_rec)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
         cases = [
             (args(nfft=8), GJ_ERR_UNSUPPORTED),
             (args(nfft=8192, n_samples=3 * 8192), GJ_ERR_UNSUPPORTED),
@@ -310,12 +250,7 @@ def test_refusals_enqueue_nothing(dev, pair, res):
             (args(d_b=out, nbytes_b=a.nbytes, d_out=out.ptr + a.nbytes - 1), GJ_ERR_INVALID),
             (args(d_b=out.ptr + 512, nbytes_b=1024, n_samples=256, d_out=out.ptr + 1), GJ_ERR_INVALID),
         ]
-        for call, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.cancel_dev(*call)
-            assert e.value.status == status, (call[1:3], call[4:12], e.value)
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL)
+        refused(dev, dev.cancel_dev, cases, out, rec)
         # accepted: a call that just fits both captures, the output right behind an input's last byte, d_b == d_a at
         # odd and different firsts, no records, 16 points at the capture's end
         dev.cancel_dev(*args(first_a=FA, first_b=FB, n_samples=N))
@@ -323,10 +258,10 @@ def test_refusals_enqueue_nothing(dev, pair, res):
         dev.cancel_dev(*args(d_b=a, nbytes_b=a.nbytes, first_a=1, first_b=5, d_rec=None))
         dev.cancel_dev(*args(first_a=a.nsamples - 16, first_b=b.nsamples - 16, n_samples=16, nfft=16, d_thr=t16))
         dev.synchronize()
-        assert np.all(out.download(np.uint8, PAD, a.nbytes) == SENTINEL)
+        out.check_pads("output")
+        rec.check_pads("records")
     finally:
-        out.free()
-        rec.free()
+        freed(out, rec)
 
 
 # ------------------------------------------------------------------------------------------------ Device.cancel
@@ -342,7 +277,7 @@ def test_device_cancel_takes_host_bytes_and_captures(dev, pair):
     try:
         assert isinstance(x, gpsjam.Capture) and x.nbytes == 2 * N and rec_x.dtype == gpsjam.CANCEL_DTYPE
         assert x.download().tobytes() == y.download().tobytes() and rec_x.tobytes() == rec_y.tobytes()
-        compare(x.download(), rec_x, want, "Device.cancel")
+        cr.compare(x.download(), rec_x, want, "Device.cancel")
         # one set, no threshold, the defaults: the whole of what both hold from sample 0
         z, rec_z = dev.cancel(pair[0], pair[1], w[0], nfft=nfft)
         assert z.nsamples == min(pair[0].nsamples, pair[1].nsamples) and not rec_z["n_excised"].any()

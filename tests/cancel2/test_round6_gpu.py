@@ -19,17 +19,14 @@ import cancel_restatement as cr
 import excise_restatement as er
 import gpsjam
 import stft_scale_inputs as si
-from cancel import test_round6_gpu as cancel_t
-from excise import test_round6_gpu as excise_t
 from gpsjam import gnss, mitigate
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, Resident, freed, refused, run_cancel, run_excise
+from gpu_lib import run_cancel2 as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
 REC = gpsjam.CANCEL_DTYPE.itemsize
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind d_out[2 n_samples] and behind d_frames[F]
-RTOL = 1e-5
+RTOL = cr.RTOL
 FA, FB, FC, N = c2.PARITY_FIRST_A, c2.PARITY_FIRST_B, c2.PARITY_FIRST_C, c2.PARITY_SAMPLES
 FPS = c2.PARITY_FRAMES_PER_SET
 
@@ -44,54 +41,13 @@ def triple(dev):
 
 @pytest.fixture(scope="module")
 def res(dev):
-    r = cancel_t.Resident(dev)
+    r = Resident(dev)
     yield r
     r.free()
 
 
-def run(dev, caps, firsts, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, want_frames=True):
-    """(bytes[2 n_samples], records[F]) through gj_cancel2_dev into sentinel-filled buffers.  caps: the three captures."""
-    nf = gpsjam.excise_frames(n_samples, nfft)
-    out, rec = dev.alloc(2 * n_samples + PAD), dev.alloc(nf * REC + PAD)
-    (a, b, c), (fa, fb, fc) = caps, firsts
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
-        dev.cancel2_dev(a, a.nbytes, fa, b, b.nbytes, fb, c, c.nbytes, fc, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, out,
-                        rec if want_frames else None)
-        got, raw = out.download(np.uint8), rec.download(np.uint8)
-    finally:
-        out.free()
-        rec.free()
-    assert np.all(got[2 * n_samples:] == SENTINEL), "bytes were written behind d_out[2 n_samples]"
-    assert np.all(raw[(nf * REC if want_frames else 0):] == SENTINEL), "records were written behind d_frames[F]"
-    return got[:2 * n_samples], raw[:nf * REC].view(gpsjam.CANCEL_DTYPE)
-
-
 def run_triple(dev, triple, nfft, d_w, frames_per_set, n_sets, d_thr, firsts=(FA, FB, FC), n_samples=N, want_frames=True):
     return run(dev, triple, firsts, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr, want_frames)
-
-
-def compare(got, rec, want, what):
-    """GPU bytes and records against a Cancelled of the restatement: tests/cancel's comparison with this file's tie band."""
-    assert rec.size == want.records.size and got.size == want.out.size, what
-    np.testing.assert_array_equal(rec["n_excised"], want.records["n_excised"], err_msg=str(what))
-    tin = want.records["total_in"]
-    for key in ("total_in", "total", "removed"):
-        err = float(np.max(np.abs(rec[key] - want.records[key]) / tin))
-        print(f"{what} {key}: {err:.2e} of total_in")
-        assert err <= RTOL, (what, key, err)
-    assert np.array_equal(got[:want.lo], want.out[:want.lo]) and np.array_equal(got[want.hi:], want.out[want.hi:]), (what, "edges")
-    body, ref = got[want.lo:want.hi].astype(np.int16), want.out[want.lo:want.hi].astype(np.int16)
-    clear = er.tie_distance(want.value) > c2.TIE_BAND
-    diff = np.abs(body - ref)
-    print(f"{what}: {int(np.sum(diff != 0))} of {diff.size} bytes differ, {int(np.sum(~clear))} lie in the tie band")
-    assert not diff[clear].any(), (what, int(np.sum(diff[clear] != 0)), "bytes differ outside the tie band")
-    assert diff.max(initial=0) <= 1, (what, int(diff.max()))
-
-
-def f32(w):
-    return np.ascontiguousarray(w, np.complex64).view(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ 1. parity
@@ -102,8 +58,8 @@ def test_parity_with_the_restatement(dev, triple, res, nfft):
             dev.set_unpack(offset, scale)
             want = c2.parity_reference(nfft, offset, scale)
             w = c2.parity_weights(nfft, offset)
-            got, rec = run_triple(dev, triple, nfft, res(f32(w)), FPS, w.shape[0], res(c2.parity_threshold(nfft, scale)))
-            compare(got, rec, want, (nfft, offset))
+            got, rec = run_triple(dev, triple, nfft, res(c2.f32(w)), FPS, w.shape[0], res(c2.parity_threshold(nfft, scale)))
+            c2.compare(got, rec, want, (nfft, offset))
             assert want.cut.any() and not want.cut.all(), "the mask is neither empty nor full"
     finally:
         dev.set_unpack()
@@ -123,15 +79,15 @@ def test_anchors_are_bit_exact(dev, triple, res, nfft):
     # W2 = 0: gj_cancel_dev(a, b, W1), whatever c is;  W1 = 0: gj_cancel_dev(a, c, W2), whatever b is
     for ws, aux, first_aux, others in ((w1_only, b, FB, ((a, b, c), (a, b, a))), (w2_only, c, FC, ((a, b, c), (a, a, c)))):
         single = np.ascontiguousarray(ws[:, 0] + ws[:, 1])                       # the one set that is not zero
-        ref_b, ref_r = cancel_t.run(dev, a, a.nbytes, FA, aux, aux.nbytes, first_aux, N, nfft, res(f32(single)), FPS, n_sets, d_thr)
+        ref_b, ref_r = run_cancel(dev, a, a.nbytes, FA, aux, aux.nbytes, first_aux, N, nfft, res(c2.f32(single)), FPS, n_sets, d_thr)
         assert ref_r["n_excised"].any() and ref_r["total"].tobytes() != ref_r["total_in"].tobytes()
         for caps in others:
             firsts = (FA, FB if caps[1] is b else 0, FC if caps[2] is c else 0)
-            got, rec = run(dev, caps, firsts, N, nfft, res(f32(ws)), FPS, n_sets, d_thr)
+            got, rec = run(dev, caps, firsts, N, nfft, res(c2.f32(ws)), FPS, n_sets, d_thr)
             assert got.tobytes() == ref_b.tobytes(), (nfft, "bytes of gj_cancel_dev")
             assert rec.tobytes() == ref_r.tobytes(), (nfft, "records of gj_cancel_dev")
     # both zero: gj_excise_dev on capture a
-    ex_b, ex_r = excise_t.run(dev, a, a.nbytes, FA, N, nfft, d_thr)
+    ex_b, ex_r = run_excise(dev, a, a.nbytes, FA, N, nfft, d_thr)
     got, rec = run_triple(dev, triple, nfft, res(np.zeros(4 * nfft)), 3, 1, d_thr)
     assert ex_r["n_excised"].any() and got.tobytes() == ex_b.tobytes(), (nfft, "bytes of gj_excise_dev")
     for key in ("total", "removed", "n_excised"):
@@ -153,7 +109,7 @@ def test_anchors_are_bit_exact(dev, triple, res, nfft):
     finally:
         dev.set_unpack()
     # every threshold negative: everything that is left is removed
-    got, rec = run_triple(dev, triple, nfft, res(f32(w)), FPS, n_sets, res(np.full(nfft, -1.0)))
+    got, rec = run_triple(dev, triple, nfft, res(c2.f32(w)), FPS, n_sets, res(np.full(nfft, -1.0)))
     assert np.all(rec["n_excised"] == nfft) and rec["removed"].tobytes() == rec["total"].tobytes() and np.all(rec["total"] > 0)
     assert np.all(got[2 * h:rec.size * nfft] == 128)
 
@@ -164,7 +120,7 @@ def test_translation_null_records_and_repetition(dev, triple, res, nfft):
     h = nfft // 2
     d_thr = res(c2.parity_threshold(nfft))
     w = c2.parity_weights(nfft)
-    d_w, n_sets, set_bytes = res(f32(w)), w.shape[0], 16 * nfft
+    d_w, n_sets, set_bytes = res(c2.f32(w)), w.shape[0], 16 * nfft
     long_b, long_r = run_triple(dev, triple, nfft, d_w, FPS, n_sets, d_thr)
     again_b, again_r = run_triple(dev, triple, nfft, d_w, FPS, n_sets, d_thr)
     assert again_b.tobytes() == long_b.tobytes() and again_r.tobytes() == long_r.tobytes(), "two identical calls"
@@ -236,7 +192,7 @@ def test_runs_longer_than_four_frames(dev, seam_cap, res, nfft):
     assert gpsjam.excise_frames(n, nfft) == f and SEAM_FIRST_C + n <= cap.nsamples
     n_sets = -(-f // fps)
     w = seam_weights(nfft, n_sets)
-    d_w, d_thr = res(f32(w)), res(si.excise_thresholds(nfft))
+    d_w, d_thr = res(c2.f32(w)), res(si.excise_thresholds(nfft))
 
     def call(first_frame, n_samples, want_frames=True):
         assert first_frame % fps == 0
@@ -283,14 +239,12 @@ def test_refusals_enqueue_nothing(dev, triple, res):
     n = 8 * 256
     t256, t16 = res(np.full(256, -1.0)), res(np.full(16, -1.0))
     w256 = res(np.zeros(2 * 2 * 2 * 256))
-    out, rec = dev.alloc(a.nbytes + PAD), dev.alloc(4096 * REC + PAD)
+    out, rec = Guarded(dev, a.nbytes), Guarded(dev, 4096 * REC)
 
     def args(d_a=a, nbytes_a=a.nbytes, first_a=0, d_b=b, nbytes_b=b.nbytes, first_b=0, d_c=c, nbytes_c=c.nbytes, first_c=0, n_samples=n,
              nfft=256, d_w=w256, fps=4, n_sets=2, d_thr=t256, d_out=out, d_rec=rec):
         return (d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, d_c, nbytes_c, first_c, n_samples, nfft, d_w, fps, n_sets, d_thr, d_out, d_rec)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
         cases = [
             (args(nfft=8), GJ_ERR_UNSUPPORTED),
             (args(nfft=8192, n_samples=3 * 8192), GJ_ERR_UNSUPPORTED),
@@ -329,12 +283,7 @@ def test_refusals_enqueue_nothing(dev, triple, res):
             (args(d_c=out, nbytes_c=a.nbytes, d_out=out.ptr + a.nbytes - 1), GJ_ERR_INVALID),
             (args(d_c=out.ptr + 512, nbytes_c=1024, n_samples=256, d_out=out.ptr + 1), GJ_ERR_INVALID),
         ]
-        for call, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.cancel2_dev(*call)
-            assert e.value.status == status, (call[1:3], call[4:6], call[7:15], e.value)
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL)
+        refused(dev, dev.cancel2_dev, cases, out, rec)
         # accepted: a call that just fits all three captures, the output right behind an input's last byte, one pointer
         # at odd and different firsts, no records, 16 points at the captures' ends
         dev.cancel2_dev(*args(first_a=FA, first_b=FB, first_c=FC, n_samples=N))
@@ -342,10 +291,10 @@ def test_refusals_enqueue_nothing(dev, triple, res):
         dev.cancel2_dev(*args(d_b=a, nbytes_b=a.nbytes, d_c=a, nbytes_c=a.nbytes, first_a=1, first_b=5, first_c=8, d_rec=None))
         dev.cancel2_dev(*args(first_a=a.nsamples - 16, first_b=b.nsamples - 16, first_c=c.nsamples - 16, n_samples=16, nfft=16, d_thr=t16))
         dev.synchronize()
-        assert np.all(out.download(np.uint8, PAD, a.nbytes) == SENTINEL)
+        out.check_pads("output")
+        rec.check_pads("records")
     finally:
-        out.free()
-        rec.free()
+        freed(out, rec)
 
 
 # ------------------------------------------------------------------------------------------------ Device.cancel2
@@ -362,7 +311,7 @@ def test_device_cancel2_takes_host_bytes_and_captures(dev, triple):
     try:
         assert isinstance(x, gpsjam.Capture) and x.nbytes == 2 * N and rec_x.dtype == gpsjam.CANCEL_DTYPE
         assert x.download().tobytes() == y.download().tobytes() and rec_x.tobytes() == rec_y.tobytes()
-        compare(x.download(), rec_x, want, "Device.cancel2")
+        c2.compare(x.download(), rec_x, want, "Device.cancel2")
         # one set, no threshold, the defaults: the whole of what all three hold from sample 0
         z, rec_z = dev.cancel2(*triple, w[0], nfft=nfft)
         assert z.nsamples == min(c.nsamples for c in triple) and not rec_z["n_excised"].any()

@@ -197,3 +197,12 @@ def e2e_predicted_db(w1, w2, psi_b, psi_c):
     w1, w2 = np.asarray(w1, np.complex128), np.asarray(w2, np.complex128)
     gain = np.mean(np.abs(1.0 - w1 * np.exp(1j * psi_b) - w2 * np.exp(1j * psi_c)) ** 2)
     return 10.0 * math.log10(gain / np.mean(1.0 + np.abs(w1) ** 2 + np.abs(w2) ** 2))
+
+
+def compare(got, rec, want, what):
+    """GPU bytes and records against a Cancelled of this restatement: the two-antenna comparison with this file's tie band."""
+    cr.compare(got, rec, want, what, TIE_BAND)
+
+
+def f32(w):
+    return np.ascontiguousarray(w, np.complex64).view(np.float32)

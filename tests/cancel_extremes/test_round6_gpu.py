@@ -22,21 +22,18 @@ import cancel_restatement as cr
 import excise_restatement as er
 import extremes_inputs as xi
 import gpsjam
-from cancel import test_round6_gpu as cancel_t
-from cancel2 import test_round6_gpu as cancel2_t
-from extremes.test_round6_gpu import Convention
 from gpsjam import _bands, coherence
+from gpu_lib import GJ_ERR_INVALID, Convention, Guarded, Resident, freed, refused, run_cancel, run_cancel2
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID = cancel_t.GJ_ERR_INVALID
-SENTINEL, PAD, REC = cancel_t.SENTINEL, cancel_t.PAD, cancel_t.REC
-f32 = cancel2_t.f32
+REC = gpsjam.CANCEL_DTYPE.itemsize
+f32 = c2.f32
 
 
 @pytest.fixture(scope="module")
 def res(dev):
-    r = cancel_t.Resident(dev)
+    r = Resident(dev)
     yield r
     r.free()
 
@@ -57,11 +54,11 @@ def caps(dev):
 
 
 def run(dev, captures, firsts, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr):
-    """(bytes, records) through gj_cancel_dev for a pair and gj_cancel2_dev for a triple, by the two files' own run()."""
+    """(bytes, records) through gj_cancel_dev for a pair and gj_cancel2_dev for a triple, by gpu_lib's run_cancel and run_cancel2."""
     if len(captures) == 2:
         (a, b), (fa, fb) = captures, firsts[:2]
-        return cancel_t.run(dev, a, a.nbytes, fa, b, b.nbytes, fb, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr)
-    return cancel2_t.run(dev, tuple(captures), tuple(firsts), n_samples, nfft, d_w, frames_per_set, n_sets, d_thr)
+        return run_cancel(dev, a, a.nbytes, fa, b, b.nbytes, fb, n_samples, nfft, d_w, frames_per_set, n_sets, d_thr)
+    return run_cancel2(dev, tuple(captures), tuple(firsts), n_samples, nfft, d_w, frames_per_set, n_sets, d_thr)
 
 
 def compare(got, rec, want, d_f, band, tol, what):
@@ -164,18 +161,11 @@ def far(dev):
 
 def refused_and_wrote_nothing(dev, launch, args_of, n_samples, nfft):
     """launch(*args_of(out, rec)) is GJ_ERR_INVALID and leaves sentinel-filled buffers as they were."""
-    out, rec = dev.alloc(2 * n_samples + PAD), dev.alloc(gpsjam.excise_frames(n_samples, nfft) * REC + PAD)
+    out, rec = Guarded(dev, 2 * n_samples), Guarded(dev, gpsjam.excise_frames(n_samples, nfft) * REC)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
-        with pytest.raises(gpsjam.GpsJamError) as e:
-            launch(*args_of(out, rec))
-        assert e.value.status == GJ_ERR_INVALID, e.value
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL)
+        refused(dev, launch, [(args_of(out, rec), GJ_ERR_INVALID)], out, rec)
     finally:
-        out.free()
-        rec.free()
+        freed(out, rec)
 
 
 @pytest.mark.parametrize("nfft", ce.FAR_NFFT)
@@ -184,7 +174,7 @@ def test_past_byte_2_32(dev, far, res, n_aux, nfft):
     """a, b (and c) are the windows at samples 2^31 + 1, 2^31 + 4 (and 2^31 + 9) of the big allocation: the bits of the
     same bytes uploaded as a small capture, which give the restatement's result by the parity comparison."""
     big, small = far
-    mod, mod_t = (cr, cancel_t) if n_aux == 1 else (c2, cancel2_t)
+    mod = cr if n_aux == 1 else c2
     n, fps, s0 = ce.FAR_SAMPLES, cr.PARITY_FRAMES_PER_SET, ce.FAR_S0
     w = mod.parity_weights(nfft)
     d_w, n_sets, d_thr = res(f32(w)), w.shape[0], res(ce.far_threshold(n_aux, nfft))
@@ -197,7 +187,7 @@ def test_past_byte_2_32(dev, far, res, n_aux, nfft):
                    d_w, fps, n_sets, d_thr)
 
     near_b, near_r = call(*[False] * (1 + n_aux))
-    mod_t.compare(near_b, near_r, ce.far_reference(n_aux, nfft), (n_aux, nfft, "the window as a capture of its own"))
+    mod.compare(near_b, near_r, ce.far_reference(n_aux, nfft), (n_aux, nfft, "the window as a capture of its own"))
     mixes = [[True] * (1 + n_aux)] + [[i == j for j in range(1 + n_aux)] for i in range(1 + n_aux)]
     if n_aux == 1:
         assert mixes == [[True, True], [True, False], [False, True]]

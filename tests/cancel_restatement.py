@@ -245,3 +245,26 @@ def e2e_predicted_db(w_abs, dphi):
     """What the canceller costs a satellite whose inter-antenna phase is dphi from the jammer's: the signal goes through
     |1 - W e^{j dphi}|^2 and the noise rises by 1 + |W|^2."""
     return 10.0 * math.log10(abs(1.0 - w_abs * np.exp(1j * dphi)) ** 2 / (1.0 + w_abs * w_abs))
+
+
+RTOL = 1e-5                                     # of total_in: the project's figure for a K2 value summed in another order
+
+
+def compare(got, rec, want, what, band=TIE_BAND):
+    """GPU bytes and records against a Cancelled; ``band``: the tie band of the canceller that made them."""
+    assert rec.size == want.records.size and got.size == want.out.size, what
+    # the mask on every bin: per frame the count is equal, and no bin of the restatement is near its threshold, so a
+    # differing bin would have to be matched by another differing the other way at a margin of 1e-4 each
+    np.testing.assert_array_equal(rec["n_excised"], want.records["n_excised"], err_msg=str(what))
+    tin = want.records["total_in"]
+    for key in ("total_in", "total", "removed"):
+        err = float(np.max(np.abs(rec[key] - want.records[key]) / tin))
+        print(f"{what} {key}: {err:.2e} of total_in")
+        assert err <= RTOL, (what, key, err)
+    assert np.array_equal(got[:want.lo], want.out[:want.lo]) and np.array_equal(got[want.hi:], want.out[want.hi:]), (what, "edges")
+    body, ref = got[want.lo:want.hi].astype(np.int16), want.out[want.lo:want.hi].astype(np.int16)
+    clear = er.tie_distance(want.value) > band
+    diff = np.abs(body - ref)
+    print(f"{what}: {int(np.sum(diff != 0))} of {diff.size} bytes differ, {int(np.sum(~clear))} lie in the tie band")
+    assert not diff[clear].any(), (what, int(np.sum(diff[clear] != 0)), "bytes differ outside the tie band")
+    assert diff.max(initial=0) <= 1, (what, int(diff.max()))

@@ -16,13 +16,12 @@ import chirp_restatement as cr
 import gpsjam
 import ridge_restatement as rr
 from gpsjam import classify
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, freed, refused
+from gpu_lib import run_chirp as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
 REC = gpsjam.CHIRP_DTYPE.itemsize
-SENTINEL = 0xA5
-PAD = 64                                        # sentinel records behind d_out[n_frames], sentinel floats behind d_peaks
 RTOL = cr.RTOL
 
 
@@ -40,55 +39,6 @@ def caps(dev):
         c.free()
 
 
-def run(dev, d_iq, nbytes, nfft, hop, first, n_frames, rates, guard=2, want_peaks=True):
-    """(records, peaks or None) of one gj_chirp_dev call into sentinel-filled buffers; the bytes behind the records and
-    behind the peaks must stay untouched."""
-    n_rates = rates[2]
-    out = dev.alloc((n_frames + PAD) * REC)
-    pk = dev.alloc((n_frames * n_rates + PAD) * 4) if want_peaks else None
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        if pk is not None:
-            pk.upload(np.full(pk.nbytes, SENTINEL, np.uint8))
-        dev.chirp_dev(d_iq, nbytes, first, nfft, hop, n_frames, guard, rates[0], rates[1], n_rates, out, pk)
-        raw = out.download(np.uint8)
-        praw = pk.download(np.uint8) if pk is not None else None
-    finally:
-        out.free()
-        if pk is not None:
-            pk.free()
-    assert np.all(raw[n_frames * REC:] == SENTINEL), "records were written behind d_out[n_frames]"
-    rec = raw[:n_frames * REC].view(gpsjam.CHIRP_DTYPE)
-    assert not rec["reserved"].any()
-    if praw is None:
-        return rec, None
-    assert np.all(praw[n_frames * n_rates * 4:] == SENTINEL), "peaks were written behind d_peaks[n_frames][n_rates]"
-    return rec, praw[:n_frames * n_rates * 4].view(np.float32).reshape(n_frames, n_rates)
-
-
-WORST = {"total": 0.0, "peak": 0.0, "second": 0.0, "peaks": 0.0}   # largest error met so far, printed for the notes
-
-
-def compare(got, peaks, want, what):
-    rec = want.records
-    assert got.size == rec.size, what
-    np.testing.assert_array_equal(got["rate_index"], rec["rate_index"], err_msg=str(what))
-    np.testing.assert_array_equal(got["peak_bin"], rec["peak_bin"], err_msg=str(what))
-    for key in ("total", "peak"):
-        err = np.max(np.abs(got[key] - rec[key]) / rec[key])
-        WORST[key] = max(WORST[key], float(err))
-        assert err <= RTOL, (what, key, err)
-    err = np.max(np.abs(got["second"] - rec["second"]) / rec["peak"])
-    WORST["second"] = max(WORST["second"], float(err))
-    assert err <= RTOL, (what, "second", err)
-    if peaks is not None:
-        err = np.max(np.abs(peaks - want.peaks) / want.peaks)
-        WORST["peaks"] = max(WORST["peaks"], float(err))
-        assert err <= RTOL, (what, "peaks", err)
-        rows = np.arange(got.size)
-        assert np.array_equal(peaks[rows, got["rate_index"]], got["peak"]), what
-
-
 @pytest.mark.parametrize("nfft", cr.PARITY_NFFT)
 def test_parity_with_the_restatement(dev, caps, nfft):
     cap = caps(nfft)
@@ -96,12 +46,12 @@ def test_parity_with_the_restatement(dev, caps, nfft):
         for first in (0, 1):
             want = cr.parity_reference(nfft, rates, first)
             got, peaks = run(dev, cap, cap.nbytes, nfft, cr.parity_hop(nfft), first, want.records.size, rates)
-            compare(got, peaks, want, (nfft, rates, first))
+            cr.compare(got, peaks, want, (nfft, rates, first))
     # guard 0: only `second` changes
     want = cr.parity_reference(nfft, (-3, 2, 5), 1, 0)
     got, _ = run(dev, cap, cap.nbytes, nfft, cr.parity_hop(nfft), 1, want.records.size, (-3, 2, 5), guard=0, want_peaks=False)
-    compare(got, None, want, (nfft, "guard 0"))
-    print(f"nfft {nfft}: largest relative errors so far {WORST} (tolerance {RTOL:.0e})")
+    cr.compare(got, None, want, (nfft, "guard 0"))
+    print(f"nfft {nfft}: largest relative errors so far {cr.WORST} (tolerance {RTOL:.0e})")
 
 
 @pytest.mark.parametrize("nfft", [64, 1024, 4096])
@@ -153,7 +103,7 @@ def test_frame_counts_that_do_not_fill_a_workgroup_step(dev, caps, nfft):
             got, peaks = run(dev, exact, nbytes, nfft, hop, first, n_frames, rates)
         want = cr.parity_reference(nfft, rates, first)
         head = cr.Scan(want.records[:n_frames], want.peaks[:n_frames], None, None)
-        compare(got, peaks, head, (nfft, n_frames, "exact"))
+        cr.compare(got, peaks, head, (nfft, n_frames, "exact"))
         # the same frames as the head of the long capture: same bits
         long, lpeaks = run(dev, cap, cap.nbytes, nfft, hop, first, n_frames, rates)
         assert long.tobytes() == got.tobytes() and lpeaks.tobytes() == peaks.tobytes(), (nfft, n_frames)
@@ -186,13 +136,13 @@ def test_unpack_convention(dev):
                 assert not peaks.any()
             want = cr.parity_reference(nfft, rates, first, 2, 128.0, 1.0 / 128.0)
             got, peaks = run(dev, cap, cap.nbytes, nfft, cr.parity_hop(nfft), first, want.records.size, rates)
-            compare(got, peaks, want, "gnssdec convention")
+            cr.compare(got, peaks, want, "gnssdec convention")
         finally:
             dev.set_unpack()
         assert dev.get_unpack() == (127.5, 1.0 / 127.5)
         want = cr.parity_reference(nfft, rates, first)
         got, peaks = run(dev, cap, cap.nbytes, nfft, cr.parity_hop(nfft), first, want.records.size, rates)
-        compare(got, peaks, want, "default convention restored")
+        cr.compare(got, peaks, want, "default convention restored")
 
 
 def test_refusals_enqueue_nothing(dev, caps):
@@ -210,21 +160,13 @@ def test_refusals_enqueue_nothing(dev, caps):
         (256, 128, 0, 0, 2, ok, GJ_ERR_INVALID), (256, 128, 0, fit + 1, 2, ok, GJ_ERR_INVALID),
         (256, 128, cap.nsamples, 1, 2, ok, GJ_ERR_INVALID),
     ]
-    out = dev.alloc((fit + 1 + PAD) * REC)
-    pk = dev.alloc((fit + 1) * 2 * 4 + 64)
+    out, pk = Guarded(dev, (fit + 1) * REC, pad=64 * REC), Guarded(dev, (fit + 1) * 2 * 4)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        pk.upload(np.full(pk.nbytes, SENTINEL, np.uint8))
-        for nfft, hop, first, n_frames, guard, (q0, dq, nq), status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.chirp_dev(cap, cap.nbytes, first, nfft, hop, n_frames, guard, q0, dq, nq, out, pk)
-            assert e.value.status == status, (nfft, hop, first, n_frames, guard, q0, dq, nq, e.value)
+        calls = [((cap, cap.nbytes, first, nfft, hop, n_frames, guard, q0, dq, nq, out, pk), status)
+                 for nfft, hop, first, n_frames, guard, (q0, dq, nq), status in cases]
         for d_iq, d_out, d_pk in ((0, out, pk), (cap, 0, pk), (cap.ptr + 1, out, pk), (cap, out.ptr + 2, pk), (cap, out, pk.ptr + 2)):
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.chirp_dev(d_iq, cap.nbytes - 2, 0, 256, 128, 4, 2, 0, 1, 1, d_out, d_pk)
-            assert e.value.status == GJ_ERR_INVALID
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(pk.download(np.uint8) == SENTINEL)
+            calls.append(((d_iq, cap.nbytes - 2, 0, 256, 128, 4, 2, 0, 1, 1, d_out, d_pk), GJ_ERR_INVALID))
+        refused(dev, dev.chirp_dev, calls, out, pk)
         # the limits themselves are accepted: 256 rates, both ends of the rate range, the largest guard, every frame that fits
         big = dev.alloc(4 * 256 * 4)
         try:
@@ -234,10 +176,12 @@ def test_refusals_enqueue_nothing(dev, caps):
             dev.chirp_dev(cap, cap.nbytes, 0, 4096, 2048, 1, 2, -8388608, 1, 1, out, None)
             dev.chirp_dev(cap, cap.nbytes, 0, 256, 128, fit, 2, 0, 1, 2, out, pk)
             dev.synchronize()
+            out.check_pads("records")
+            pk.check_pads("peaks")
         finally:
             big.free()
     finally:
-        out.free()
+        freed(out, pk)
         pk.free()
 
 
@@ -249,7 +193,7 @@ def test_device_chirp_takes_host_bytes_and_captures(dev, caps):
     b = dev.chirp(cr.parity_capture(nfft), nfft=nfft, hop=hop, rates=rates, guard=2)
     assert (a.nfft, a.hop, a.first_sample, a.guard, a.rates, len(a)) == (nfft, hop, 0, 2, rates, want.records.size)
     assert a.records.tobytes() == b.records.tobytes() and b.peaks is None
-    compare(a.records, a.peaks, want, "Device.chirp")
+    cr.compare(a.records, a.peaks, want, "Device.chirp")
     np.testing.assert_array_equal(a.rate, -3 + 2 * want.records["rate_index"])
     part = dev.chirp(cap, nfft=nfft, hop=100, rates=(1, 1, 2), first_sample=5, n_frames=10, guard=1)
     assert len(part) == 10 and part[4:].first_sample == 405 and part.hop == 100

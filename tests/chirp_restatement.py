@@ -196,3 +196,26 @@ def fast_chirp_capture():
 
 def classifier_capture(case):
     return fast_chirp_capture() if case == "fast chirp" else rr.classifier_capture(case)
+
+
+WORST = {"total": 0.0, "peak": 0.0, "second": 0.0, "peaks": 0.0}   # largest error met so far, printed for the notes
+
+
+def compare(got, peaks, want, what):
+    rec = want.records
+    assert got.size == rec.size, what
+    np.testing.assert_array_equal(got["rate_index"], rec["rate_index"], err_msg=str(what))
+    np.testing.assert_array_equal(got["peak_bin"], rec["peak_bin"], err_msg=str(what))
+    for key in ("total", "peak"):
+        err = np.max(np.abs(got[key] - rec[key]) / rec[key])
+        WORST[key] = max(WORST[key], float(err))
+        assert err <= RTOL, (what, key, err)
+    err = np.max(np.abs(got["second"] - rec["second"]) / rec["peak"])
+    WORST["second"] = max(WORST["second"], float(err))
+    assert err <= RTOL, (what, "second", err)
+    if peaks is not None:
+        err = np.max(np.abs(peaks - want.peaks) / want.peaks)
+        WORST["peaks"] = max(WORST["peaks"], float(err))
+        assert err <= RTOL, (what, "peaks", err)
+        rows = np.arange(got.size)
+        assert np.array_equal(peaks[rows, got["rate_index"]], got["peak"]), what

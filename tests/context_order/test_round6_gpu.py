@@ -35,6 +35,7 @@ import pytest
 
 import context_order_inputs as co
 import gpsjam
+from gpu_lib import SENTINEL
 
 pytestmark = pytest.mark.gpu
 
@@ -98,7 +99,7 @@ def same(probes, expect, names, slot=0, what=""):
 def test_alone_against_the_restatement(name):
     outs = solitary(name)
     assert all(len(o) for o in outs)
-    assert any(o != bytes([co.SENTINEL]) * len(o) for o in outs), "the call wrote its outputs"
+    assert any(o != bytes([SENTINEL]) * len(o) for o in outs), "the call wrote its outputs"
 
 
 # ------------------------------------------------------------------------------------------------ 2. growth in flight

@@ -23,12 +23,12 @@ from typing import Callable, NamedTuple, Tuple
 
 import numpy as np
 
+import acq_edges_inputs as ai
 import gpsjam
 from gpsjam import _ffi, gnss
 from gpsjam.synth import StreamSpec, generate
+from gpu_lib import CAF_REC, Guarded, caf_records, make_slots
 
-SENTINEL = 0xA5
-PAD = 256
 DEFAULT = (127.5, 1.0 / 127.5)
 CONVENTIONS = (DEFAULT, (128.0, 1.0 / 128.0), (0.0, 1.0), (255.0, 1.0))     # the order test 6 queues them in
 FILLS = (0x00, 0xFF, 0x7F)          # zeros (what fresh pages hold), NaN / all-ones, large finite float / large positive int
@@ -124,7 +124,6 @@ ACQ_INTG = 3
 
 @functools.lru_cache(maxsize=None)
 def acq_case():
-    import acq_edges_inputs as ai
     nsamp = ai.nsamp_of(ACQ_FS)
     raw = ai.gps_like(2 * 700 + (ACQ_INTG + 1) * nsamp + ai.TAIL + 5, [(3, 200.0, nsamp // 3, 9.0)], fs=ACQ_FS, seed=49)
     return ai.Case("context order 512", raw, ACQ_FS, ACQ_PRNS, first=5, intg=ACQ_INTG, hband=600.0)
@@ -138,9 +137,8 @@ BIG_SERIES_STRIDE = 1500
 
 @functools.lru_cache(maxsize=None)
 def big_series_capture(n_epochs):
-    from acq_series import test_acq_gpu as series_t
     n = 1000 + (n_epochs - 1) * BIG_SERIES_STRIDE + 11 * 2048 + 3 * 2048
-    raw = series_t.gps_like(n, BIG_SERIES_SATS)
+    raw = ai.series_like(n, BIG_SERIES_SATS)
     raw.setflags(write=False)
     return raw
 
@@ -185,12 +183,11 @@ def _build_chunk_power(dev):
 def _check_scan(raw, power, amp, onset, conv):
     import exact_restatement as ex
     from oracle import gpsjam_oracle as orc
-    import test_round6_gpu as k34_t
     if not _default_only(conv):
         return
     np.testing.assert_array_equal(_view(power, np.float32), ex.chunk_power(raw, 65536))
-    k34_t._check_exact(amp, onset, raw, 0.1)
-    assert _view(onset, k34_t.ONSET_T)[0]["start"] == orc.tdoa_onset(orc.tdoa_unpack(raw)) > 0
+    ex.check_exact(amp, onset, raw, 0.1)
+    assert _view(onset, ex.ONSET_T)[0]["start"] == orc.tdoa_onset(orc.tdoa_unpack(raw)) > 0
 
 
 def _build_scan(fused_tail):
@@ -220,7 +217,6 @@ def _build_scan(fused_tail):
 
 def _build_amp_onset(which, offset):
     def build(dev):
-        import test_round6_gpu as k34_t
         raw = amp_capture()
         cap = dev.alloc(raw.size + 16).upload(raw)
         nbytes = raw.size - 2
@@ -237,12 +233,12 @@ def _build_amp_onset(which, offset):
             if not _default_only(conv):
                 return
             if which == "amp":
-                a, want = _view(outs[0], k34_t.AMP_T)[0], ex.amp_stats(piece, 0.2)
+                a, want = _view(outs[0], ex.AMP_T)[0], ex.amp_stats(piece, 0.2)
                 assert (a["i"], a["c"]) == (want["first"], want["count"]) and want["count"] > 0
                 np.testing.assert_allclose(a["s"], want["sum"], rtol=2e-7)
                 np.testing.assert_allclose(a["m"], want["mean"], rtol=2e-7)
             else:
-                o, want = _view(outs[0], k34_t.ONSET_T)[0], ex.onset(piece, NOISE, WINDOW, FACTOR)
+                o, want = _view(outs[0], ex.ONSET_T)[0], ex.onset(piece, NOISE, WINDOW, FACTOR)
                 assert want["start"] > 0
                 for f in ("start", "guard", "noise", "thr", "hit"):
                     assert o[f] == want[f], (f, o, want)
@@ -355,8 +351,7 @@ def _build_xcorr(n, slots=False):
     def build(dev):
         raws = antennas(n, False)
         if slots:
-            from xcorr_caf import test_round6_gpu as caf_t
-            d_slots, sb = caf_t.make_slots(dev, raws, n)
+            d_slots, sb = make_slots(dev, raws, n)
             keep = [d_slots]
 
             def launch(outs):
@@ -375,10 +370,9 @@ def _build_xcorr(n, slots=False):
 def _build_caf(n, slots=False):
     def build(dev):
         import caf_lengths_inputs as ci
-        from xcorr_caf import test_round6_gpu as caf_t
         raws = antennas(n, True)
         if slots:
-            d_slots, sb = caf_t.make_slots(dev, raws, n)
+            d_slots, sb = make_slots(dev, raws, n)
             keep = [d_slots]
 
             def launch(outs):
@@ -394,7 +388,7 @@ def _build_caf(n, slots=False):
         def check(outs, conv):
             if not _restated(conv):
                 return
-            recs = caf_t.records(outs[0])
+            recs = caf_records(outs[0])
             lags = _view(outs[1], np.int32).reshape(3, CAF_BINS)
             peaks = _view(outs[2], np.float32).reshape(3, CAF_BINS)
             bins = list(range(CAF_FIRST, CAF_FIRST + CAF_BINS))
@@ -404,7 +398,7 @@ def _build_caf(n, slots=False):
                 assert (want.lag, want.bin) == (CAF_SPECS[j][0] - CAF_SPECS[i][0], int(CAF_SPECS[j][1] - CAF_SPECS[i][1]))
                 ci.hold(recs[k], lags[k], peaks[k], want, f"n {n} pair {(i, j)} offset {conv[0]}")
             assert bins[0] == -2
-        return Built(keep, (caf_t.REC * 3, 4 * 3 * CAF_BINS, 4 * 3 * CAF_BINS), launch, check)
+        return Built(keep, (CAF_REC * 3, 4 * 3 * CAF_BINS, 4 * 3 * CAF_BINS), launch, check)
     return build
 
 
@@ -423,19 +417,15 @@ def _acq_searcher(dev, case):
 
 
 def _check_acq_records(rec_bytes, case, what):
-    import acq_edges_inputs as ai
-    from acq_edges import test_acq_gpu as acq_t
-    got = acq_t.records(rec_bytes)
+    got = ai.records(rec_bytes)
     ref = ai.reference(case)
     for k, prn in enumerate(case.prns):
-        acq_t.check_record(got[k], ref[prn][-1], case, (what, prn))
+        ai.check_record(got[k], ref[prn][-1], case, (what, prn))
     return got
 
 
 def _build_acq_search(with_power):
     def build(dev):
-        import acq_edges_inputs as ai
-        from acq_edges import test_acq_gpu as acq_t
         case = acq_case()
         srch = _acq_searcher(dev, case)
         cap = dev.alloc(case.raw.size + 16).upload(case.raw)
@@ -448,21 +438,20 @@ def _build_acq_search(with_power):
             got = _check_acq_records(outs[0], case, "power form" if with_power else "single launch")
             assert bool(got[0]["acquired"]) and bool(got[2]["acquired"]) and not bool(got[1]["acquired"])
             assert int(got[1]["steps"]) == case.intg >= 2, "the absent PRN runs every step: running maxima and done flags are used"
-            assert outs[0][:acq_t.REC] == outs[0][2 * acq_t.REC:], "the repeated PRN: the same record"
+            assert outs[0][:ai.REC] == outs[0][2 * ai.REC:], "the repeated PRN: the same record"
             if with_power:
                 P = _view(outs[1], np.float64).reshape(len(case.prns), len(srch.freqs), srch.nsamp)
                 for k, prn in enumerate(case.prns):
-                    acq_t.check_power(P[k], ai.reference(case)[prn][-1], case, ("power form", prn))
-        return Built([srch, cap], (acq_t.REC * len(case.prns),) + ((8 * cells,) if with_power else ()), launch, check)
+                    ai.check_power(P[k], ai.reference(case)[prn][-1], case, ("power form", prn))
+        return Built([srch, cap], (ai.REC * len(case.prns),) + ((8 * cells,) if with_power else ()), launch, check)
     return build
 
 
 def _build_acq_series(dev):
-    from acq_edges import test_acq_gpu as acq_t
     case = acq_case()
     srch = _acq_searcher(dev, case)
     cap = dev.alloc(case.raw.size + 16).upload(case.raw)
-    per = acq_t.REC * len(case.prns)
+    per = ai.REC * len(case.prns)
 
     def check(outs, conv):
         for e in range(SERIES_EPOCHS):
@@ -475,17 +464,16 @@ def _build_big_series(n_epochs):
     """The series at the reference's own rate (nsamp 2048, 71 bins, intg 10) with every epoch in ONE launch: a rung of the
     ladder.  Held to the oracle's search at the first and the last epoch, as tests/acq_series does."""
     def build(dev):
-        from acq_series import test_acq_gpu as series_t
         raw = big_series_capture(n_epochs)
         srch = _quiet_searcher(dev, prns=BIG_SERIES_PRNS)
         cap = dev.alloc(raw.size + 16).upload(raw)
-        per = series_t.REC * len(BIG_SERIES_PRNS)
+        per = ai.REC * len(BIG_SERIES_PRNS)
 
         def check(outs, conv):
             for e in (0, n_epochs - 1):
                 first = 1000 + e * BIG_SERIES_STRIDE
                 for k, prn in enumerate(BIG_SERIES_PRNS):
-                    r = gnss._AcqStruct.from_buffer_copy(outs[0], e * per + k * series_t.REC)
+                    r = gnss._AcqStruct.from_buffer_copy(outs[0], e * per + k * ai.REC)
                     want = big_series_reference(n_epochs, first, prn)
                     assert bool(r.acquired) == want["acquired"] and r.steps == want["steps"], (e, prn, want)
                     if want["peakr"] > 1.5:
@@ -554,7 +542,6 @@ def _build_sk(nfft, hop, m, n_rows, first=1):
     def build(dev):
         import ridge_restatement as rr
         import skurt_restatement as sr
-        from skurt import test_round6_gpu as skurt_t
         raw = rr.parity_capture()
         cap = dev.alloc(raw.size + 16).upload(raw)
         assert n_rows <= gpsjam.sk_rows(raw.size, first, nfft, hop, m)
@@ -563,7 +550,7 @@ def _build_sk(nfft, hop, m, n_rows, first=1):
             got = tuple(_view(o, np.float32).reshape(n_rows, nfft) for o in outs)
             if not _restated(conv):
                 return
-            skurt_t.compare(got, sk_powers(nfft, hop, first, m * n_rows, conv), m, n_rows, ("context order", nfft, m, conv))
+            sr.compare(got, sk_powers(nfft, hop, first, m * n_rows, conv), m, n_rows, ("context order", nfft, m, conv))
         return Built([cap], (4 * n_rows * nfft,) * 3,
                      lambda outs: dev.spectral_kurtosis_dev(cap, raw.size, first, nfft, hop, m, n_rows, outs[0], outs[1], outs[2]), check)
     return build
@@ -581,7 +568,6 @@ def sk_powers(nfft, hop, first, n_frames, conv):
 def _build_csd(nfft, hop, m, n_rows):
     def build(dev):
         import csd_restatement as cs
-        from csd import test_round6_gpu as csd_t
         a, b = cs.parity_pair()
         ca, cb = dev.alloc(a.size + 16).upload(a), dev.alloc(b.size + 16).upload(b)
         fa, fb = cs.PARITY_FIRST_A, cs.PARITY_FIRST_B
@@ -592,7 +578,7 @@ def _build_csd(nfft, hop, m, n_rows):
             got = (_view(outs[0], np.float32).reshape(cells), _view(outs[1], np.float32).reshape(cells),
                    _view(outs[2], np.complex64).reshape(cells), _view(outs[3], np.float32).reshape(cells))
             if _restated(conv):
-                csd_t.compare(got, csd_reference(nfft, hop, m, n_rows, conv), ("context order", nfft, m, conv))
+                cs.compare(got, csd_reference(nfft, hop, m, n_rows, conv), ("context order", nfft, m, conv))
         return Built([ca, cb], (4 * n_rows * nfft, 4 * n_rows * nfft, 8 * n_rows * nfft, 4 * n_rows * nfft),
                      lambda outs: dev.cross_spectrum_dev(ca, a.size, fa, cb, b.size, fb, nfft, hop, m, n_rows, outs[0], outs[1], outs[2], outs[3]),
                      check)
@@ -796,23 +782,20 @@ class Probe:
     def __init__(self, dev, spec, slots=2):
         self.dev, self.spec = dev, spec
         self.built = spec.build(dev)
-        self.outs = [[dev.alloc(s + PAD) for s in self.built.out_sizes] for _ in range(slots)]
-        for slot in range(slots):
-            self.scrub(slot)
+        self.outs = [[Guarded(dev, s) for s in self.built.out_sizes] for _ in range(slots)]
 
     def scrub(self, slot=0):
         for b in self.outs[slot]:
-            b.upload(np.full(b.nbytes, SENTINEL, np.uint8))
+            b.refill()
 
     def enqueue(self, slot=0):
         self.built.launch(self.outs[slot])
 
     def download(self, slot=0):
-        """The outputs as bytes (waits for the stream); the pads behind them must still hold the sentinel."""
-        raw = [b.download(np.uint8) for b in self.outs[slot]]
-        for k, (r, s) in enumerate(zip(raw, self.built.out_sizes)):
-            assert np.all(r[s:] == SENTINEL), f"{self.spec.name}: bytes were written behind output {k}"
-        return tuple(r[:s].tobytes() for r, s in zip(raw, self.built.out_sizes))
+        """The outputs as bytes (waits for the stream); the pads on either side of them must still hold the sentinel."""
+        for k, b in enumerate(self.outs[slot]):
+            b.check_pads(f"output {k} ({self.spec.name})")
+        return tuple(b.read().tobytes() for b in self.outs[slot])
 
     def check(self, outs, conv=DEFAULT):
         self.built.check(outs, conv)

@@ -18,12 +18,11 @@ import pytest
 import corr_restatement as cr
 import gpsjam
 from gpsjam import gnss, postcorr, spoof
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, freed, refused
+from gpu_lib import run_corr as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind the records
 TAPS9 = (1, -64, 0, 64, -1, 33, -17, 2, -2)     # 0, +-1, +-64 among them, in scrambled order
 
 
@@ -39,23 +38,6 @@ def d_codes(dev):
     b = dev.alloc(cr.parity_codes().nbytes).upload(cr.parity_codes())
     yield b
     b.free()
-
-
-def run(dev, capture, first, n, B, d_rows, n_rows, channels, taps, nbytes=None):
-    """int32[n_channels][blocks][n_taps][2] through gj_corr_bank_dev into a sentinel-filled buffer."""
-    rec = np.array(channels, gpsjam.CORR_CHANNEL_DTYPE)
-    size = 8 * len(channels) * gpsjam.corr_blocks(n, B) * len(taps)
-    out, d_ch = dev.alloc(size + PAD), dev.alloc(rec.nbytes)
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        d_ch.upload(rec)
-        dev.corr_bank_dev(capture, capture.nbytes if nbytes is None else nbytes, first, n, B, d_rows, n_rows, d_ch, len(channels), taps, out)
-        got = out.download(np.uint8)
-    finally:
-        out.free()
-        d_ch.free()
-    assert np.all(got[size:] == SENTINEL), "bytes were written behind the call's records"
-    return got[:size].view(np.int32).reshape(len(channels), -1, len(taps), 2)
 
 
 def compare(dev, capture, raw, first, n, B, d_rows, codes, channels, taps):
@@ -136,9 +118,8 @@ def test_refusals_enqueue_nothing(dev, cap, d_codes):
     rec = np.array(channels, gpsjam.CORR_CHANNEL_DTYPE)
     n, B, T = 3 * 2048, 2048, (0, -1, 1)
     size = 8 * 3 * 3 * 3
-    out, d_ch = dev.alloc(size + PAD), dev.alloc(rec.nbytes + 8)
+    out, d_ch = Guarded(dev, size), dev.alloc(rec.nbytes + 8)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
         d_ch.upload(rec)
         I, U = GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
         cases = [  # d_iq, nbytes, first, n, B, d_codes, rows, d_channels, n_channels, taps, d_out, status
@@ -167,12 +148,8 @@ def test_refusals_enqueue_nothing(dev, cap, d_codes):
             (cap, cap.nbytes, 0, 0, B, d_codes, 4, d_ch, 3, T, out, U),                            # n_samples
             (cap, 2 ** 40, 0, 2 ** 28 + 1, B, d_codes, 4, d_ch, 3, T, out, U),
         ]
-        for d_iq, nbytes, first, ns, bs, d_rows, rows, d_c, n_ch, taps, d_o, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.corr_bank_dev(d_iq, nbytes, first, ns, bs, d_rows, rows, d_c, n_ch, taps, d_o)
-            assert e.value.status == status, (first, ns, bs, rows, n_ch, taps, e.value)
-            dev.synchronize()
-            assert np.all(out.download(np.uint8) == SENTINEL), (first, ns, bs, rows, n_ch, taps)
+        for c in cases:                                      # nothing written behind each one of them
+            refused(dev, dev.corr_bank_dev, [(c[:-1], c[-1])], out)
         # channel fields live in device memory: the library cannot refuse them with a status, so the launch writes nothing
         bad = [(0, 1, 0, 0, 0, 1), (0, 1, 0, 0, 4, 0), (0, 1, 0, 0, -1, 0), (cr.PERIOD, 1, 0, 0, 0, 0), (0, 2 ** 34, 0, 0, 0, 0)]
         for ch in bad:
@@ -182,7 +159,7 @@ def test_refusals_enqueue_nothing(dev, cap, d_codes):
                 d_ch.upload(np.array(table, gpsjam.CORR_CHANNEL_DTYPE))
                 dev.corr_bank_dev(cap, cap.nbytes, 0, n, B, d_codes, 4, d_ch, 3, T, out)
                 dev.synchronize()
-                assert np.all(out.download(np.uint8) == SENTINEL), (ch, at)
+                out.check_untouched(f"channel {ch} at {at}")
             # ... and the wrapper checks them on the host, before anything is uploaded
             with pytest.raises(gpsjam.GpsJamError) as e:
                 dev.corr_bank(cap, channels[:2] + [ch], codes)
@@ -192,10 +169,9 @@ def test_refusals_enqueue_nothing(dev, cap, d_codes):
         dev.corr_bank_dev(cap, cap.nbytes, cap.nsamples - 1, 1, 4096, d_codes, 4, d_ch, 1, (64,), out)
         dev.corr_bank_dev(cap, cap.nbytes, 0, 16, 16, d_codes, 4, d_ch, 1, (-64,), out)
         dev.synchronize()
-        assert np.all(out.download(np.uint8, PAD, size) == SENTINEL)
+        out.check_pads("records")
     finally:
-        out.free()
-        d_ch.free()
+        freed(out, d_ch)
     # the next valid call gives the parity bits, and a library refusal through the wrapper raises and leaves the capture alone
     compare(dev, cap, raw, 7, n + 5, B, d_codes, codes, channels, T)
     with pytest.raises(gpsjam.GpsJamError) as e:

@@ -27,15 +27,12 @@ import csd_restatement as cs
 import gpsjam
 import skurt_restatement as sr
 from gpsjam import coherence
-from skurt import test_round6_gpu as skurt_t
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, PAD, SENTINEL, Guarded, freed, refused, run_sk
+from gpu_lib import run_csd as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind each output
 FA, FB = cs.PARITY_FIRST_A, cs.PARITY_FIRST_B   # 1 and 4
-worst = {"saa": 0.0, "sbb": 0.0, "sab": 0.0, "msc_ulp": 0.0}   # largest errors seen, relative to the tolerance's own reference
 
 
 @pytest.fixture(scope="module")
@@ -44,27 +41,6 @@ def pair(dev):
     yield a, b
     a.free()
     b.free()
-
-
-def run(dev, d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, nfft, hop, m, n_rows, want_msc=True):
-    """(Saa, Sbb, Sab, MSC | None) through gj_csd_dev into sentinel-filled buffers."""
-    cells = n_rows * nfft
-    sizes = (4 * cells, 4 * cells, 8 * cells, 4 * cells)
-    bufs = [dev.alloc(s + PAD) for s in sizes]
-    try:
-        for b in bufs:
-            b.upload(np.full(b.nbytes, SENTINEL, np.uint8))
-        dev.cross_spectrum_dev(d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, nfft, hop, m, n_rows, bufs[0], bufs[1], bufs[2],
-                               bufs[3] if want_msc else None)
-        raw = [b.download(np.uint8) for b in bufs]
-    finally:
-        for b in bufs:
-            b.free()
-    for k, (r, s) in enumerate(zip(raw, sizes)):
-        assert np.all(r[s if (k < 3 or want_msc) else 0:] == SENTINEL), f"output {k}: bytes were written behind the asked-for output"
-    saa, sbb = (raw[k][:sizes[k]].view(np.float32).reshape(n_rows, nfft) for k in (0, 1))
-    sab = raw[2][:sizes[2]].view(np.complex64).reshape(n_rows, nfft)
-    return saa, sbb, sab, (raw[3][:sizes[3]].view(np.float32).reshape(n_rows, nfft) if want_msc else None)
 
 
 def run_pair(dev, pair, nfft, hop, m, n_rows, first_a=FA, first_b=FB, want_msc=True):
@@ -76,39 +52,9 @@ def same(x, y):
     return all((p is None and q is None) or p.tobytes() == q.tobytes() for p, q in zip(x, y))
 
 
-def check_msc(saa, sbb, sab, msc, what):
-    """d_msc against the formula in float64 on the float32 values the call wrote."""
-    want = cs.coherence(saa, sbb, sab)
-    dead = saa.astype(np.float64) * sbb.astype(np.float64) == 0
-    assert np.array_equal(np.isnan(msc), dead), (what, "NaN exactly where Saa * Sbb == 0")
-    live = ~dead
-    if live.any():
-        w32 = want[live].astype(np.float32)
-        ulps = np.abs(msc[live].astype(np.float64) - want[live]) / np.spacing(np.abs(w32)).astype(np.float64)
-        worst["msc_ulp"] = max(worst["msc_ulp"], float(ulps.max()))
-        assert ulps.max() <= 2.0, (what, float(ulps.max()))
-
-
-def compare(got, ref, what):
-    """GPU sums against the restatement's (Saa, Sbb, Sab, MSC) of float64."""
-    saa, sbb, sab, msc = got
-    raa, rbb, rab, _ = ref
-    assert saa.shape == raa.shape == sbb.shape == sab.shape, what
-    ma, mb = raa.max(axis=1, keepdims=True), rbb.max(axis=1, keepdims=True)
-    ea, eb = float(np.max(np.abs(saa - raa) / ma)), float(np.max(np.abs(sbb - rbb) / mb))
-    cross = np.sqrt(ma * mb)
-    eab = float(max(np.max(np.abs(sab.real - rab.real) / cross), np.max(np.abs(sab.imag - rab.imag) / cross)))
-    worst["saa"], worst["sbb"], worst["sab"] = max(worst["saa"], ea), max(worst["sbb"], eb), max(worst["sab"], eab)
-    assert ea <= cs.S1_TOL, (what, "Saa", ea)
-    assert eb <= cs.S1_TOL, (what, "Sbb", eb)
-    assert eab <= cs.S1_TOL, (what, "Sab", eab)
-    if msc is not None:
-        check_msc(saa, sbb, sab, msc, what)
-
-
 def report(head):
-    print(f"{head}: largest errors so far Saa {worst['saa']:.2e}, Sbb {worst['sbb']:.2e}, Sab {worst['sab']:.2e} (tolerance {cs.S1_TOL:.0e}), "
-          f"MSC {worst['msc_ulp']:.2f} ulp (tolerance 2)")
+    print(f"{head}: largest errors so far Saa {cs.worst['saa']:.2e}, Sbb {cs.worst['sbb']:.2e}, Sab {cs.worst['sab']:.2e} (tolerance {cs.S1_TOL:.0e}), "
+          f"MSC {cs.worst['msc_ulp']:.2f} ulp (tolerance 2)")
 
 
 @pytest.mark.parametrize("nfft", cs.NFFT)
@@ -121,7 +67,7 @@ def test_parity_with_the_restatement(dev, pair, nfft):
                 for m in cs.PARITY_M:
                     n_rows = gpsjam.csd_rows(pair[0].nbytes, FA, pair[1].nbytes, FB, nfft, hop, m)
                     assert n_rows == sa.shape[0] // m >= 1
-                    compare(run_pair(dev, pair, nfft, hop, m, n_rows), cs.sums_of(sa, sb, m, n_rows, scale), (nfft, hop, m, offset))
+                    cs.compare(run_pair(dev, pair, nfft, hop, m, n_rows), cs.sums_of(sa, sb, m, n_rows, scale), (nfft, hop, m, offset))
     finally:
         dev.set_unpack()
     assert dev.get_unpack() == (127.5, 1.0 / 127.5)
@@ -136,7 +82,7 @@ def test_block_boundaries(dev, pair, nfft):
     for m in cs.BOUNDARY_M:
         for n_rows in (1, 3):
             assert n_rows <= gpsjam.csd_rows(pair[0].nbytes, FA, pair[1].nbytes, FB, nfft, hop, m)
-            compare(run_pair(dev, pair, nfft, hop, m, n_rows), cs.sums_of(sa, sb, m, n_rows), (nfft, m, n_rows))
+            cs.compare(run_pair(dev, pair, nfft, hop, m, n_rows), cs.sums_of(sa, sb, m, n_rows), (nfft, m, n_rows))
     report(f"nfft {nfft}")
 
 
@@ -150,7 +96,7 @@ def test_workgroups_that_take_more_than_one_step(dev):
     assert nsteps > 2 * cus, f"{nsteps} steps are sized for 256 CUs with two workgroups each, this device has {cus}"
     with dev.capture(a) as ca, dev.capture(b) as cb:
         got = run(dev, ca, ca.nbytes, FA, cb, cb.nbytes, FB, 16, 1, 2, n_rows)
-    compare(got, cs.csd(a, b, 16, 1, 2, FA, FB, n_rows), "M 2 on 2^19 samples")
+    cs.compare(got, cs.csd(a, b, 16, 1, 2, FA, FB, n_rows), "M 2 on 2^19 samples")
     report(f"{nsteps} steps")
 
 
@@ -193,7 +139,7 @@ def test_saa_against_the_kurtosis_s1(dev, pair, nfft):
         for m in cs.PARITY_M:
             n_rows = gpsjam.csd_rows(pair[0].nbytes, FA, pair[1].nbytes, FB, nfft, hop, m)
             saa = run_pair(dev, pair, nfft, hop, m, n_rows)[0]
-            s1 = skurt_t.run(dev, a, a.nbytes, nfft, hop, FA, m, n_rows, want_sk=False)[0]
+            s1 = run_sk(dev, a, a.nbytes, nfft, hop, FA, m, n_rows, want_sk=False)[0]
             err = float(np.max(np.abs(saa.astype(np.float64) - s1) / s1.max(axis=1, keepdims=True)))
             assert err <= cs.S1_TOL, (nfft, hop, m, err)
             identical &= saa.tobytes() == s1.tobytes()
@@ -204,7 +150,7 @@ def test_refusals_enqueue_nothing(dev, pair):
     a, b = pair
     fit = gpsjam.csd_rows(a.nbytes, 0, b.nbytes, 0, 256, 128, 16)
     cells = (fit + 1) * 256
-    saa, sbb, sab, msc = dev.alloc(4 * cells + PAD), dev.alloc(4 * cells + PAD), dev.alloc(8 * cells + PAD), dev.alloc(4 * cells + PAD)
+    saa, sbb, sab, msc = Guarded(dev, 4 * cells), Guarded(dev, 4 * cells), Guarded(dev, 8 * cells), Guarded(dev, 4 * cells)
     outs = (saa, sbb, sab, msc)
     ok = (a, a.nbytes, 0, b, b.nbytes, 0, 256, 128, 16, 4)
 
@@ -240,15 +186,7 @@ def test_refusals_enqueue_nothing(dev, pair):
         (*ok, saa, sbb, sab.ptr + 2, msc, GJ_ERR_INVALID),
     ]
     try:
-        for buf in outs:
-            buf.upload(np.full(buf.nbytes, SENTINEL, np.uint8))
-        for *args, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.cross_spectrum_dev(*args)
-            assert e.value.status == status, (args[1:10], e.value)
-        dev.synchronize()
-        for buf in outs:
-            assert np.all(buf.download(np.uint8) == SENTINEL)
+        refused(dev, dev.cross_spectrum_dev, [(c[:-1], c[-1]) for c in cases], *outs)
         # accepted: M at its smallest, a call that just fits, no d_msc, d_saa only 4-byte aligned
         need = dev.csd_workspace(256, 16, fit)
         assert need == fit * 4 * 256 * 4
@@ -259,9 +197,9 @@ def test_refusals_enqueue_nothing(dev, pair):
         size = 4 * fit * 256
         for buf, s in ((saa, size), (sbb, size), (sab, 2 * size)):
             assert np.all(buf.download(np.uint8, PAD, s) == SENTINEL)
+            buf.check_pads("output")
     finally:
-        for buf in outs:
-            buf.free()
+        freed(*outs)
 
 
 def test_extremes(dev):
@@ -276,7 +214,7 @@ def test_extremes(dev):
                 assert rows >= 1
                 saa, sbb, sab, msc = run(dev, ca, n, 1, cb, n, 2, nfft, nfft // 4, 3, rows)
             assert np.isfinite(saa).all() and np.isfinite(sbb).all() and np.isfinite(sab.real).all() and np.isfinite(sab.imag).all()
-            check_msc(saa, sbb, sab, msc, (nfft, "saturated"))
+            cs.check_msc(saa, sbb, sab, msc, (nfft, "saturated"))
             live = saa.astype(np.float64) * sbb.astype(np.float64) > 0
             assert np.isfinite(msc[live]).all() and live[:, [0, 1, -1]].all()
             np.testing.assert_allclose(msc[:, [0, 1, -1]], 1.0, rtol=1e-5)
@@ -308,7 +246,7 @@ def test_past_byte_2_32(dev, nfft):
     with dev.capture(raw) as small:
         near = run(dev, small, small.nbytes, FA, small, small.nbytes, FB, nfft, hop, m, rows)
     sa, sb = cs.frame_spectra(raw, nfft, hop, FA, 0, rows * m), cs.frame_spectra(raw, nfft, hop, FB, 0, rows * m)
-    compare(near, cs.sums_of(sa, sb, m, rows), (nfft, "the window as a capture of its own"))
+    cs.compare(near, cs.sums_of(sa, sb, m, rows), (nfft, "the window as a capture of its own"))
     big = dev.alloc(BIG)
     try:
         assert big.ptr and big.nbytes == BIG
@@ -327,7 +265,7 @@ def test_device_cross_spectrum_takes_host_bytes_and_captures(dev, pair):
     y = dev.cross_spectrum(ra, rb, nfft=256, hop=256, frames_per_row=64)
     assert (x.nfft, x.hop, x.frames_per_row, x.first_a, x.first_b, len(x)) == (256, 256, 64, 0, 0, 8)
     assert same((x.saa, x.sbb, x.sab, x.msc), (y.saa, y.sbb, y.sab, y.msc)) and dev.last_kernel_ms > 0
-    compare((x.saa, x.sbb, x.sab, x.msc), cs.csd(ra, rb, 256, 256, 64), "Device.cross_spectrum")
+    cs.compare((x.saa, x.sbb, x.sab, x.msc), cs.csd(ra, rb, 256, 256, 64), "Device.cross_spectrum")
     part = dev.cross_spectrum(pair[0], pair[1], nfft=64, hop=100, frames_per_row=5, first_a=5, first_b=2, n_rows=3)
     assert len(part) == 3 and part.sab.shape == (3, 64) and part.sab.dtype == np.complex64
     assert len(dev.cross_spectrum(np.zeros(100, np.uint8), rb)) == 0

@@ -220,3 +220,36 @@ def parity_spectra(nfft, hop, first_a=PARITY_FIRST_A, first_b=PARITY_FIRST_B, of
     sa.setflags(write=False)
     sb.setflags(write=False)
     return sa, sb
+
+
+worst = {"saa": 0.0, "sbb": 0.0, "sab": 0.0, "msc_ulp": 0.0}   # largest errors seen, relative to the tolerance's own reference
+
+
+def check_msc(saa, sbb, sab, msc, what):
+    """d_msc against the formula in float64 on the float32 values the call wrote."""
+    want = coherence(saa, sbb, sab)
+    dead = saa.astype(np.float64) * sbb.astype(np.float64) == 0
+    assert np.array_equal(np.isnan(msc), dead), (what, "NaN exactly where Saa * Sbb == 0")
+    live = ~dead
+    if live.any():
+        w32 = want[live].astype(np.float32)
+        ulps = np.abs(msc[live].astype(np.float64) - want[live]) / np.spacing(np.abs(w32)).astype(np.float64)
+        worst["msc_ulp"] = max(worst["msc_ulp"], float(ulps.max()))
+        assert ulps.max() <= 2.0, (what, float(ulps.max()))
+
+
+def compare(got, ref, what):
+    """GPU sums against the restatement's (Saa, Sbb, Sab, MSC) of float64."""
+    saa, sbb, sab, msc = got
+    raa, rbb, rab, _ = ref
+    assert saa.shape == raa.shape == sbb.shape == sab.shape, what
+    ma, mb = raa.max(axis=1, keepdims=True), rbb.max(axis=1, keepdims=True)
+    ea, eb = float(np.max(np.abs(saa - raa) / ma)), float(np.max(np.abs(sbb - rbb) / mb))
+    cross = np.sqrt(ma * mb)
+    eab = float(max(np.max(np.abs(sab.real - rab.real) / cross), np.max(np.abs(sab.imag - rab.imag) / cross)))
+    worst["saa"], worst["sbb"], worst["sab"] = max(worst["saa"], ea), max(worst["sbb"], eb), max(worst["sab"], eab)
+    assert ea <= S1_TOL, (what, "Saa", ea)
+    assert eb <= S1_TOL, (what, "Sbb", eb)
+    assert eab <= S1_TOL, (what, "Sab", eab)
+    if msc is not None:
+        check_msc(saa, sbb, sab, msc, what)

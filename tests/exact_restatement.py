@@ -100,3 +100,18 @@ def xcorr_f64(sig1: np.ndarray, sig0: np.ndarray):
     c[k] = -1.0
     runner_up = max(float(c.max()), 0.0) if c.size > 1 else 0.0
     return k - (np.asarray(sig0).size - 1), peak, runner_up
+
+
+NOISE, WINDOW, FACTOR = 200000, 1000, 50.0       # the K4 arguments of tests/test_round6_gpu.py
+ONSET_T = np.dtype([("start", "<i8"), ("noise", "<f4"), ("thr", "<f4"), ("hit", "<f4"), ("before", "<f4"), ("guard", "<i8")])
+AMP_T = np.dtype([("i", "<i8"), ("c", "<u8"), ("s", "<f8"), ("m", "<f4"), ("r", "<f4")])
+
+
+def check_exact(amp_bytes, on_bytes, raw, thr, noise=NOISE, window=WINDOW):
+    a, o = np.frombuffer(amp_bytes, AMP_T)[0], np.frombuffer(on_bytes, ONSET_T)[0]
+    want_a, want_o = amp_stats(raw, thr), onset(raw, noise, window, FACTOR)
+    assert (a["i"], a["c"]) == (want_a["first"], want_a["count"])
+    np.testing.assert_allclose(a["s"], want_a["sum"], rtol=2e-7)
+    np.testing.assert_allclose(a["m"], want_a["mean"], rtol=2e-7)
+    for f in ("start", "guard", "noise", "thr", "hit"):
+        assert o[f] == want_o[f], (f, o, want_o)

@@ -16,14 +16,12 @@ import pytest
 import excise_restatement as er
 import gpsjam
 from gpsjam import gnss, mitigate
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, Resident, freed, refused
+from gpu_lib import run_excise as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
 REC = gpsjam.EXCISE_DTYPE.itemsize
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind d_out[2 n_samples] and behind d_frames[F]
-RTOL = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -33,64 +31,11 @@ def cap(dev):
     c.free()
 
 
-class Thr:
-    """Thresholds resident once per (values)."""
-
-    def __init__(self, dev):
-        self.dev, self.bufs = dev, {}
-
-    def __call__(self, values):
-        values = np.ascontiguousarray(values, np.float32)
-        key = values.tobytes()
-        if key not in self.bufs:
-            self.bufs[key] = self.dev.alloc(values.nbytes).upload(values)
-        return self.bufs[key]
-
-    def free(self):
-        for b in self.bufs.values():
-            b.free()
-
-
 @pytest.fixture(scope="module")
 def thr(dev):
-    t = Thr(dev)
+    t = Resident(dev)
     yield t
     t.free()
-
-
-def run(dev, d_iq, nbytes, first, n_samples, nfft, d_thr, want_frames=True):
-    """(bytes[2 n_samples], records[F]) through gj_excise_dev into sentinel-filled buffers."""
-    nf = gpsjam.excise_frames(n_samples, nfft)
-    out, rec = dev.alloc(2 * n_samples + PAD), dev.alloc(nf * REC + PAD)
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
-        dev.excise_dev(d_iq, nbytes, first, n_samples, nfft, d_thr, out, rec if want_frames else None)
-        got, raw = out.download(np.uint8), rec.download(np.uint8)
-    finally:
-        out.free()
-        rec.free()
-    assert np.all(got[2 * n_samples:] == SENTINEL), "bytes were written behind d_out[2 n_samples]"
-    assert np.all(raw[(nf * REC if want_frames else 0):] == SENTINEL), "records were written behind d_frames[F]"
-    return got[:2 * n_samples], raw[:nf * REC].view(gpsjam.EXCISE_DTYPE)
-
-
-def compare(got, rec, want, what):
-    """GPU bytes and records against an er.Excised."""
-    assert rec.size == want.records.size and got.size == want.out.size, what
-    np.testing.assert_array_equal(rec["n_excised"], want.records["n_excised"], err_msg=str(what))
-    assert not rec["reserved"].any()
-    tot = want.records["total"]
-    for key in ("total", "removed"):
-        err = float(np.max(np.abs(rec[key] - want.records[key]) / tot))
-        assert err <= RTOL, (what, key, err)
-    assert np.array_equal(got[:want.lo], want.out[:want.lo]) and np.array_equal(got[want.hi:], want.out[want.hi:]), (what, "edges")
-    body, ref = got[want.lo:want.hi].astype(np.int16), want.out[want.lo:want.hi].astype(np.int16)
-    clear = er.tie_distance(want.value) > er.TIE_BAND
-    diff = np.abs(body - ref)
-    print(f"{what}: {int(np.sum(diff != 0))} of {diff.size} bytes differ, {int(np.sum(~clear))} lie in the tie band")
-    assert not diff[clear].any(), (what, int(np.sum(diff[clear] != 0)), "bytes differ outside the tie band")
-    assert diff.max(initial=0) <= 1, (what, int(diff.max()))
 
 
 @pytest.mark.parametrize("nfft", er.NFFT)
@@ -114,7 +59,7 @@ def test_parity_with_the_restatement(dev, cap, thr, nfft):
             dev.set_unpack(offset, scale)
             want = er.parity_reference(nfft, offset, scale)
             got, rec = run(dev, cap, cap.nbytes, er.PARITY_FIRST, cap.nsamples - er.PARITY_FIRST, nfft, thr(er.parity_threshold(nfft, scale)))
-            compare(got, rec, want, (nfft, offset))
+            er.compare(got, rec, want, (nfft, offset))
     finally:
         dev.set_unpack()
     assert dev.get_unpack() == (127.5, 1.0 / 127.5)
@@ -190,16 +135,14 @@ def test_overshoot_is_clamped_not_wrapped(dev, thr, nfft):
     body = got[want.lo:want.hi]
     assert np.all(body[want.value > 256.0] == 255) and np.all(body[want.value < -1.0] == 0)
     assert np.sum(body == 255) > body.size // 20 and np.sum(body == 0) > body.size // 20
-    compare(got, rec, want, ("clamp", nfft))
+    er.compare(got, rec, want, ("clamp", nfft))
 
 
 def test_refusals_enqueue_nothing(dev, cap, thr):
     n = 8 * 256
     t256, t16 = thr(np.full(256, -1.0)), thr(np.full(16, -1.0))
-    out, rec = dev.alloc(cap.nbytes + PAD), dev.alloc(4096 * REC + PAD)
+    out, rec = Guarded(dev, cap.nbytes), Guarded(dev, 4096 * REC)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
         cases = [  # d_iq, nbytes, first, n_samples, nfft, d_thr, d_out, d_frames, status
             (cap, cap.nbytes, 0, n, 8, t256, out, rec, GJ_ERR_UNSUPPORTED),
             (cap, cap.nbytes, 0, 3 * 8192, 8192, t256, out, rec, GJ_ERR_UNSUPPORTED),
@@ -222,21 +165,16 @@ def test_refusals_enqueue_nothing(dev, cap, thr):
             (out, cap.nbytes, 0, n, 256, t256, out.ptr + cap.nbytes - 1, rec, GJ_ERR_INVALID),
             (out.ptr + 512, 1024, 0, 256, 256, t256, out.ptr + 1, rec, GJ_ERR_INVALID),
         ]
-        for d_iq, nbytes, first, ns, nfft, d_thr, d_out, d_rec, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.excise_dev(d_iq, nbytes, first, ns, nfft, d_thr, d_out, d_rec)
-            assert e.value.status == status, (nbytes, first, ns, nfft, e.value)
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL)
+        refused(dev, dev.excise_dev, [(c[:-1], c[-1]) for c in cases], out, rec)
         # accepted: a call that just fits (the whole capture; the output right behind the input's last byte), 16 points
         dev.excise_dev(cap, cap.nbytes, 0, cap.nsamples, 256, t256, out, rec)
         dev.excise_dev(out, 2 * n, 0, n, 256, t256, out.ptr + 2 * n, None)
         dev.excise_dev(cap, cap.nbytes, cap.nsamples - 16, 16, 16, t16, out, rec)
         dev.synchronize()
-        assert np.all(out.download(np.uint8, PAD, cap.nbytes) == SENTINEL)
+        out.check_pads("output")
+        rec.check_pads("records")
     finally:
-        out.free()
-        rec.free()
+        freed(out, rec)
 
 
 def test_device_excise_and_mitigate_clean(dev, cap):
@@ -250,7 +188,7 @@ def test_device_excise_and_mitigate_clean(dev, cap):
     try:
         assert isinstance(a, gpsjam.Capture) and a.nbytes == cap.nbytes and a.ptr != cap.ptr
         assert a.download().tobytes() == b.download().tobytes() and rec_a.tobytes() == rec_b.tobytes()
-        compare(a.download(), rec_a, want, "Device.excise")
+        er.compare(a.download(), rec_a, want, "Device.excise")
         part, rec_p = dev.excise(cap, er.parity_threshold(nfft), nfft=nfft, first_sample=128 * 3, n_samples=5000)
         assert part.nbytes == 10000 and rec_p.tobytes() == rec_a[3:3 + rec_p.size].tobytes()
         part.free()

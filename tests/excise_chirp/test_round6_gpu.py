@@ -16,33 +16,14 @@ import excise_chirp_restatement as xr
 import excise_restatement as er
 import gpsjam
 from gpsjam import gnss, mitigate
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, Resident, freed, refused
+from gpu_lib import run_excise_chirp as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
 REC = gpsjam.EXCISE_DTYPE.itemsize
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind d_out[2 n_samples] and behind d_frames[F]
 EXACT_NFFT = (16, 64, 1024, 2048, 4096)         # rate 0 against gj_excise_dev
 SHIFT_NFFT = (64, 1024, 2048, 4096)             # translation and repetition
-
-
-class Resident:
-    """Arrays resident once per (dtype, values)."""
-
-    def __init__(self, dev):
-        self.dev, self.bufs = dev, {}
-
-    def __call__(self, values, dtype=np.float32):
-        values = np.ascontiguousarray(values, dtype)
-        key = (np.dtype(dtype).str, values.tobytes())
-        if key not in self.bufs:
-            self.bufs[key] = self.dev.alloc(max(values.nbytes, 4)).upload(values)
-        return self.bufs[key]
-
-    def free(self):
-        for b in self.bufs.values():
-            b.free()
 
 
 @pytest.fixture(scope="module")
@@ -65,47 +46,6 @@ def caps(dev):
         c.free()
 
 
-def run(dev, d_iq, nbytes, first, n_samples, nfft, d_rate, d_thr, want_frames=True, plain=False):
-    """(bytes[2 n_samples], records[F]) through gj_excise_chirp_dev (plain: gj_excise_dev) into sentinel-filled buffers."""
-    nf = gpsjam.excise_frames(n_samples, nfft)
-    out, rec = dev.alloc(2 * n_samples + PAD), dev.alloc(nf * REC + PAD)
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
-        if plain:
-            dev.excise_dev(d_iq, nbytes, first, n_samples, nfft, d_thr, out, rec if want_frames else None)
-        else:
-            dev.excise_chirp_dev(d_iq, nbytes, first, n_samples, nfft, d_rate, d_thr, out, rec if want_frames else None)
-        got, raw = out.download(np.uint8), rec.download(np.uint8)
-    finally:
-        out.free()
-        rec.free()
-    assert np.all(got[2 * n_samples:] == SENTINEL), "bytes were written behind d_out[2 n_samples]"
-    assert np.all(raw[(nf * REC if want_frames else 0):] == SENTINEL), "records were written behind d_frames[F]"
-    return got[:2 * n_samples], raw[:nf * REC].view(gpsjam.EXCISE_DTYPE)
-
-
-def compare(got, rec, want, what):
-    """GPU bytes and records against an er.Excised."""
-    assert rec.size == want.records.size and got.size == want.out.size, what
-    np.testing.assert_array_equal(rec["n_excised"], want.records["n_excised"], err_msg=str(what))
-    assert not rec["reserved"].any()
-    tot = want.records["total"]
-    for key in ("total", "removed"):
-        err = float(np.max(np.abs(rec[key] - want.records[key]) / tot))
-        print(f"{what}: {key} within {err:.2e}")
-        assert err <= xr.RTOL, (what, key, err)
-    assert np.array_equal(got[:want.lo], want.out[:want.lo]) and np.array_equal(got[want.hi:], want.out[want.hi:]), (what, "edges")
-    body, ref = got[want.lo:want.hi].astype(np.int16), want.out[want.lo:want.hi].astype(np.int16)
-    clear = er.tie_distance(want.value) > xr.TIE_BAND
-    diff = np.abs(body - ref)
-    share = float(np.mean(~clear))
-    print(f"{what}: {int(np.sum(diff != 0))} of {diff.size} bytes differ, {int(np.sum(~clear))} lie in the tie band ({share:.2e})")
-    assert share <= xr.TIE_SHARE_CAP, (what, share)
-    assert not diff[clear].any(), (what, int(np.sum(diff[clear] != 0)), "bytes differ outside the tie band")
-    assert diff.max(initial=0) <= 1, (what, int(diff.max()))
-
-
 @pytest.mark.parametrize("nfft", xr.NFFT)
 def test_parity_with_the_restatement(dev, caps, res, nfft):
     cap = caps(nfft)
@@ -116,7 +56,7 @@ def test_parity_with_the_restatement(dev, caps, res, nfft):
             want = xr.parity_reference(nfft, offset, scale)
             got, rec = run(dev, cap, cap.nbytes, xr.PARITY_FIRST, cap.nsamples - xr.PARITY_FIRST, nfft, d_rate,
                            res(xr.parity_threshold(nfft, scale)))
-            compare(got, rec, want, (nfft, offset))
+            xr.compare(got, rec, want, (nfft, offset))
     finally:
         dev.set_unpack()
     assert dev.get_unpack() == (127.5, 1.0 / 127.5)
@@ -218,10 +158,8 @@ def test_refusals_enqueue_nothing(dev, caps, res):
     n = 8 * 256
     t256, t16 = res(np.full(256, -1.0)), res(np.full(16, -1.0))
     rt = res(np.arange(4096) % 7, np.int32)
-    out, rec = dev.alloc(cap.nbytes + PAD), dev.alloc(4096 * REC + PAD)
+    out, rec = Guarded(dev, cap.nbytes), Guarded(dev, 4096 * REC)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
         cases = [  # d_iq, nbytes, first, n_samples, nfft, d_rate, d_thr, d_out, d_frames, status
             (cap, cap.nbytes, 0, n, 8, rt, t256, out, rec, GJ_ERR_UNSUPPORTED),
             (cap, cap.nbytes, 0, 3 * 8192, 8192, rt, t256, out, rec, GJ_ERR_UNSUPPORTED),
@@ -247,44 +185,34 @@ def test_refusals_enqueue_nothing(dev, caps, res):
             (out, cap.nbytes, 0, n, 256, rt, t256, out.ptr + cap.nbytes - 1, rec, GJ_ERR_INVALID),
             (out.ptr + 512, 1024, 0, 256, 256, rt, t256, out.ptr + 1, rec, GJ_ERR_INVALID),
         ]
-        for d_iq, nbytes, first, ns, nfft, d_rate, d_thr, d_out, d_rec, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.excise_chirp_dev(d_iq, nbytes, first, ns, nfft, d_rate, d_thr, d_out, d_rec)
-            assert e.value.status == status, (nbytes, first, ns, nfft, e.value)
+        refused(dev, dev.excise_chirp_dev, [(c[:-1], c[-1]) for c in cases], out, rec)
         # the picker: d_scan, n_frames, rate_first, rate_step, min_concentration, d_rate (the record buffer stands in for both)
-        for d_scan, nf, first, step, minc, d_rate in ((0, 8, 0, 1, 0.1, out), (rec, 8, 0, 1, 0.1, 0), (rec.ptr + 2, 8, 0, 1, 0.1, out),
-                                                      (rec, 8, 0, 1, 0.1, out.ptr + 2), (rec, 0, 0, 1, 0.1, out), (rec, 8, 0, 0, 0.1, out),
-                                                      (rec, 8, 0, -1, 0.1, out)):
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.chirp_rates_dev(d_scan, nf, first, step, minc, d_rate)
-            assert e.value.status == GJ_ERR_INVALID, (nf, step, e.value)
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL)
+        picks = ((0, 8, 0, 1, 0.1, out), (rec, 8, 0, 1, 0.1, 0), (rec.ptr + 2, 8, 0, 1, 0.1, out),
+                 (rec, 8, 0, 1, 0.1, out.ptr + 2), (rec, 0, 0, 1, 0.1, out), (rec, 8, 0, 0, 0.1, out),
+                 (rec, 8, 0, -1, 0.1, out))
+        refused(dev, dev.chirp_rates_dev, [(c, GJ_ERR_INVALID) for c in picks], out, rec)
         # accepted: a call that just fits (the whole capture; the output right behind the input's last byte), 16 points
         dev.excise_chirp_dev(cap, cap.nbytes, 0, cap.nsamples, 256, rt, t256, out, rec)
         dev.excise_chirp_dev(out, 2 * n, 0, n, 256, rt, t256, out.ptr + 2 * n, None)
         dev.excise_chirp_dev(cap, cap.nbytes, cap.nsamples - 16, 16, 16, rt, t16, out, rec)
         dev.synchronize()
-        assert np.all(out.download(np.uint8, PAD, cap.nbytes) == SENTINEL)
+        out.check_pads("output")
+        rec.check_pads("records")
     finally:
-        out.free()
-        rec.free()
+        freed(out, rec)
 
 
 def pick(dev, records, rate_first, rate_step, minc):
     """gj_chirp_rates_dev on host records, into a sentinel-filled buffer."""
     records = np.ascontiguousarray(records, gpsjam.CHIRP_DTYPE)
-    scan, out = dev.alloc(records.nbytes), dev.alloc(4 * records.size + PAD)
+    scan, out = dev.alloc(records.nbytes), Guarded(dev, 4 * records.size)
     try:
         scan.upload(records)
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
         dev.chirp_rates_dev(scan, records.size, rate_first, rate_step, minc, out)
-        got = out.download(np.uint8)
+        out.check_pads("rates")
+        return out.read(np.int32)
     finally:
-        scan.free()
-        out.free()
-    assert np.all(got[4 * records.size:] == SENTINEL)
-    return got[:4 * records.size].view(np.int32)
+        freed(scan, out)
 
 
 def test_rate_picker_gives_the_restatements_integers(dev, caps):
@@ -345,7 +273,7 @@ def test_device_excise_chirp(dev, caps):
         assert dev.kernel_calls["excise_chirp"] == calls + 2
         assert isinstance(a, gpsjam.Capture) and a.nbytes == cap.nbytes and a.ptr != cap.ptr
         assert a.download().tobytes() == b.download().tobytes() and rec_a.tobytes() == rec_b.tobytes()
-        compare(a.download(), rec_a, want, "Device.excise_chirp")
+        xr.compare(a.download(), rec_a, want, "Device.excise_chirp")
         part, rec_p = dev.excise_chirp(cap, thr, rates[3:3 + gpsjam.excise_frames(5000, nfft)], nfft=nfft, first_sample=128 * 3,
                                        n_samples=5000)
         assert part.nbytes == 10000 and rec_p.tobytes() == rec_a[3:3 + rec_p.size].tobytes()

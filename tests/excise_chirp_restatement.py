@@ -239,3 +239,24 @@ def e2e_flat_threshold(nfft=E2E_NFFT, scale=1.0 / 127.5):
     """What clean_swept applies: flat, the nominal floor of sigma = 10 noise times 12 dB (the measured median of the
     quiet part's floor is within a few percent of it)."""
     return np.full(nfft, er.noise_floor(nfft, er.E2E_SIGMA, scale) * 10.0 ** (er.E2E_RISE_DB / 10.0), np.float32)
+
+
+def compare(got, rec, want, what):
+    """GPU bytes and records against an er.Excised."""
+    assert rec.size == want.records.size and got.size == want.out.size, what
+    np.testing.assert_array_equal(rec["n_excised"], want.records["n_excised"], err_msg=str(what))
+    assert not rec["reserved"].any()
+    tot = want.records["total"]
+    for key in ("total", "removed"):
+        err = float(np.max(np.abs(rec[key] - want.records[key]) / tot))
+        print(f"{what}: {key} within {err:.2e}")
+        assert err <= RTOL, (what, key, err)
+    assert np.array_equal(got[:want.lo], want.out[:want.lo]) and np.array_equal(got[want.hi:], want.out[want.hi:]), (what, "edges")
+    body, ref = got[want.lo:want.hi].astype(np.int16), want.out[want.lo:want.hi].astype(np.int16)
+    clear = er.tie_distance(want.value) > TIE_BAND
+    diff = np.abs(body - ref)
+    share = float(np.mean(~clear))
+    print(f"{what}: {int(np.sum(diff != 0))} of {diff.size} bytes differ, {int(np.sum(~clear))} lie in the tie band ({share:.2e})")
+    assert share <= TIE_SHARE_CAP, (what, share)
+    assert not diff[clear].any(), (what, int(np.sum(diff[clear] != 0)), "bytes differ outside the tie band")
+    assert diff.max(initial=0) <= 1, (what, int(diff.max()))

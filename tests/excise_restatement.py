@@ -221,3 +221,24 @@ def e2e_capture(jammer="tone"):
     raw = (np.clip(np.round(iq), -128, 127) + 128).astype(np.uint8)
     raw.setflags(write=False)
     return raw
+
+
+RTOL = 1e-5                                     # of total: the project's figure for a K2 value summed in another order
+
+
+def compare(got, rec, want, what):
+    """GPU bytes and records against an Excised."""
+    assert rec.size == want.records.size and got.size == want.out.size, what
+    np.testing.assert_array_equal(rec["n_excised"], want.records["n_excised"], err_msg=str(what))
+    assert not rec["reserved"].any()
+    tot = want.records["total"]
+    for key in ("total", "removed"):
+        err = float(np.max(np.abs(rec[key] - want.records[key]) / tot))
+        assert err <= RTOL, (what, key, err)
+    assert np.array_equal(got[:want.lo], want.out[:want.lo]) and np.array_equal(got[want.hi:], want.out[want.hi:]), (what, "edges")
+    body, ref = got[want.lo:want.hi].astype(np.int16), want.out[want.lo:want.hi].astype(np.int16)
+    clear = tie_distance(want.value) > TIE_BAND
+    diff = np.abs(body - ref)
+    print(f"{what}: {int(np.sum(diff != 0))} of {diff.size} bytes differ, {int(np.sum(~clear))} lie in the tie band")
+    assert not diff[clear].any(), (what, int(np.sum(diff[clear] != 0)), "bytes differ outside the tie band")
+    assert diff.max(initial=0) <= 1, (what, int(diff.max()))

@@ -23,16 +23,12 @@ import extremes_inputs as xi
 import gpsjam
 import ridge_restatement as rr
 import skurt_restatement as sr
-from chirp import test_round6_gpu as chirp_t
-from excise import test_round6_gpu as excise_t
-from excise_chirp import test_round6_gpu as xchirp_t
-from ridge import test_round6_gpu as ridge_t
-from skurt import test_round6_gpu as skurt_t
+from gpu_lib import Convention, Resident, run_chirp, run_excise, run_excise_chirp, run_ridge, run_sk
 
 pytestmark = pytest.mark.gpu
 
 RTOL = cr.RTOL
-assert RTOL == ridge_t.RTOL == 1e-5
+assert RTOL == rr.RTOL == 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -47,20 +43,6 @@ def caps(dev):
     yield get
     for c in held.values():
         c.free()
-
-
-class Convention:
-    """offset and scale for the body, the default convention afterwards."""
-
-    def __init__(self, dev, offset, scale):
-        self.dev, self.offset, self.scale = dev, offset, scale
-
-    def __enter__(self):
-        self.dev.set_unpack(self.offset, self.scale)
-
-    def __exit__(self, *exc):
-        self.dev.set_unpack()
-        assert self.dev.get_unpack() == (127.5, 1.0 / 127.5)
 
 
 def within(got, want, scale, what):
@@ -95,7 +77,7 @@ def test_ridge(dev, caps, name, nfft):
                 tied = xi.ridge_not_clear(name, nfft, hop, offset, scale)
                 clear = margin >= rr.NEAR_TIE
                 what = (name, nfft, hop, offset)
-                got = ridge_t.run(dev, cap, cap.nbytes, nfft, hop, xi.FIRST, rec.size, xi.GUARD)
+                got = run_ridge(dev, cap, cap.nbytes, nfft, hop, xi.FIRST, rec.size, xi.GUARD)
                 compare_records(got, rec, clear, what)
                 for f in tied:                               # the GPU's bin is one of the tied ones
                     p = xi.frame_spectrum(name, nfft, xi.FIRST + int(f) * hop, offset, scale)
@@ -121,7 +103,7 @@ def test_chirp(dev, caps, name, nfft):
                     clear = np.ones(rec.size, bool)
                     clear[tied] = False
                     what = (name, nfft, hop, rates, offset)
-                    got, peaks = chirp_t.run(dev, cap, cap.nbytes, nfft, hop, xi.FIRST, rec.size, rates, xi.GUARD)
+                    got, peaks = run_chirp(dev, cap, cap.nbytes, nfft, hop, xi.FIRST, rec.size, rates, xi.GUARD)
                     compare_records(got, rec, clear, what)
                     np.testing.assert_array_equal(got["rate_index"][clear], rec["rate_index"][clear], err_msg=str(what))
                     within(peaks, want.peaks, want.peaks, (what, "peaks"))
@@ -152,19 +134,19 @@ def test_kurtosis(dev, caps, name, nfft):
                 n_rows = gpsjam.sk_rows(cap.nbytes, xi.FIRST, nfft, hop, m)
                 assert n_rows == p.shape[0] // m >= 1
                 r1, r2, _ = sr.sums_of(p, m, n_rows)
-                s1, s2, skv = skurt_t.run(dev, cap, cap.nbytes, nfft, hop, xi.FIRST, m, n_rows)
+                s1, s2, skv = run_sk(dev, cap, cap.nbytes, nfft, hop, xi.FIRST, m, n_rows)
                 what = (name, nfft, hop, m, offset)
                 # sr.S1_TOL and sr.S2_TOL of the row's largest reference value; a row without power is 0
                 assert np.all(np.abs(s1 - r1) <= sr.S1_TOL * r1.max(axis=1, keepdims=True)), (what, "S1")
                 assert np.all(np.abs(s2 - r2) <= sr.S2_TOL * r2.max(axis=1, keepdims=True)), (what, "S2")
                 assert np.all(np.isfinite(s1)) and np.all(np.isfinite(s2)), what
-                skurt_t.check_sk(s1, s2, skv, m, what)       # NaN exactly where the GPU's own S1 is 0
+                sr.check_sk(s1, s2, skv, m, what)       # NaN exactly where the GPU's own S1 is 0
 
 
 # ------------------------------------------------------------------------------------------------ 4. excisors
 @pytest.fixture(scope="module")
 def res(dev):
-    r = xchirp_t.Resident(dev)
+    r = Resident(dev)
     yield r
     r.free()
 
@@ -181,8 +163,8 @@ def test_excisors_identity_is_byte_exact(dev, caps, res, name, nfft):
     inf = res(np.full(nfft, np.inf))
     for offset, scale in xi.CONVENTIONS:
         with Convention(dev, offset, scale):
-            runs = [("plain", excise_t.run(dev, cap, cap.nbytes, xi.FIRST, n, nfft, inf))]
-            runs += [(q, xchirp_t.run(dev, cap, cap.nbytes, xi.FIRST, n, nfft, res(np.full(nf, q), np.int32), inf))
+            runs = [("plain", run_excise(dev, cap, cap.nbytes, xi.FIRST, n, nfft, inf))]
+            runs += [(q, run_excise_chirp(dev, cap, cap.nbytes, xi.FIRST, n, nfft, res(np.full(nf, q), np.int32), inf))
                      for q in xi.chirp_identity_rates(nfft)]
             want = xi.notch_reference(name, nfft, offset, scale).records["total"]     # the totals do not depend on the threshold
             for kind, (got, rec) in runs:
@@ -222,7 +204,7 @@ def test_excisor_notches(dev, caps, res, name, nfft, offset, scale):
     thr = er.parity_threshold(nfft, scale)
     want = xi.notch_reference(name, nfft, offset, scale)
     with Convention(dev, offset, scale):
-        got, rec = excise_t.run(dev, cap, cap.nbytes, xi.FIRST, cap.nsamples - xi.FIRST, nfft, res(thr))
+        got, rec = run_excise(dev, cap, cap.nbytes, xi.FIRST, cap.nsamples - xi.FIRST, nfft, res(thr))
     compare_notched(got, rec, want, thr, (name, nfft, offset))
 
 
@@ -233,7 +215,7 @@ def test_chirp_excisor_notches(dev, caps, res, name, nfft, offset, scale):
     thr = er.parity_threshold(nfft, scale)
     want = xi.chirp_notch_reference(name, nfft, offset, scale)
     with Convention(dev, offset, scale):
-        got, rec = xchirp_t.run(dev, cap, cap.nbytes, xi.FIRST, cap.nsamples - xi.FIRST, nfft, res(xi.chirp_notch_rates(nfft), np.int32), res(thr))
+        got, rec = run_excise_chirp(dev, cap, cap.nbytes, xi.FIRST, cap.nsamples - xi.FIRST, nfft, res(xi.chirp_notch_rates(nfft), np.int32), res(thr))
     compare_notched(got, rec, want, thr, ("chirp excisor", name, nfft, offset))
 
 
@@ -244,6 +226,6 @@ def test_excisor_clamps_at_both_ends(dev, res, nfft):
     want = xi.clamp_reference(nfft)
     assert want.value.max() > 255.5 and want.value.min() < -0.5
     with dev.capture(raw) as cap:
-        got, rec = excise_t.run(dev, cap, cap.nbytes, xi.FIRST, cap.nsamples - xi.FIRST, nfft, res(thr))
+        got, rec = run_excise(dev, cap, cap.nbytes, xi.FIRST, cap.nsamples - xi.FIRST, nfft, res(thr))
     compare_notched(got, rec, want, thr, ("clamp", nfft))
     assert (got == 0).any() and (got == 255).any()

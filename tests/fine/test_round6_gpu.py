@@ -24,12 +24,11 @@ import fine_restatement as fr
 import gpsjam
 import k5_check
 from gpsjam import tdoa
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, freed, refused
+from gpu_lib import run_fine as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind d_total and behind d_blocks
 
 
 @pytest.fixture(scope="module")
@@ -38,24 +37,6 @@ def caps(dev):
     yield a, b
     a.free()
     b.free()
-
-
-def run(dev, a, b, first_a, first_b, n, centre, half, want_blocks=True, nbytes_a=None, nbytes_b=None):
-    """(total int64[2R+1][2], blocks int32[nb][2R+1][2] or None) through gj_xcorr_fine_dev into sentinel-filled buffers."""
-    nl, nb = 2 * half + 1, gpsjam.fine_blocks(n)
-    tot, rec = dev.alloc(16 * nl + PAD), dev.alloc(8 * nl * nb + PAD)
-    try:
-        tot.upload(np.full(tot.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
-        dev.xcorr_fine_dev(a, a.nbytes if nbytes_a is None else nbytes_a, first_a, b, b.nbytes if nbytes_b is None else nbytes_b,
-                           first_b, n, centre, half, tot, rec if want_blocks else None)
-        t, r = tot.download(np.uint8), rec.download(np.uint8)
-    finally:
-        tot.free()
-        rec.free()
-    assert np.all(t[16 * nl:] == SENTINEL), "bytes were written behind d_total"
-    assert np.all(r[(8 * nl * nb if want_blocks else 0):] == SENTINEL), "records were written behind d_blocks"
-    return t[:16 * nl].view(np.int64).reshape(nl, 2), (r[:8 * nl * nb].view(np.int32).reshape(nb, nl, 2) if want_blocks else None)
 
 
 def compare(got, want, what):
@@ -213,10 +194,8 @@ def test_end_to_end_refine_on_a_resident_pair(dev):
 def test_refusals_enqueue_nothing(dev, caps):
     a, b = caps
     n, nl = 3 * 4096, 33
-    tot, rec = dev.alloc(16 * 65 + PAD), dev.alloc(8 * 65 * 4 + PAD)
+    tot, rec = Guarded(dev, 16 * 65), Guarded(dev, 8 * 65 * 4)
     try:
-        tot.upload(np.full(tot.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
         I, U = GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
         cases = [  # d_a, nbytes_a, first_a, d_b, nbytes_b, first_b, n, centre, half, d_total, d_blocks, status
             (a, a.nbytes, 0, b, b.nbytes, 0, 0, 0, 16, tot, rec, I),                          # n_samples == 0
@@ -237,21 +216,17 @@ def test_refusals_enqueue_nothing(dev, caps):
             (a, a.nbytes, 0, b, b.nbytes, 0, n, 0, -1, tot, rec, U),
             (a, a.nbytes, 0, b, b.nbytes, 0, n, 0, 33, tot, rec, U),
         ]
-        for d_a, nba, fa, d_b, nbb, fb, ns, centre, half, d_t, d_r, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.xcorr_fine_dev(d_a, nba, fa, d_b, nbb, fb, ns, centre, half, d_t, d_r)
-            assert e.value.status == status, (fa, fb, ns, centre, half, e.value)
-            dev.synchronize()
-            assert np.all(tot.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL), (fa, fb, ns, centre, half)
+        for c in cases:                                      # nothing written behind each one of them
+            refused(dev, dev.xcorr_fine_dev, [(c[:-1], c[-1])], tot, rec)
         # accepted: the limits of the lag (no overlap: zeros), the whole captures, one sample
         dev.xcorr_fine_dev(a, a.nbytes, 0, b, b.nbytes, 0, n, 2 ** 31 - 1 - 16, 16, tot, rec)
         dev.xcorr_fine_dev(a, a.nbytes, 0, b, b.nbytes, 0, n, -2 ** 31 + 1, 0, tot, None)
         dev.xcorr_fine_dev(a, a.nbytes, a.nsamples - 1, b, b.nbytes, b.nsamples - 1, 1, 0, 32, tot, rec)
         dev.synchronize()
-        assert np.all(tot.download(np.uint8, PAD, 16 * 65) == SENTINEL) and np.all(rec.download(np.uint8, PAD, 8 * 65 * 4) == SENTINEL)
+        tot.check_pads("totals")
+        rec.check_pads("records")
     finally:
-        tot.free()
-        rec.free()
+        freed(tot, rec)
     # the next valid call gives the parity bits
     compare(run(dev, a, b, fr.PARITY_FIRST_A, fr.PARITY_FIRST_B, fr.PARITY_SAMPLES, 1, nl // 2), fr.parity_reference(1, 16), "after the refusals")
     # the wrapper: a library refusal raises, frees everything and leaves the captures alone

@@ -18,13 +18,17 @@ import gpsjam
 from gpsjam import _ffi
 import floor_restatement as fr
 import result_restatement as rr
+from gpu_lib import GJ_ERR_UNSUPPORTED, SENTINEL, Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256
-SENTINEL = 0xA5
 NOISE, WINDOW, FACTOR = 200000, 1000, 50.0
-GJ_ERR_UNSUPPORTED = -5
+
+
+def payload(g) -> np.ndarray:
+    """What the call wrote into a Guarded buffer; the pads on either side of it must be untouched."""
+    g.check_pads("output")
+    return g.read()
 
 
 def same_bits(got, want) -> bool:
@@ -32,30 +36,6 @@ def same_bits(got, want) -> bool:
     if np.isnan(want):
         return bool(np.isnan(got))
     return got.view(np.uint32) == want.view(np.uint32)
-
-
-class Guarded:
-    """A device buffer of `nbytes` behind and in front of GUARD sentinel bytes, itself filled with the sentinel."""
-
-    def __init__(self, dev, nbytes):
-        self.nbytes = int(nbytes)
-        self.buf = dev.alloc(self.nbytes + 2 * GUARD)
-        self.ptr = self.buf.ptr + GUARD
-        self.fill()
-
-    def fill(self, nbytes=None):
-        self.used = self.nbytes if nbytes is None else int(nbytes)
-        self.buf.upload(np.full(self.used + 2 * GUARD, SENTINEL, np.uint8))
-
-    def read(self) -> np.ndarray:
-        """The payload; the guards on either side of it must be untouched."""
-        raw = self.buf.download(np.uint8, self.used + 2 * GUARD)
-        assert np.all(raw[:GUARD] == SENTINEL), "bytes in front of the buffer were written"
-        assert np.all(raw[GUARD + self.used:] == SENTINEL), "bytes behind the buffer were written"
-        return raw[GUARD:GUARD + self.used]
-
-    def free(self):
-        self.buf.free()
 
 
 # --------------------------------------------------------------------------------------- the floor rule
@@ -71,7 +51,7 @@ class Rule:
         """(stats, mask) of one call with a mask and one without; the two calls' stats are the same bytes."""
         n = pm.size
         self.d_pow.upload(pm)
-        self.mask.fill(n)
+        self.mask.refill(n)
         self.d_st.upload(np.full(16, SENTINEL, np.uint8))
         self.d_st2.upload(np.full(16, SENTINEL, np.uint8))
         self.dev.power_threshold_dev(self.d_pow, n, self.d_st, self.mask.ptr, pct=float(pct), rise_db=float(rise_db))
@@ -80,7 +60,7 @@ class Rule:
         st, st2 = self.d_st.download(np.uint8, 16), self.d_st2.download(np.uint8, 16)
         assert st.tobytes() == st2.tobytes(), "the statistics depend on whether a mask is asked for"
         assert np.all(st[12:] == SENTINEL)
-        return st[:12].view(np.float32), self.mask.read()
+        return st[:12].view(np.float32), payload(self.mask)
 
     def free(self):
         for b in (self.d_pow, self.d_st, self.d_st2, self.mask):
@@ -164,13 +144,13 @@ class Scan:
             self.d_iq.upload(raw)
             self.loaded = key
         nch = raw.size // chunk_bytes
-        self.mask.fill(nch)
+        self.mask.refill(nch)
         self.d_pow.upload(np.full(4 * nch, SENTINEL, np.uint8))
         self.d_st.upload(np.full(16, SENTINEL, np.uint8))
         self.dev.capture_scan_dev(self.d_iq, raw.size, chunk_bytes, self.d_pow, 0.0, self.d_amp, NOISE, WINDOW, FACTOR, self.d_on,
                                   d_stats=self.d_st, d_mask=self.mask.ptr, pct=float(pct), rise_db=float(rise_db))
         self.dev.synchronize()
-        return self.d_pow.download(np.float32, nch), self.d_st.download(np.float32, 3), self.mask.read()
+        return self.d_pow.download(np.float32, nch), self.d_st.download(np.float32, 3), payload(self.mask)
 
     def free(self):
         for b in (self.d_iq, self.d_pow, self.d_st, self.d_amp, self.d_on, self.mask):
@@ -336,7 +316,7 @@ def test_pack_result(dev, name):
     want = rr.pack_result(c["n_chunks"], x.power, x.stats, x.amp, x.onset, x.psd, c["rows"], c["nperseg"], c["rank"],
                           c["n_pairs"], c["pair_cap"], *pairs.host)
     assert want[8] == (0.0 if c["rank"] == 0 else rr.LAG_INVALID) and (c["first_index"] != -1 or want[4] == -1.0)
-    vector_held(name, out.read(), want, x.psd, c["rows"], c["nperseg"], c["n_chunks"])
+    vector_held(name, payload(out), want, x.psd, c["rows"], c["nperseg"], c["n_chunks"])
     for b in (x, pairs, out):
         b.free()
 
@@ -360,7 +340,7 @@ def test_pack_results_three_captures(dev):
     for a, (c, x, o) in enumerate(zip(cs, xs, outs)):
         want = rr.pack_result(c["n_chunks"], x.power, x.stats, x.amp, x.onset, x.psd, c["rows"], nperseg, c["rank"], c["n_pairs"],
                               c["pair_cap"], *pairs.host)
-        vector_held(f"capture {a}", o.read(), want, x.psd, c["rows"], nperseg, c["n_chunks"])
+        vector_held(f"capture {a}", payload(o), want, x.psd, c["rows"], nperseg, c["n_chunks"])
     for b in xs + outs + [pairs, no_rows]:
         b.free()
 
@@ -389,7 +369,7 @@ def test_pack_part(dev, full):
     dev.synchronize()
     want = rr.pack_part(**hdr, **cap, **cnt, nperseg=nperseg, power=x.power, amp=x.amp_part, onset=x.onset, tiles=tiles, psd=x.psd,
                         pairs=pairs.host[0], lags=pairs.host[1], peaks=pairs.host[2], margins=pairs.host[3])
-    got = out.read()
+    got = payload(out)
     assert got.size == want.nbytes
     bad = np.flatnonzero(got.view(np.uint64) != want.view(np.uint64))
     assert bad.size == 0, (bad[:10], got.view(np.float64)[bad[:4]], want[bad[:4]])
@@ -409,7 +389,7 @@ def test_pack_result_refuses_what_the_batched_packer_refuses(dev, nperseg):
                             None, None, None, None, out.ptr)
     assert e.value.status == GJ_ERR_UNSUPPORTED
     dev.synchronize()
-    assert np.all(out.read() == SENTINEL)
+    out.check_untouched("a refused call")
     desc = _ffi.CombineCapture(n_chunks=c["n_chunks"], rows=c["rows"], n_tiles=0, total_bytes=0, n_parts=1, antenna=0, n_pairs=0,
                                pair_cap=c["pair_cap"], d_power=x.d_power.ptr, d_stats=x.d_stats.ptr, d_tiles=None, d_amp_parts=None,
                                d_onset_parts=None, d_amp=x.d_amp.ptr, d_onset=x.d_onset.ptr, d_psd=x.d_psd.ptr, d_out=out.ptr)

@@ -34,3 +34,47 @@ def check(lag, peak, margin, e: dict, what=""):
     assert int(lag) == e["lag"], f"{what}: lag {int(lag)}, want {e['lag']}"
     assert abs(float(peak) - e["peak"]) <= PEAK_RTOL * e["peak"], f"{what}: peak {float(peak)}, want {e['peak']}"
     assert abs(float(margin) - e["margin"]) <= MARGIN_ATOL, f"{what}: margin {float(margin)}, want {e['margin']}"
+
+
+def k5_fft_len(n: int) -> int:
+    return max(1 << 16, 1 << (2 * n - 2).bit_length())
+
+
+def k5_planted(n: int, lag: int, rng, second_lag=None, width=None, at=None):
+    """(sig0, sig1), n samples each: low-level noise (bytes 127 / 128: +-0.5 after unpack) and one burst of rail values
+    (0 / 255: +-127.5), 1..16 samples long, at the two places whose overlap is `lag` -- the correlation peak
+    (correlate(sig1, sig0) peaks where sig1 is sig0 delayed by `lag`).  ``second_lag``: a copy at 0.8 amplitude
+    (bytes 25 / 230) in sig1 as well, whose overlap is that lag -- a deliberate runner-up.  ``at``: the burst's place in
+    sig0 (default: random)."""
+    w = int(width or rng.integers(1, 17))
+    w = min(w, n - abs(lag))
+    sig = [rng.integers(127, 129, size=2 * n, dtype=np.uint8) for _ in range(2)]
+    if at is not None:
+        p0 = at
+    elif lag >= 0:
+        p0 = int(rng.integers(0, n - w - lag + 1))
+    else:
+        p0 = int(rng.integers(0, n - w + lag + 1)) - lag
+    burst = rng.integers(0, 2, size=2 * w, dtype=np.uint8)
+    assert 0 <= p0 <= n - w and 0 <= p0 + lag <= n - w
+    sig[0][2 * p0:2 * (p0 + w)] = burst * 255
+    sig[1][2 * (p0 + lag):2 * (p0 + lag + w)] = burst * 255
+    if second_lag is not None:
+        q = p0 + second_lag
+        assert 0 <= q <= n - w and (q + w <= p0 + lag or q >= p0 + lag + w)
+        sig[1][2 * q:2 * (q + w)] = np.where(burst == 1, 230, 25).astype(np.uint8)
+    return sig[0], sig[1]
+
+
+def k5_edge_lags(n: int):
+    """Peaks at both ends of the 'full' range (circular index N-1 and L-N+1, the last ones before the zero-padding
+    band), at 0, on both sides of a 4096-point row (the column index n2 = lag mod 4096 is 4095, 0, 1), at the first
+    and last rows that hold a lag, and at the edge of a column kernel's tile of B = 4096 / L1 columns."""
+    B = 4096 // (k5_fft_len(n) // 4096)
+    K = (n - 2) // 4096
+    lags = {n - 1, -(n - 1), n - 2, -(n - 2), 0, 4095, 4096, 4097, -4095, -4096, -4097, 4096 * K - 1, -(4096 * K + 1),
+            B - 1, B, -B}
+    return sorted(x for x in lags if abs(x) <= n - 1)
+
+
+K5_PLANT_N = [32768, (1 << 22) - 3]      # L1 = 16 (L = 2N: a one-point padding band), L1 = 2048

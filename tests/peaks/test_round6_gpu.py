@@ -19,26 +19,11 @@ import corr_restatement as cr
 import gpsjam
 import peaks_restatement as pr
 from gpsjam import gnss, spoof
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, SENTINEL, Guarded, refused
+from gpu_lib import run_peaks as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind the records
-
-
-def run(dev, P, k, guard):
-    """(peaks ACQ_PEAK_DTYPE[n_prn][k], floor ACQ_FLOOR_DTYPE[n_prn]) through gj_acq_peaks_dev into sentinel-filled buffers."""
-    P = np.ascontiguousarray(P, np.float64)
-    n_prn, n_freq, nsamp = P.shape
-    with dev.alloc(P.nbytes) as d_power, dev.alloc(16 * n_prn * k + PAD) as d_peaks, dev.alloc(16 * n_prn + PAD) as d_floor:
-        d_power.upload(P)
-        d_peaks.upload(np.full(d_peaks.nbytes, SENTINEL, np.uint8))
-        d_floor.upload(np.full(d_floor.nbytes, SENTINEL, np.uint8))
-        dev.acq_peaks_dev(d_power, n_prn, n_freq, nsamp, k, guard, d_peaks, d_floor)
-        peaks, floor = d_peaks.download(np.uint8), d_floor.download(np.uint8)
-    assert np.all(peaks[16 * n_prn * k:] == SENTINEL) and np.all(floor[16 * n_prn:] == SENTINEL), "bytes were written behind the call's records"
-    return (peaks[:16 * n_prn * k].view(gpsjam.ACQ_PEAK_DTYPE).reshape(n_prn, k), floor[:16 * n_prn].view(gpsjam.ACQ_FLOOR_DTYPE))
 
 
 def compare(dev, P, k, guard):
@@ -181,10 +166,8 @@ def test_zones_that_leave_a_single_column(dev):
 def test_refusals_enqueue_nothing(dev):
     P = pr.random_surfaces(3, 2, 500)
     I, U = GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
-    with dev.alloc(P.nbytes) as d_power, dev.alloc(16 * 3 * 8 + PAD) as d_peaks, dev.alloc(16 * 3 + PAD) as d_floor:
+    with dev.alloc(P.nbytes) as d_power, Guarded(dev, 16 * 3 * 8) as d_peaks, Guarded(dev, 16 * 3) as d_floor:
         d_power.upload(P)
-        d_peaks.upload(np.full(d_peaks.nbytes, SENTINEL, np.uint8))
-        d_floor.upload(np.full(d_floor.nbytes, SENTINEL, np.uint8))
         cases = [  # d_power, n_prn, n_freq, nsamp, k, guard, d_peaks, d_floor, status
             (0, 3, 2, 500, 2, 4, d_peaks, d_floor, I),                                  # null pointers
             (d_power, 3, 2, 500, 2, 4, 0, d_floor, I),
@@ -210,17 +193,14 @@ def test_refusals_enqueue_nothing(dev):
             (d_power, 3, 2, 500, 1, 250, d_peaks, d_floor, I),                          # 501
             (d_power, 3, 2, 500, 8, 2 ** 31 - 1, d_peaks, d_floor, I),                  # k (2 guard + 1) past int32
         ]
-        for d_p, n_prn, n_freq, nsamp, k, guard, d_pk, d_fl, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.acq_peaks_dev(d_p, n_prn, n_freq, nsamp, k, guard, d_pk, d_fl)
-            assert e.value.status == status, (n_prn, n_freq, nsamp, k, guard, e.value)
-            dev.synchronize()
-            assert np.all(d_peaks.download(np.uint8) == SENTINEL) and np.all(d_floor.download(np.uint8) == SENTINEL), (n_prn, n_freq, nsamp, k, guard)
+        for c in cases:                                      # nothing written behind each one of them
+            refused(dev, dev.acq_peaks_dev, [(c[:-1], c[-1])], d_peaks, d_floor)
         # accepted: the limits themselves (4 * 125 - 1 = 499 < 500; one zone of 499 columns)
         dev.acq_peaks_dev(d_power, 3, 2, 500, 8, 30, d_peaks, d_floor)                  # 8 * 61 = 488
         dev.acq_peaks_dev(d_power, 3, 2, 500, 1, 249, d_peaks, d_floor)
         dev.synchronize()
-        assert np.all(d_peaks.download(np.uint8, PAD, 16 * 3 * 8) == SENTINEL) and np.all(d_floor.download(np.uint8, PAD, 16 * 3) == SENTINEL)
+        d_peaks.check_pads("peaks")
+        d_floor.check_pads("floor")
     compare(dev, P, 2, 4)                                                               # the next valid call gives the parity bits
 
 

@@ -14,14 +14,12 @@ import pytest
 import gpsjam
 import ridge_restatement as rr
 from gpsjam import classify
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, refused
+from gpu_lib import run_ridge as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
 REC = gpsjam.RIDGE_DTYPE.itemsize
-SENTINEL = 0xA5
-PAD = 64                                        # sentinel records behind d_out[n_frames]
-RTOL = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -31,29 +29,6 @@ def cap(dev):
     c.free()
 
 
-def run(dev, d_iq, nbytes, nfft, hop, first, n_frames, guard):
-    """n_frames records through gj_ridge_dev into a sentinel-filled buffer; the bytes behind them must stay untouched."""
-    out = dev.alloc((n_frames + PAD) * REC)
-    try:
-        out.upload(np.full((n_frames + PAD) * REC, SENTINEL, np.uint8))
-        dev.ridge_dev(d_iq, nbytes, first, nfft, hop, n_frames, guard, out)
-        raw = out.download(np.uint8)
-    finally:
-        out.free()
-    assert np.all(raw[n_frames * REC:] == SENTINEL), "records were written behind d_out[n_frames]"
-    return raw[:n_frames * REC].view(gpsjam.RIDGE_DTYPE)
-
-
-def compare(got, want, what):
-    assert got.size == want.size, what
-    np.testing.assert_array_equal(got["peak_bin"], want["peak_bin"], err_msg=str(what))
-    for key in ("total", "peak"):
-        err = np.max(np.abs(got[key] - want[key]) / want[key])
-        assert err <= RTOL, (what, key, err)
-    err = np.max(np.abs(got["second"] - want["second"]) / want["peak"])
-    assert err <= RTOL, (what, "second", err)
-
-
 @pytest.mark.parametrize("nfft", rr.PARITY_NFFT)
 def test_parity_with_the_restatement(dev, cap, nfft):
     for hop in rr.parity_hops(nfft):
@@ -61,7 +36,7 @@ def test_parity_with_the_restatement(dev, cap, nfft):
             for guard in (0, 2):
                 want, _ = rr.parity_reference(nfft, hop, first, guard)
                 got = run(dev, cap, cap.nbytes, nfft, hop, first, want.size, guard)
-                compare(got, want, (nfft, hop, first, guard))
+                rr.compare(got, want, (nfft, hop, first, guard))
 
 
 @pytest.mark.parametrize("nfft", rr.PARITY_NFFT)
@@ -76,7 +51,7 @@ def test_frame_counts_that_do_not_fill_a_workgroup_step(dev, cap, nfft):
         with dev.capture(raw[:nbytes]) as exact:
             got = run(dev, exact, nbytes, nfft, hop, first, n_frames, 2)
         want, _ = rr.ridge(raw[:nbytes], nfft, hop, first, n_frames, 2)
-        compare(got, want, (nfft, n_frames, "exact"))
+        rr.compare(got, want, (nfft, n_frames, "exact"))
         # the same frames as the head of the long capture: same bits
         head = run(dev, cap, cap.nbytes, nfft, hop, first, n_frames, 2)
         assert head.tobytes() == got.tobytes(), (nfft, n_frames)
@@ -106,12 +81,12 @@ def test_unpack_convention(dev, cap):
         for nfft in rr.PARITY_NFFT:
             hop = nfft // 2 + 37
             want, _ = rr.parity_reference(nfft, hop, 1, 2, 128.0, 1.0 / 128.0)
-            compare(run(dev, cap, cap.nbytes, nfft, hop, 1, want.size, 2), want, (nfft, "gnssdec convention"))
+            rr.compare(run(dev, cap, cap.nbytes, nfft, hop, 1, want.size, 2), want, (nfft, "gnssdec convention"))
     finally:
         dev.set_unpack()
     assert dev.get_unpack() == (127.5, 1.0 / 127.5)
     want, _ = rr.parity_reference(256, 128, 0, 2)
-    compare(run(dev, cap, cap.nbytes, 256, 128, 0, want.size, 2), want, "default convention restored")
+    rr.compare(run(dev, cap, cap.nbytes, 256, 128, 0, want.size, 2), want, "default convention restored")
 
 
 def test_refusals_enqueue_nothing(dev, cap):
@@ -123,22 +98,15 @@ def test_refusals_enqueue_nothing(dev, cap):
         (256, 128, 0, 0, 2, GJ_ERR_INVALID), (256, 128, 0, fit + 1, 2, GJ_ERR_INVALID),
         (256, 128, cap.nsamples, 1, 2, GJ_ERR_INVALID),
     ]
-    out = dev.alloc((fit + 1 + PAD) * REC)
+    out = Guarded(dev, (fit + 1) * REC, pad=64 * REC)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        for nfft, hop, first, n_frames, guard, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.ridge_dev(cap, cap.nbytes, first, nfft, hop, n_frames, guard, out)
-            assert e.value.status == status, (nfft, hop, first, n_frames, guard, e.value)
-        with pytest.raises(gpsjam.GpsJamError) as e:
-            dev.ridge_dev(0, cap.nbytes, 0, 256, 128, 4, 2, out)
-        assert e.value.status == GJ_ERR_INVALID
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL)
+        calls = [((cap, cap.nbytes, first, nfft, hop, n_frames, guard, out), status) for nfft, hop, first, n_frames, guard, status in cases]
+        refused(dev, dev.ridge_dev, calls + [((0, cap.nbytes, 0, 256, 128, 4, 2, out), GJ_ERR_INVALID)], out)
         # guard at its largest (2 guard + 1 < nfft) and a call that just fits are accepted
         dev.ridge_dev(cap, cap.nbytes, 0, 16, 8, 4, 7, out)
         dev.ridge_dev(cap, cap.nbytes, 0, 256, 128, fit, 2, out)
         dev.synchronize()
+        out.check_pads("records")
     finally:
         out.free()
 
@@ -149,7 +117,7 @@ def test_device_ridge_takes_host_bytes_and_captures(dev, cap):
     b = dev.ridge(rr.parity_capture(), nfft=256, hop=128, guard=2)
     assert (a.nfft, a.hop, a.first_sample, a.guard, len(a)) == (256, 128, 0, 2, want.size)
     assert a.records.tobytes() == b.records.tobytes()
-    compare(a.records, want, "Device.ridge")
+    rr.compare(a.records, want, "Device.ridge")
     part = dev.ridge(cap, nfft=64, hop=100, first_sample=5, n_frames=10, guard=1)
     assert len(part) == 10 and part[4:].first_sample == 405
     np.testing.assert_allclose(a.concentration, want["peak"] / want["total"], rtol=3e-5)

@@ -204,3 +204,16 @@ def parity_reference(nfft, hop, first_sample, guard, offset=127.5, scale=1.0 / 1
     rec.setflags(write=False)
     margin.setflags(write=False)
     return rec, margin
+
+
+RTOL = 1e-5                 # the project's figure for a K2 PSD value summed in another order (tests/test_gpu_parity.py)
+
+
+def compare(got, want, what):
+    assert got.size == want.size, what
+    np.testing.assert_array_equal(got["peak_bin"], want["peak_bin"], err_msg=str(what))
+    for key in ("total", "peak"):
+        err = np.max(np.abs(got[key] - want[key]) / want[key])
+        assert err <= RTOL, (what, key, err)
+    err = np.max(np.abs(got["second"] - want["second"]) / want["peak"])
+    assert err <= RTOL, (what, "second", err)

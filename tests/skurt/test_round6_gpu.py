@@ -20,13 +20,11 @@ import gpsjam
 import ridge_restatement as rr
 import skurt_restatement as sr
 from gpsjam import kurtosis, mitigate
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, Guarded, freed, refused
+from gpu_lib import run_sk as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind each output
-worst = {"s1": 0.0, "s2": 0.0, "sk_ulp": 0.0}   # largest errors seen, relative to the tolerance's own reference
 
 
 @pytest.fixture(scope="module")
@@ -34,51 +32,6 @@ def cap(dev):
     c = dev.capture(rr.parity_capture())
     yield c
     c.free()
-
-
-def run(dev, d_iq, nbytes, nfft, hop, first, m, n_rows, want_sk=True):
-    """(S1, S2, SK | None) as float32[n_rows][nfft] through gj_sk_dev into sentinel-filled buffers."""
-    size = 4 * n_rows * nfft
-    bufs = [dev.alloc(size + PAD) for _ in range(3)]
-    try:
-        for b in bufs:
-            b.upload(np.full(b.nbytes, SENTINEL, np.uint8))
-        dev.spectral_kurtosis_dev(d_iq, nbytes, first, nfft, hop, m, n_rows, bufs[0], bufs[1], bufs[2] if want_sk else None)
-        raw = [b.download(np.uint8) for b in bufs]
-    finally:
-        for b in bufs:
-            b.free()
-    for k, r in enumerate(raw):
-        assert np.all(r[size if (k < 2 or want_sk) else 0:] == SENTINEL), f"output {k}: bytes were written behind [n_rows][nfft]"
-    out = [r[:size].view(np.float32).reshape(n_rows, nfft) for r in raw]
-    return out[0], out[1], (out[2] if want_sk else None)
-
-
-def check_sk(s1, s2, skv, m, what):
-    """d_sk against the formula in float64 on the float32 sums the call wrote."""
-    want = sr.estimate(s1, s2, m)
-    dead = s1 == 0
-    assert np.array_equal(np.isnan(skv), dead), (what, "NaN exactly where S1 == 0")
-    live = ~dead
-    if live.any():
-        w32 = want[live].astype(np.float32)
-        ulps = np.abs(skv[live].astype(np.float64) - want[live]) / np.spacing(np.abs(w32)).astype(np.float64)
-        worst["sk_ulp"] = max(worst["sk_ulp"], float(ulps.max()))
-        assert ulps.max() <= 2.0, (what, float(ulps.max()))
-
-
-def compare(got, p, m, n_rows, what):
-    """GPU sums against the restatement's, from frame powers p."""
-    r1, r2, _ = sr.sums_of(p, m, n_rows)
-    s1, s2, skv = got
-    assert s1.shape == r1.shape, what
-    e1 = float(np.max(np.abs(s1 - r1) / r1.max(axis=1, keepdims=True)))
-    e2 = float(np.max(np.abs(s2 - r2) / r2.max(axis=1, keepdims=True)))
-    worst["s1"], worst["s2"] = max(worst["s1"], e1), max(worst["s2"], e2)
-    assert e1 <= sr.S1_TOL, (what, "S1", e1)
-    assert e2 <= sr.S2_TOL, (what, "S2", e2)
-    if skv is not None:
-        check_sk(s1, s2, skv, m, what)
 
 
 @pytest.mark.parametrize("nfft", sr.NFFT)
@@ -89,9 +42,9 @@ def test_parity_with_the_restatement(dev, cap, nfft):
             for m in sr.PARITY_M:
                 n_rows = gpsjam.sk_rows(cap.nbytes, first, nfft, hop, m)
                 assert n_rows == p.shape[0] // m >= 1
-                compare(run(dev, cap, cap.nbytes, nfft, hop, first, m, n_rows), p, m, n_rows, (nfft, hop, first, m))
-    print(f"nfft {nfft}: largest errors so far S1 {worst['s1']:.2e} (tolerance {sr.S1_TOL:.0e}), S2 {worst['s2']:.2e} "
-          f"(tolerance {sr.S2_TOL:.0e}), SK {worst['sk_ulp']:.2f} ulp")
+                sr.compare(run(dev, cap, cap.nbytes, nfft, hop, first, m, n_rows), p, m, n_rows, (nfft, hop, first, m))
+    print(f"nfft {nfft}: largest errors so far S1 {sr.worst['s1']:.2e} (tolerance {sr.S1_TOL:.0e}), S2 {sr.worst['s2']:.2e} "
+          f"(tolerance {sr.S2_TOL:.0e}), SK {sr.worst['sk_ulp']:.2f} ulp")
 
 
 @pytest.mark.parametrize("nfft", sr.BOUNDARY_NFFT)      # a group inside a wave, a whole wave, the whole workgroup
@@ -102,8 +55,8 @@ def test_block_boundaries(dev, cap, nfft):
     for m in sr.BOUNDARY_M:
         for n_rows in (1, 3):
             assert n_rows <= gpsjam.sk_rows(cap.nbytes, first, nfft, hop, m)
-            compare(run(dev, cap, cap.nbytes, nfft, hop, first, m, n_rows), p, m, n_rows, (nfft, m, n_rows))
-    print(f"nfft {nfft}: largest errors so far S1 {worst['s1']:.2e}, S2 {worst['s2']:.2e}, SK {worst['sk_ulp']:.2f} ulp")
+            sr.compare(run(dev, cap, cap.nbytes, nfft, hop, first, m, n_rows), p, m, n_rows, (nfft, m, n_rows))
+    print(f"nfft {nfft}: largest errors so far S1 {sr.worst['s1']:.2e}, S2 {sr.worst['s2']:.2e}, SK {sr.worst['sk_ulp']:.2f} ulp")
 
 
 def test_exactly_all_rows_that_fit(dev):
@@ -114,7 +67,7 @@ def test_exactly_all_rows_that_fit(dev):
         assert gpsjam.sk_rows(nbytes, first, nfft, hop, m) == n_rows and gpsjam.sk_rows(nbytes - 2, first, nfft, hop, m) == n_rows - 1
         with dev.capture(raw[:nbytes]) as exact:
             got = run(dev, exact, nbytes, nfft, hop, first, m, n_rows)
-        compare(got, sr.parity_powers(nfft, hop, first), m, n_rows, (nfft, "exact"))
+        sr.compare(got, sr.parity_powers(nfft, hop, first), m, n_rows, (nfft, "exact"))
 
 
 def test_workgroups_that_take_more_than_one_step(dev):
@@ -127,13 +80,13 @@ def test_workgroups_that_take_more_than_one_step(dev):
     assert n_rows == ((1 << 18) - 16 + 1) // 4
     with dev.capture(raw) as c:
         got = run(dev, c, c.nbytes, 16, 1, 0, 4, n_rows)
-    compare(got, sr.frame_powers(raw, 16, 1, 0, 4 * n_rows), 4, n_rows, "M 4 on 2^18 samples")
+    sr.compare(got, sr.frame_powers(raw, 16, 1, 0, 4 * n_rows), 4, n_rows, "M 4 on 2^18 samples")
     raw = sr.detect_capture("tone")
     n_rows = gpsjam.sk_rows(raw.size, 0, 16, 1, 2)
     assert n_rows * 1 >= 768 * 256 + 1
     with dev.capture(raw) as c:
         got = run(dev, c, c.nbytes, 16, 1, 0, 2, n_rows, want_sk=False)
-    compare(got, sr.frame_powers(raw, 16, 1, 0, 2 * n_rows), 2, n_rows, "M 2 on 2^19 samples")
+    sr.compare(got, sr.frame_powers(raw, 16, 1, 0, 2 * n_rows), 2, n_rows, "M 2 on 2^19 samples")
 
 
 @pytest.mark.parametrize("nfft", sr.BOUNDARY_NFFT)
@@ -165,18 +118,18 @@ def test_unpack_convention(dev, cap):
             hop = nfft // 2 + 37
             p = sr.parity_powers(nfft, hop, 1, 128.0, 1.0 / 128.0)
             n_rows = p.shape[0] // 5
-            compare(run(dev, cap, cap.nbytes, nfft, hop, 1, 5, n_rows), p, 5, n_rows, (nfft, "gnssdec convention"))
+            sr.compare(run(dev, cap, cap.nbytes, nfft, hop, 1, 5, n_rows), p, 5, n_rows, (nfft, "gnssdec convention"))
     finally:
         dev.set_unpack()
     assert dev.get_unpack() == (127.5, 1.0 / 127.5)
     p = sr.parity_powers(256, 256, 0)
-    compare(run(dev, cap, cap.nbytes, 256, 256, 0, 17, p.shape[0] // 17), p, 17, p.shape[0] // 17, "default convention restored")
+    sr.compare(run(dev, cap, cap.nbytes, 256, 256, 0, 17, p.shape[0] // 17), p, 17, p.shape[0] // 17, "default convention restored")
 
 
 def test_refusals_enqueue_nothing(dev, cap):
     fit = gpsjam.sk_rows(cap.nbytes, 0, 256, 128, 16)
     size = 4 * (fit + 1) * 256
-    s1, s2, skb = (dev.alloc(size + PAD) for _ in range(3))
+    s1, s2, skb = (Guarded(dev, size) for _ in range(3))
     ok = (cap, cap.nbytes, 0, 256, 128, 16, 4)
     cases = [  # d_iq, nbytes, first, nfft, hop, M, n_rows, d_s1, d_s2, d_sk, status
         (cap, cap.nbytes, 0, 8, 4, 16, 4, s1, s2, skb, GJ_ERR_UNSUPPORTED),
@@ -200,23 +153,15 @@ def test_refusals_enqueue_nothing(dev, cap):
         (*ok, s1, s2, skb.ptr + 2, GJ_ERR_INVALID),
     ]
     try:
-        for b in (s1, s2, skb):
-            b.upload(np.full(b.nbytes, SENTINEL, np.uint8))
-        for *args, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.spectral_kurtosis_dev(*args)
-            assert e.value.status == status, (args[1:7], e.value)
-        dev.synchronize()
-        for b in (s1, s2, skb):
-            assert np.all(b.download(np.uint8) == SENTINEL)
+        refused(dev, dev.spectral_kurtosis_dev, [(c[:-1], c[-1]) for c in cases], s1, s2, skb)
         # accepted: M at its smallest, a call that just fits, no d_sk
         dev.spectral_kurtosis_dev(cap, cap.nbytes, 0, 16, 8, 2, 4, s1, s2, skb)
         dev.spectral_kurtosis_dev(cap, cap.nbytes, 0, 256, 128, 16, fit, s1, s2, None)
         dev.synchronize()
-        assert np.all(s1.download(np.uint8, PAD, size) == SENTINEL) and np.all(s2.download(np.uint8, PAD, size) == SENTINEL)
+        for b, what in ((s1, "S1"), (s2, "S2"), (skb, "SK")):
+            b.check_pads(what)
     finally:
-        for b in (s1, s2, skb):
-            b.free()
+        freed(s1, s2, skb)
 
 
 def test_device_spectral_kurtosis_takes_host_bytes_and_captures(dev, cap):
@@ -225,7 +170,7 @@ def test_device_spectral_kurtosis_takes_host_bytes_and_captures(dev, cap):
     b = dev.spectral_kurtosis(rr.parity_capture(), nfft=256, hop=256, frames_per_row=64)
     assert (a.nfft, a.hop, a.frames_per_row, a.first_sample, len(a)) == (256, 256, 64, 0, 8)
     assert a.s1.tobytes() == b.s1.tobytes() and a.s2.tobytes() == b.s2.tobytes() and a.sk.tobytes() == b.sk.tobytes()
-    compare((a.s1, a.s2, a.sk), p, 64, 8, "Device.spectral_kurtosis")
+    sr.compare((a.s1, a.s2, a.sk), p, 64, 8, "Device.spectral_kurtosis")
     part = dev.spectral_kurtosis(cap, nfft=64, hop=100, frames_per_row=5, first_sample=5, n_rows=3)
     assert len(part) == 3 and part.s1.shape == (3, 64)
     np.testing.assert_allclose(a.merged(), sr.sums_of(p, 512, 1)[2][0], rtol=1e-4)

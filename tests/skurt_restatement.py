@@ -174,3 +174,33 @@ def parity_powers(nfft, hop, first_sample, offset=127.5, scale=1.0 / 127.5):
     p = frame_powers(raw, nfft, hop, first_sample, rr.frames_that_fit(raw.size, first_sample, nfft, hop), offset, scale)
     p.setflags(write=False)
     return p
+
+
+worst = {"s1": 0.0, "s2": 0.0, "sk_ulp": 0.0}   # largest errors seen, relative to the tolerance's own reference
+
+
+def check_sk(s1, s2, skv, m, what):
+    """d_sk against the formula in float64 on the float32 sums the call wrote."""
+    want = estimate(s1, s2, m)
+    dead = s1 == 0
+    assert np.array_equal(np.isnan(skv), dead), (what, "NaN exactly where S1 == 0")
+    live = ~dead
+    if live.any():
+        w32 = want[live].astype(np.float32)
+        ulps = np.abs(skv[live].astype(np.float64) - want[live]) / np.spacing(np.abs(w32)).astype(np.float64)
+        worst["sk_ulp"] = max(worst["sk_ulp"], float(ulps.max()))
+        assert ulps.max() <= 2.0, (what, float(ulps.max()))
+
+
+def compare(got, p, m, n_rows, what):
+    """GPU sums against the restatement's, from frame powers p."""
+    r1, r2, _ = sums_of(p, m, n_rows)
+    s1, s2, skv = got
+    assert s1.shape == r1.shape, what
+    e1 = float(np.max(np.abs(s1 - r1) / r1.max(axis=1, keepdims=True)))
+    e2 = float(np.max(np.abs(s2 - r2) / r2.max(axis=1, keepdims=True)))
+    worst["s1"], worst["s2"] = max(worst["s1"], e1), max(worst["s2"], e2)
+    assert e1 <= S1_TOL, (what, "S1", e1)
+    assert e2 <= S2_TOL, (what, "S2", e2)
+    if skv is not None:
+        check_sk(s1, s2, skv, m, what)

@@ -31,18 +31,12 @@ import gpsjam
 import ridge_restatement as rr
 import skurt_restatement as sr
 import stft_scale_inputs as si
-from chirp import test_round6_gpu as chirp_t
-from excise import test_round6_gpu as excise_t
-from excise_chirp import test_round6_gpu as xchirp_t
-from ridge import test_round6_gpu as ridge_t
-from skurt import test_round6_gpu as skurt_t
+from gpu_lib import GJ_ERR_INVALID, Guarded, Resident, freed, refused, run_chirp, run_excise_chirp, run_ridge, run_sk
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID = -1                             # include/gpsjam.h gj_status
-SENTINEL = 0xA5
 RTOL = cr.RTOL
-assert RTOL == ridge_t.RTOL == xr.RTOL == 1e-5
+assert RTOL == rr.RTOL == xr.RTOL == 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -73,7 +67,7 @@ def sweeps(dev):
 
 @pytest.fixture(scope="module")
 def res(dev):
-    r = xchirp_t.Resident(dev)
+    r = Resident(dev)
     yield r
     r.free()
 
@@ -111,14 +105,14 @@ def test_ridge_at_1541_steps(dev, cus, tone, nfft):
     grid = many_steps(cus, si.ridge_min_waves(nfft), si.STEPS, f"ridge {nfft}")
     want, margin = si.ridge_reference(nfft)
     assert margin.min() >= rr.NEAR_TIE
-    got = ridge_t.run(dev, tone, tone.nbytes, nfft, hop, si.FIRST, n, si.GUARD)
+    got = run_ridge(dev, tone, tone.nbytes, nfft, hop, si.FIRST, n, si.GUARD)
     print(f"ridge {nfft}: {n} frames, peak_bin differs on {int(np.sum(got['peak_bin'] != want['peak_bin']))}, total {rel(got['total'], want['total']):.2e}, "
           f"peak {rel(got['peak'], want['peak']):.2e}, second {rel(got['second'], want['second'], want['peak']):.2e} (tolerance {RTOL:.0e})")
-    ridge_t.compare(got, want, (nfft, hop, "1541 steps"))
-    assert ridge_t.run(dev, tone, tone.nbytes, nfft, hop, si.FIRST, n, si.GUARD).tobytes() == got.tobytes(), "the long call repeated"
+    rr.compare(got, want, (nfft, hop, "1541 steps"))
+    assert run_ridge(dev, tone, tone.nbytes, nfft, hop, si.FIRST, n, si.GUARD).tobytes() == got.tobytes(), "the long call repeated"
     for k, m in pieces(grid, b, n):
         assert one_step_each(cus, si.ridge_min_waves(nfft), -(-m // b))
-        piece = ridge_t.run(dev, tone, tone.nbytes, nfft, hop, si.FIRST + k * hop, m, si.GUARD)
+        piece = run_ridge(dev, tone, tone.nbytes, nfft, hop, si.FIRST + k * hop, m, si.GUARD)
         assert piece.tobytes() == got[k:k + m].tobytes(), (nfft, k, m)
 
 
@@ -163,13 +157,13 @@ def test_chirp_at_1541_steps(dev, cus, sweeps, nfft):
     grid = many_steps(cus, si.chirp_min_waves(nfft), si.STEPS, f"chirp {nfft}")
     cap = sweeps(nfft)
     assert gpsjam.ridge_frames(cap.nbytes, si.FIRST, nfft, hop) == n
-    got, peaks = chirp_t.run(dev, cap, cap.nbytes, nfft, hop, si.FIRST, n, rates, si.GUARD)
+    got, peaks = run_chirp(dev, cap, cap.nbytes, nfft, hop, si.FIRST, n, rates, si.GUARD)
     compare_chirp(got, peaks, si.chirp_reference(nfft), si.scale_sweep_capture(nfft), nfft, rates, f"chirp {nfft}")
-    again, pagain = chirp_t.run(dev, cap, cap.nbytes, nfft, hop, si.FIRST, n, rates, si.GUARD)
+    again, pagain = run_chirp(dev, cap, cap.nbytes, nfft, hop, si.FIRST, n, rates, si.GUARD)
     assert again.tobytes() == got.tobytes() and pagain.tobytes() == peaks.tobytes(), "the long call repeated"
     for k, m in pieces(grid, b, n):
         assert one_step_each(cus, si.chirp_min_waves(nfft), -(-m // b))
-        piece, ppiece = chirp_t.run(dev, cap, cap.nbytes, nfft, hop, si.FIRST + k * hop, m, rates, si.GUARD)
+        piece, ppiece = run_chirp(dev, cap, cap.nbytes, nfft, hop, si.FIRST + k * hop, m, rates, si.GUARD)
         assert piece.tobytes() == got[k:k + m].tobytes() and ppiece.tobytes() == peaks[k:k + m].tobytes(), (nfft, k, m)
 
 
@@ -180,9 +174,9 @@ def test_rate_zero_is_gj_ridge_dev_byte_for_byte_at_1541_steps(dev, cus, sweeps,
     many_steps(cus, si.chirp_min_waves(nfft), si.STEPS, f"chirp {nfft} at rate 0")
     many_steps(cus, si.ridge_min_waves(nfft), si.STEPS, f"ridge {nfft} on the sweep")
     cap = sweeps(nfft)
-    got, peaks = chirp_t.run(dev, cap, cap.nbytes, nfft, hop, si.FIRST, n, rates, si.GUARD)
-    ridge = ridge_t.run(dev, cap, cap.nbytes, nfft, hop, si.FIRST, n, si.GUARD)
-    head = np.ascontiguousarray(got.view(np.uint8).reshape(n, chirp_t.REC)[:, :16])
+    got, peaks = run_chirp(dev, cap, cap.nbytes, nfft, hop, si.FIRST, n, rates, si.GUARD)
+    ridge = run_ridge(dev, cap, cap.nbytes, nfft, hop, si.FIRST, n, si.GUARD)
+    head = np.ascontiguousarray(got.view(np.uint8).reshape(n, gpsjam.CHIRP_DTYPE.itemsize)[:, :16])
     assert head.tobytes() == ridge.tobytes(), nfft
     assert not got["rate_index"].any() and peaks[:, 0].tobytes() == got["peak"].tobytes()
     moves = int(np.sum(np.diff(ridge["peak_bin"]) != 0))
@@ -200,21 +194,21 @@ def test_kurtosis_block_hand_over_across_steps(dev, cus, tone, nfft):
     nsteps = -(-nb * rows // b)
     grid = many_steps(cus, si.sk_min_waves(nfft), nsteps, f"kurtosis {nfft}")
     assert rows <= gpsjam.sk_rows(tone.nbytes, si.FIRST, nfft, si.SK_HOP, m) and m <= 64
-    s1, s2, skv = skurt_t.run(dev, tone, tone.nbytes, nfft, si.SK_HOP, si.FIRST, m, rows)
+    s1, s2, skv = run_sk(dev, tone, tone.nbytes, nfft, si.SK_HOP, si.FIRST, m, rows)
     r1, r2 = si.sk_reference(nfft)
     e1, e2 = rel(s1, r1, r1.max(axis=1, keepdims=True)), rel(s2, r2, r2.max(axis=1, keepdims=True))
     print(f"kurtosis {nfft}: {rows} rows of {m} frames, S1 {e1:.2e} (tolerance {sr.S1_TOL:.0e}), S2 {e2:.2e} (tolerance {sr.S2_TOL:.0e})")
     assert e1 <= sr.S1_TOL, (nfft, "S1", e1)
     assert e2 <= sr.S2_TOL, (nfft, "S2", e2)
-    skurt_t.check_sk(s1, s2, skv, m, (nfft, "many steps"))
-    print(f"kurtosis {nfft}: SK within {skurt_t.worst['sk_ulp']:.2f} ulp (the largest of this run so far; tolerance 2)")
-    again = skurt_t.run(dev, tone, tone.nbytes, nfft, si.SK_HOP, si.FIRST, m, rows)
+    sr.check_sk(s1, s2, skv, m, (nfft, "many steps"))
+    print(f"kurtosis {nfft}: SK within {sr.worst['sk_ulp']:.2f} ulp (the largest of this run so far; tolerance 2)")
+    again = run_sk(dev, tone, tone.nbytes, nfft, si.SK_HOP, si.FIRST, m, rows)
     assert all(x.tobytes() == y.tobytes() for x, y in zip(again, (s1, s2, skv))), "the long call repeated"
     second_round = -(-grid * b // nb) + 1
     assert second_round + 8 <= rows - 8
     for k in (second_round, rows - 8):
         assert one_step_each(cus, si.sk_min_waves(nfft), -(-nb * 8 // b))
-        piece = skurt_t.run(dev, tone, tone.nbytes, nfft, si.SK_HOP, si.FIRST + k * m * si.SK_HOP, m, 8)
+        piece = run_sk(dev, tone, tone.nbytes, nfft, si.SK_HOP, si.FIRST + k * m * si.SK_HOP, m, 8)
         assert all(x.tobytes() == y[k:k + 8].tobytes() for x, y in zip(piece, (s1, s2, skv))), (nfft, k)
 
 
@@ -264,7 +258,7 @@ def test_excisor_runs_longer_than_four_frames(dev, cus, excise_cap, res, chirp, 
 
     def run(first_frame, n_samples, want_frames=True):
         rate = d_rate.ptr + 4 * first_frame if chirp else None
-        return xchirp_t.run(dev, cap, cap.nbytes, first + first_frame * h, n_samples, nfft, rate, d_thr, want_frames, plain=not chirp)
+        return run_excise_chirp(dev, cap, cap.nbytes, first + first_frame * h, n_samples, nfft, rate, d_thr, want_frames, plain=not chirp)
 
     long_b, long_r = run(0, n)
     assert long_r["n_excised"].sum() > 0
@@ -324,17 +318,17 @@ def test_ridge_and_kurtosis_past_byte_2_32(dev, big, nfft):
     place(big, raw)
     with dev.capture(raw) as small:
         want, _ = rr.parity_reference(nfft, hop, s, si.GUARD)
-        a = ridge_t.run(dev, small, small.nbytes, nfft, hop, s, want.size, si.GUARD)
-        ridge_t.compare(a, want, (nfft, "the window as a capture of its own"))
-        far = ridge_t.run(dev, big, BIG, nfft, hop, S0 + s, want.size, si.GUARD)
+        a = run_ridge(dev, small, small.nbytes, nfft, hop, s, want.size, si.GUARD)
+        rr.compare(a, want, (nfft, "the window as a capture of its own"))
+        far = run_ridge(dev, big, BIG, nfft, hop, S0 + s, want.size, si.GUARD)
         assert far.tobytes() == a.tobytes(), ("gj_ridge_dev", nfft)
         # kurtosis: M = 5 and a hop that is not nfft / 2
         m, p = 5, sr.parity_powers(nfft, hop, s)
         rows = p.shape[0] // m
         assert rows == gpsjam.sk_rows(small.nbytes, s, nfft, hop, m) >= 1
-        near = skurt_t.run(dev, small, small.nbytes, nfft, hop, s, m, rows)
-        skurt_t.compare(near, p, m, rows, (nfft, "the window as a capture of its own"))
-        far = skurt_t.run(dev, big, BIG, nfft, hop, S0 + s, m, rows)
+        near = run_sk(dev, small, small.nbytes, nfft, hop, s, m, rows)
+        sr.compare(near, p, m, rows, (nfft, "the window as a capture of its own"))
+        far = run_sk(dev, big, BIG, nfft, hop, S0 + s, m, rows)
         assert all(x.tobytes() == y.tobytes() for x, y in zip(far, near)), ("gj_sk_dev", nfft)
 
 
@@ -345,9 +339,9 @@ def test_chirp_past_byte_2_32(dev, big, nfft):
     with dev.capture(raw) as small:
         want = cr.parity_reference(nfft, rates, s)
         n = want.records.size
-        a, pa = chirp_t.run(dev, small, small.nbytes, nfft, hop, s, n, rates)
-        chirp_t.compare(a, pa, want, (nfft, "the window as a capture of its own"))
-        far, pfar = chirp_t.run(dev, big, BIG, nfft, hop, S0 + s, n, rates)
+        a, pa = run_chirp(dev, small, small.nbytes, nfft, hop, s, n, rates)
+        cr.compare(a, pa, want, (nfft, "the window as a capture of its own"))
+        far, pfar = run_chirp(dev, big, BIG, nfft, hop, S0 + s, n, rates)
         assert far.tobytes() == a.tobytes() and pfar.tobytes() == pa.tobytes(), ("gj_chirp_dev", nfft)
 
 
@@ -363,25 +357,20 @@ def test_excisors_past_byte_2_32(dev, big, res, nfft, chirp):
     d_rate = res(xr.parity_rates(nfft), np.int32) if chirp else None
     place(big, raw)
     with dev.capture(raw) as small:
-        near_b, near_r = xchirp_t.run(dev, small, small.nbytes, s, n, nfft, d_rate, d_thr, plain=not chirp)
-        (xchirp_t if chirp else excise_t).compare(near_b, near_r, want, (name, nfft, "the window as a capture of its own"))
-    far_b, far_r = xchirp_t.run(dev, big, BIG, S0 + s, n, nfft, d_rate, d_thr, plain=not chirp)
+        near_b, near_r = run_excise_chirp(dev, small, small.nbytes, s, n, nfft, d_rate, d_thr, plain=not chirp)
+        (xr if chirp else er).compare(near_b, near_r, want, (name, nfft, "the window as a capture of its own"))
+    far_b, far_r = run_excise_chirp(dev, big, BIG, S0 + s, n, nfft, d_rate, d_thr, plain=not chirp)
     assert far_b.tobytes() == near_b.tobytes() and far_r.tobytes() == near_r.tobytes(), (name, nfft)
     # one sample past the buffer's end: refused, nothing written
-    out, rec = dev.alloc(2 * n + 256), dev.alloc(near_r.size * xchirp_t.REC + 256)
+    out, rec = Guarded(dev, 2 * n), Guarded(dev, near_r.size * gpsjam.EXCISE_DTYPE.itemsize)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        rec.upload(np.full(rec.nbytes, SENTINEL, np.uint8))
         total = BIG // 2
-        for first in (total - n + 1, total):
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                if chirp:
-                    dev.excise_chirp_dev(big, BIG, first, n, nfft, d_rate, d_thr, out, rec)
-                else:
-                    dev.excise_dev(big, BIG, first, n, nfft, d_thr, out, rec)
-            assert e.value.status == GJ_ERR_INVALID, (name, nfft, first, e.value)
-        dev.synchronize()
-        assert np.all(out.download(np.uint8) == SENTINEL) and np.all(rec.download(np.uint8) == SENTINEL)
+
+        def launch(first):
+            if chirp:
+                dev.excise_chirp_dev(big, BIG, first, n, nfft, d_rate, d_thr, out, rec)
+            else:
+                dev.excise_dev(big, BIG, first, n, nfft, d_thr, out, rec)
+        refused(dev, launch, [((first,), GJ_ERR_INVALID) for first in (total - n + 1, total)], out, rec)
     finally:
-        out.free()
-        rec.free()
+        freed(out, rec)

@@ -20,12 +20,11 @@ import gpsjam
 import peaks_restatement as pr
 import subtract_restatement as sr
 from gpsjam import gnss, mitigate, spoof
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, PAD, SENTINEL, Guarded, freed, refused
+from gpu_lib import run_subtract as run
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes on either side of the output
 SIZES = (1, 15, 16, 17, 4095, 4096, 4097, 3 * 4096 + 5)
 INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
 
@@ -42,33 +41,6 @@ def d_codes(dev):
     b = dev.alloc(cr.parity_codes().nbytes).upload(cr.parity_codes())
     yield b
     b.free()
-
-
-def run(dev, capture, first, n, B, d_rows, n_rows, channels, amps, flags, seed, records=True, out_offset=0):
-    """(uint8[2 n], SUB_DTYPE[blocks] or None) through gj_subtract_dev into sentinel-filled buffers; ``out_offset``: bytes by
-    which d_out is moved off its 256-byte aligned place."""
-    rec = np.array(channels, gpsjam.CORR_CHANNEL_DTYPE)
-    amps = np.ascontiguousarray(amps, np.int32)
-    assert amps.shape == (len(channels), cr.blocks(n, B), 2)
-    size, rsize = 2 * n, 24 * sr.blocks(n)
-    out, d_rec, d_ch, d_amp = dev.alloc(PAD + out_offset + size + PAD), dev.alloc(PAD + rsize + PAD), dev.alloc(rec.nbytes), dev.alloc(amps.nbytes)
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        d_rec.upload(np.full(d_rec.nbytes, SENTINEL, np.uint8))
-        d_ch.upload(rec)
-        d_amp.upload(amps)
-        dev.subtract_dev(capture, capture.nbytes, first, n, B, d_rows, n_rows, d_ch, len(channels), d_amp, flags, seed,
-                         out.ptr + PAD + out_offset, d_rec.ptr + PAD if records else None)
-        got, got_rec = out.download(np.uint8), d_rec.download(np.uint8)
-    finally:
-        for b in (out, d_rec, d_ch, d_amp):
-            b.free()
-    lo = PAD + out_offset
-    assert np.all(got[:lo] == SENTINEL) and np.all(got[lo + size:] == SENTINEL), "bytes were written outside the call's output"
-    assert np.all(got_rec[:PAD] == SENTINEL) and np.all(got_rec[PAD + rsize:] == SENTINEL), "bytes were written outside the call's records"
-    if not records:
-        assert np.all(got_rec == SENTINEL), "no records were asked for"
-    return got[lo:lo + size], got_rec[PAD:PAD + rsize].view(gpsjam.SUB_DTYPE) if records else None
 
 
 def compare(dev, capture, raw, first, n, B, d_rows, codes, channels, amps, flags, seed, **how):
@@ -175,10 +147,8 @@ def test_refusals_and_a_bad_channel_write_nothing(dev, cap, d_codes):
     rec = np.array(channels, gpsjam.CORR_CHANNEL_DTYPE)
     n, B = 2 * 4096 + 5, 256
     amps = sr.random_amps(64, cr.blocks(n, B), 2 ** 14)
-    out, d_rec, d_ch, d_amp = dev.alloc(2 * n + PAD), dev.alloc(24 * 3 + PAD), dev.alloc(rec.nbytes + 8), dev.alloc(amps.nbytes + 8)
+    out, d_rec, d_ch, d_amp = Guarded(dev, 2 * n), Guarded(dev, 24 * 3), dev.alloc(rec.nbytes + 8), dev.alloc(amps.nbytes + 8)
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        d_rec.upload(np.full(d_rec.nbytes, SENTINEL, np.uint8))
         d_ch.upload(rec)
         d_amp.upload(amps)
         I, U = GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
@@ -201,14 +171,11 @@ def test_refusals_and_a_bad_channel_write_nothing(dev, cap, d_codes):
                  (dict(B=0), U), (dict(B=24), U), (dict(B=4112), U), (dict(B=-256), U),
                  (dict(n_ch=0), U), (dict(n_ch=65), U),
                  (dict(n=0), U), (dict(nbytes=2 ** 40, n=2 ** 28 + 1), U)]
-        for change, status in cases:
-            a = dict(ok, **change)
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.subtract_dev(a["d_iq"], a["nbytes"], a["first"], a["n"], a["B"], a["d_codes"], a["rows"], a["d_ch"], a["n_ch"],
-                                 a["d_amp"], a["flags"], a["seed"], a["d_out"], a["d_blocks"])
-            assert e.value.status == status, (change, e.value)
-            dev.synchronize()
-            assert np.all(out.download(np.uint8) == SENTINEL) and np.all(d_rec.download(np.uint8) == SENTINEL), change
+        def launch(a):
+            dev.subtract_dev(a["d_iq"], a["nbytes"], a["first"], a["n"], a["B"], a["d_codes"], a["rows"], a["d_ch"], a["n_ch"],
+                             a["d_amp"], a["flags"], a["seed"], a["d_out"], a["d_blocks"])
+        for change, status in cases:                         # nothing written behind each one of them
+            refused(dev, launch, [((dict(ok, **change),), status)], out, d_rec)
         assert cap.download().tobytes() == raw.tobytes(), "the capture is as it was"
         # channel fields live in device memory: the library cannot refuse them with a status, so the launch writes nothing
         bad = [(0, 1, 0, 0, 0, 1), (0, 1, 0, 0, 4, 0), (0, 1, 0, 0, -1, 0), (cr.PERIOD, 1, 0, 0, 0, 0), (0, 2 ** 34, 0, 0, 0, 0)]
@@ -219,7 +186,8 @@ def test_refusals_and_a_bad_channel_write_nothing(dev, cap, d_codes):
                 d_ch.upload(np.array(table, gpsjam.CORR_CHANNEL_DTYPE))
                 dev.subtract_dev(cap, cap.nbytes, 0, n, B, d_codes, 4, d_ch, 64, d_amp, 1, 0, out, d_rec)
                 dev.synchronize()
-                assert np.all(out.download(np.uint8) == SENTINEL) and np.all(d_rec.download(np.uint8) == SENTINEL), (ch, at)
+                out.check_untouched(f"channel {ch} at {at}, output")
+                d_rec.check_untouched(f"channel {ch} at {at}, records")
             # ... and the wrapper checks them on the host, before anything is uploaded
             with pytest.raises(gpsjam.GpsJamError) as e:
                 dev.subtract(cap, channels[:2] + [ch], codes, np.zeros((3, cr.blocks(cap.nsamples, 256), 2), np.int32))
@@ -230,10 +198,11 @@ def test_refusals_and_a_bad_channel_write_nothing(dev, cap, d_codes):
         dev.subtract_dev(cap, cap.nbytes, 0, 16, 16, d_codes, 4, d_ch, 64, d_amp, 1, 2 ** 32 - 1, out.ptr + 64, d_rec)
         dev.subtract_dev(out.ptr + 96, 64, 0, 16, 16, d_codes, 4, d_ch, 1, d_amp, 0, 0, out.ptr + 64, None)
         dev.synchronize()
-        assert np.all(out.download(np.uint8, out.nbytes - 96, 96) == SENTINEL) and np.all(d_rec.download(np.uint8, PAD, 24) == SENTINEL)
+        assert np.all(out.download(np.uint8, out.nbytes - 96 + PAD, 96) == SENTINEL) and np.all(d_rec.download(np.uint8, PAD, 24) == SENTINEL)
+        out.check_pads("output")
+        d_rec.check_pads("records")
     finally:
-        for b in (out, d_rec, d_ch, d_amp):
-            b.free()
+        freed(out, d_rec, d_ch, d_amp)
     # the next valid call gives the parity bytes, and a library refusal through the wrapper raises and leaves the capture alone
     compare(dev, cap, raw, 7, n, B, d_codes, codes, channels[:3], amps[:3], 1, 0)
     with pytest.raises(gpsjam.GpsJamError) as e:

@@ -12,7 +12,7 @@ from scipy import signal
 
 import caf_lengths_inputs as ci
 import caf_restatement as caf
-import test_gpu_parity as parity
+import k5_check as k5
 from gpsjam import _ffi
 
 HOST_MAX_L = 1 << 20
@@ -108,8 +108,8 @@ def test_a_planted_burst_keeps_its_lag_and_margin_under_a_bin():
     for b in ci.plant_bins(n):
         rng = np.random.default_rng(n + b)
         low = 1.0
-        for lag in parity.k5_edge_lags(n):
-            s0, s1 = parity.k5_planted(n, lag, rng, width=1 if abs(lag) >= n - 2 else None)
+        for lag in k5.k5_edge_lags(n):
+            s0, s1 = k5.k5_planted(n, lag, rng, width=1 if abs(lag) >= n - 2 else None)
             Z0, Z1 = ci.spectrum(s0), ci.spectrum(s1)
             fwd, rev = ci.bin_of_spectra(Z1, Z0, b, n), ci.bin_of_spectra(Z0, Z1, b, n)
             assert (fwd.lag, rev.lag) == (lag, -lag), (b, lag, fwd, rev)
@@ -117,7 +117,7 @@ def test_a_planted_burst_keeps_its_lag_and_margin_under_a_bin():
         print(f"n = {n} bin {b}: smallest margin of a planted peak {low:.4f} (needs {ci.GAP:g})")
         assert low > ci.GAP
     assert ci.plant_bins(n) == [17, -1] and ci.plant_bins(ci.PLANT_N[1]) == [2049, -1]
-    assert ci.PLANT_N == parity.K5_PLANT_N
+    assert ci.PLANT_N == k5.K5_PLANT_N
 
 
 # ------------------------------------------------------------------ 3: the clip, on the host

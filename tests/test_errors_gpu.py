@@ -6,10 +6,9 @@ import pytest
 
 import gpsjam
 from gpsjam.synth import StreamSpec, generate
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
 
 pytestmark = pytest.mark.gpu
-
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5
 
 
 def test_bad_parameters_are_reported_and_context_survives(dev):

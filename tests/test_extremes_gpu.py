@@ -152,7 +152,7 @@ import contextlib
 
 import blank_restatement as br
 import exact_restatement as ex
-from blank import test_round6_gpu as blank_t
+from gpu_lib import run_blank
 
 END_OFFSETS = (0.0, 0.5, 254.5, 255.0)
 E_MAX = 2 * 510 ** 2                       # 520 200
@@ -316,8 +316,8 @@ def test_end_offsets_blanker(dev, name, window, guard):
                     thresholds = [0.0, float(at), np.inf] + ([float(np.nextafter(at, np.float32(0)))] if e_max else [])
                     for thr in thresholds:
                         want = br.blank(raw, thr, window, guard, first, n, offset)
-                        got, rec = blank_t.run(dev, c, c.nbytes, first, n, window, guard, thr)
-                        blank_t.compare(got, rec, want, (name, window, guard, offset, first, n, thr))
+                        got, rec = run_blank(dev, c, c.nbytes, first, n, window, guard, thr)
+                        br.compare(got, rec, want, (name, window, guard, offset, first, n, thr))
                         if loudest:
                             assert int(want.records["total"].max()) == 4096 * E_MAX < 2 ** 32
                         if constant and e_max and thr == float(at):       # S = T in the interior, and the comparison is strict

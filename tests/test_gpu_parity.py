@@ -314,10 +314,6 @@ def test_k5_device_starts_and_invalid(dev, golden_meta, g4_raws):
 # (xc_cols_kernel<L1, MODE>, L1 = 16 .. 4096: k_xcorr.hip xc_cols); each is run at both edges of its bucket, N = L/4 + 1
 # and N = L/2, plus an odd N inside the buckets no other test reaches.  N = 2^23 (L = 2^24) is the largest slice the
 # library accepts.  Every pair is held to the oracle's lag and the float64 restatement (tests/k5_check.py).
-def k5_fft_len(n: int) -> int:
-    return max(1 << 16, 1 << (2 * n - 2).bit_length())
-
-
 K5_LENGTHS = sorted([(L, n) for L in (1 << p for p in range(16, 25)) for n in (L // 4 + 1, L // 2)]
                     + [(1 << 19, 200_001), (1 << 22, 1_500_001), (1 << 23, 3_000_001), (1 << 24, 6_000_001)])
 K5_DELAYS = (0, 37, -1234)
@@ -341,7 +337,7 @@ def k5_expect_all(raws, pairs):
 
 @pytest.mark.parametrize("L,n", K5_LENGTHS, ids=[f"L1={L // 4096}-n={n}" for L, n in K5_LENGTHS])
 def test_k5_every_fft_length(dev, L, n):
-    assert k5_fft_len(n) == L
+    assert k5.k5_fft_len(n) == L
     raws = [r[:2 * n] for r in k5_streams()]
     if L < (1 << 22):
         pairs = [(0, 1), (1, 0), (0, 2), (2, 1), (1, 1)]
@@ -355,51 +351,11 @@ def test_k5_every_fft_length(dev, L, n):
         assert lag == K5_DELAYS[p[1]] - K5_DELAYS[p[0]]
 
 
-def k5_planted(n: int, lag: int, rng, second_lag=None, width=None, at=None):
-    """(sig0, sig1), n samples each: low-level noise (bytes 127 / 128: +-0.5 after unpack) and one burst of rail values
-    (0 / 255: +-127.5), 1..16 samples long, at the two places whose overlap is `lag` -- the correlation peak
-    (correlate(sig1, sig0) peaks where sig1 is sig0 delayed by `lag`).  ``second_lag``: a copy at 0.8 amplitude
-    (bytes 25 / 230) in sig1 as well, whose overlap is that lag -- a deliberate runner-up.  ``at``: the burst's place in
-    sig0 (default: random)."""
-    w = int(width or rng.integers(1, 17))
-    w = min(w, n - abs(lag))
-    sig = [rng.integers(127, 129, size=2 * n, dtype=np.uint8) for _ in range(2)]
-    if at is not None:
-        p0 = at
-    elif lag >= 0:
-        p0 = int(rng.integers(0, n - w - lag + 1))
-    else:
-        p0 = int(rng.integers(0, n - w + lag + 1)) - lag
-    burst = rng.integers(0, 2, size=2 * w, dtype=np.uint8)
-    assert 0 <= p0 <= n - w and 0 <= p0 + lag <= n - w
-    sig[0][2 * p0:2 * (p0 + w)] = burst * 255
-    sig[1][2 * (p0 + lag):2 * (p0 + lag + w)] = burst * 255
-    if second_lag is not None:
-        q = p0 + second_lag
-        assert 0 <= q <= n - w and (q + w <= p0 + lag or q >= p0 + lag + w)
-        sig[1][2 * q:2 * (q + w)] = np.where(burst == 1, 230, 25).astype(np.uint8)
-    return sig[0], sig[1]
-
-
-def k5_edge_lags(n: int):
-    """Peaks at both ends of the 'full' range (circular index N-1 and L-N+1, the last ones before the zero-padding
-    band), at 0, on both sides of a 4096-point row (the column index n2 = lag mod 4096 is 4095, 0, 1), at the first
-    and last rows that hold a lag, and at the edge of a column kernel's tile of B = 4096 / L1 columns."""
-    B = 4096 // (k5_fft_len(n) // 4096)
-    K = (n - 2) // 4096
-    lags = {n - 1, -(n - 1), n - 2, -(n - 2), 0, 4095, 4096, 4097, -4095, -4096, -4097, 4096 * K - 1, -(4096 * K + 1),
-            B - 1, B, -B}
-    return sorted(x for x in lags if abs(x) <= n - 1)
-
-
-K5_PLANT_N = [32768, (1 << 22) - 3]      # L1 = 16 (L = 2N: a one-point padding band), L1 = 2048
-
-
-@pytest.mark.parametrize("n", K5_PLANT_N)
+@pytest.mark.parametrize("n", k5.K5_PLANT_N)
 def test_k5_peak_anywhere_in_the_lag_range(dev, n):
     rng = np.random.default_rng(n)
-    for lag in k5_edge_lags(n):
-        s0, s1 = k5_planted(n, lag, rng, width=1 if abs(lag) >= n - 2 else None)
+    for lag in k5.k5_edge_lags(n):
+        s0, s1 = k5.k5_planted(n, lag, rng, width=1 if abs(lag) >= n - 2 else None)
         lags, peaks, margins = dev.xcorr_lags([s0, s1], [(0, 1), (1, 0)], want_margins=True)
         e = k5.expect(s0, s1)
         assert e["lag"] == lag
@@ -407,13 +363,13 @@ def test_k5_peak_anywhere_in_the_lag_range(dev, n):
         k5.check(lags[1], peaks[1], margins[1], k5.mirror(e), f"n={n} lag={-lag} (reversed)")
 
 
-@pytest.mark.parametrize("n", K5_PLANT_N)
+@pytest.mark.parametrize("n", k5.K5_PLANT_N)
 def test_k5_strong_runner_up(dev, n):
     """A second copy at 0.8 amplitude at a lag of the other sign: margin ~0.2, so a runner-up lost in any stage of the
     arg-max (lane, wave, workgroup, the pair's last workgroup) shows."""
     rng = np.random.default_rng(n + 1)
     for lag, lag2, at in ((4097, -(n // 3), n // 2), (-(n // 2 - 17), 1, n // 2 + 100)):
-        s0, s1 = k5_planted(n, lag, rng, second_lag=lag2, width=16, at=at)
+        s0, s1 = k5.k5_planted(n, lag, rng, second_lag=lag2, width=16, at=at)
         lags, peaks, margins = dev.xcorr_lags([s0, s1], [(0, 1), (1, 0)], want_margins=True)
         e = k5.expect(s0, s1)
         assert e["lag"] == lag and 0.15 < e["margin"] < 0.25

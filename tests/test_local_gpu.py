@@ -20,7 +20,7 @@ if HERE not in sys.path:
 @pytest.mark.parametrize("name", ["g3", "g4", "syn3", "g1"])
 def test_local_antennas_are_bit_identical_to_single_streams(dev, name, graph):
     import torch
-    import test_split_gpu as sg
+    import split_scenarios as sg
     from gpsjam import local
     caps, kw = sg.scenarios()[name]
     work = torch.cuda.Stream()
@@ -51,7 +51,7 @@ def test_local_antennas_are_bit_identical_to_single_streams(dev, name, graph):
 def test_local_antennas_from_files(dev, tmp_path):
     """The same from capture FILES (uploaded once, resident): three antennas at the reference's slice size."""
     import torch
-    import test_split_gpu as sg
+    import split_scenarios as sg
     from gpsjam import local
     from gpsjam.synth import StreamSpec, generate
     n = 900_000

@@ -10,13 +10,12 @@ from gpsjam import _ffi
 from gpsjam.synth import StreamSpec, generate
 from oracle import gpsjam_oracle as orc
 import exact_restatement as ex
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
 
 pytestmark = pytest.mark.gpu
 
-NOISE, WINDOW, FACTOR = 200000, 1000, 50.0
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5
-ONSET_T = np.dtype([("start", "<i8"), ("noise", "<f4"), ("thr", "<f4"), ("hit", "<f4"), ("before", "<f4"), ("guard", "<i8")])
-AMP_T = np.dtype([("i", "<i8"), ("c", "<u8"), ("s", "<f8"), ("m", "<f4"), ("r", "<f4")])
+NOISE, WINDOW, FACTOR = ex.NOISE, ex.WINDOW, ex.FACTOR
+ONSET_T, AMP_T = ex.ONSET_T, ex.AMP_T
 
 
 def _alone(dev, ptr, nbytes, thr, noise=NOISE, window=WINDOW):
@@ -29,16 +28,6 @@ def _alone(dev, ptr, nbytes, thr, noise=NOISE, window=WINDOW):
     return out
 
 
-def _check_exact(amp_bytes, on_bytes, raw, thr, noise=NOISE, window=WINDOW):
-    a, o = np.frombuffer(amp_bytes, AMP_T)[0], np.frombuffer(on_bytes, ONSET_T)[0]
-    want_a, want_o = ex.amp_stats(raw, thr), ex.onset(raw, noise, window, FACTOR)
-    assert (a["i"], a["c"]) == (want_a["first"], want_a["count"])
-    np.testing.assert_allclose(a["s"], want_a["sum"], rtol=2e-7)
-    np.testing.assert_allclose(a["m"], want_a["mean"], rtol=2e-7)
-    for f in ("start", "guard", "noise", "thr", "hit"):
-        assert o[f] == want_o[f], (f, o, want_o)
-
-
 @pytest.mark.parametrize("nbytes,thr,jam", [(20 * 65536 + 24691, 0.0, 220000), (20 * 65536 + 24690, 0.45, 220000), (7 * 65536, 0.1, 210000),
                                             (2 * (NOISE + WINDOW), 0.0, 1 << 40), (2 * (NOISE + WINDOW) - 2, 0.3, 1 << 40),
                                             (3, 0.0, 0), (2, 0.0, 0), (1, 0.0, 0), (0, 0.0, 0), (40_960_000, 0.0, 9_000_000)])
@@ -49,7 +38,7 @@ def test_k3_k4_alone_are_the_fused_pass(dev, nbytes, thr, jam):
     raw = generate(StreamSpec(seed=(nbytes & 0xffff) + 1, jam_start=jam, jam_end=1 << 40, jam_sigma=60.0), max(n, 1))[:nbytes]
     buf = dev.alloc(max(nbytes, 16)).upload(raw) if nbytes else dev.alloc(16)
     amp_b, on_b = _alone(dev, buf, nbytes, thr)
-    _check_exact(amp_b, on_b, raw, thr)
+    ex.check_exact(amp_b, on_b, raw, thr)
     if 0 < nbytes <= 3_000_000:
         even = raw[:2 * (nbytes // 2)]
         assert np.frombuffer(on_b, ONSET_T)[0]["start"] == orc.tdoa_onset(orc.tdoa_unpack(even))
@@ -83,7 +72,7 @@ def test_k3_k4_alone_on_captures_that_are_not_16_byte_aligned(dev, off):
     buf = dev.alloc(nbytes + off + 16).upload(raw)
     piece = raw[off:off + nbytes]
     amp_b, on_b = _alone(dev, buf.ptr + off, nbytes, 0.2)
-    _check_exact(amp_b, on_b, piece, 0.2)
+    ex.check_exact(amp_b, on_b, piece, 0.2)
     assert np.frombuffer(on_b, ONSET_T)[0]["start"] == orc.tdoa_onset(orc.tdoa_unpack(piece[:2 * (nbytes // 2)]))
     aligned = dev.alloc(nbytes + 16).upload(piece)
     amp_a, on_a = _alone(dev, aligned, nbytes, 0.2)
@@ -172,7 +161,7 @@ def test_sweep_k3_k4_alone(dev, case):
     buf = dev.alloc(nbytes + off + 16).upload(raw)
     piece = raw[off:off + nbytes]
     amp_b, on_b = _alone(dev, buf.ptr + off, nbytes, thr, noise=noise, window=window)
-    _check_exact(amp_b, on_b, piece, thr, noise=noise, window=window)
+    ex.check_exact(amp_b, on_b, piece, thr, noise=noise, window=window)
     even = piece[:2 * ns]
     got_on = np.frombuffer(on_b, ONSET_T)[0]
     if window <= 1001 or ns <= 600_000:                       # the oracle's np.convolve is O(n * window)

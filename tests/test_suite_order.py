@@ -1,7 +1,11 @@
 """The GPU suite runs core-first (tests/conftest.py SUITE_ORDER): the driver's `pytest -x -m gpu` must reach the oracle
 parity tests of K1-K5 and of the BASELINE configs before anything that spawns processes or kills threads, so that one
 peripheral failure cannot hide the hot path (GPUTEST_r04: red at test 15 of 374, 359 unreached).  Ordering only --
-nothing may be deselected, skipped or expected to fail."""
+nothing may be deselected, skipped or expected to fail.
+
+No test module is another's library: what two of them share stands in a module that holds no tests (tests/gpu_lib.py,
+tests/host_lib.py, the restatements and inputs), so that editing a test file changes what that file asserts and nothing else."""
+import ast
 import os
 import re
 import subprocess
@@ -72,3 +76,20 @@ def test_cpu_suite_is_unchanged_by_the_ordering():
         if not files or files[-1] != f:
             files.append(f)
     assert files == sorted(files), "CPU tests keep pytest's default (alphabetical by file) order"
+
+
+def test_no_module_imports_a_test_module():
+    """Every .py under tests/, imports inside functions included."""
+    hits = []
+    for root, _, names in os.walk(os.path.join(REPO, "tests")):
+        for f in sorted(n for n in names if n.endswith(".py")):
+            path = os.path.join(root, f)
+            for node in ast.walk(ast.parse(open(path).read(), path)):
+                if isinstance(node, ast.Import):
+                    mods = [a.name for a in node.names]
+                elif isinstance(node, ast.ImportFrom):
+                    mods = [node.module or ""] + [f"{node.module or ''}.{a.name}" for a in node.names]
+                else:
+                    continue
+                hits += [f"{os.path.relpath(path, REPO)}:{node.lineno}: {m}" for m in mods if any(p.startswith("test_") for p in m.split("."))]
+    assert hits == [], hits

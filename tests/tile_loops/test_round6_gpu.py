@@ -29,12 +29,10 @@ import gpsjam
 import subtract_restatement as sr
 import tile_loops_inputs as tl
 from gpsjam.synth import StreamSpec, generate
+from gpu_lib import GJ_ERR_INVALID, Guarded, freed, refused, run_align, run_corr, run_fine, run_subtract
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID = -1                             # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes on either side of an output
 
 # workgroups per CU of each grid as it is launched today
 ALIGN_PER_CU = 4                                # k_align.hip gj_align_dev: slots = 4ull * num_cus
@@ -46,46 +44,6 @@ SYNTH_PER_CU = 32                               # k_synth.hip launch_synth: bloc
 TAPS = (0, -64, 33)
 FIRST = 7                                       # an odd first sample
 FINE_FIRST_A, FINE_FIRST_B = 5, 4107            # odd, and different
-
-
-class Guarded:
-    """``nbytes`` of device memory between two runs of PAD sentinel bytes, ``offset`` bytes off its 256-byte aligned
-    place; filled with the sentinel too unless the test never reads what the call leaves unwritten."""
-
-    def __init__(self, dev, nbytes, offset=0, fill=True):
-        self.nbytes, self.lo = int(nbytes), PAD + int(offset)
-        self.buf = dev.alloc(self.lo + self.nbytes + PAD)
-        if fill:
-            self.buf.upload(np.full(self.buf.nbytes, SENTINEL, np.uint8))
-        else:
-            self.buf.upload(np.full(self.lo, SENTINEL, np.uint8))
-            self.buf.upload(np.full(PAD, SENTINEL, np.uint8), offset=self.lo + self.nbytes)
-
-    @property
-    def ptr(self):
-        return self.buf.ptr + self.lo
-
-    def read(self, dtype=np.uint8, count=None, offset=0):
-        if count is None:
-            count = (self.nbytes - offset) // np.dtype(dtype).itemsize
-        assert 0 <= offset and offset + count * np.dtype(dtype).itemsize <= self.nbytes
-        return self.buf.download(dtype, count, self.lo + offset)
-
-    def check_pads(self, what):
-        front, back = self.buf.download(np.uint8, self.lo, 0), self.buf.download(np.uint8, PAD, self.lo + self.nbytes)
-        assert np.all(front == SENTINEL) and np.all(back == SENTINEL), f"bytes were written outside the call's {what}"
-
-    def check_untouched(self, what):
-        assert np.all(self.buf.download(np.uint8) == SENTINEL), f"{what}: bytes were written"
-
-    def free(self):
-        self.buf.free()
-
-
-def freed(*bufs):
-    for b in bufs:
-        if b is not None:
-            b.free()
 
 
 @pytest.fixture(scope="module")
@@ -126,70 +84,6 @@ def d_tables(dev):
     yield held
     for pair in held.values():
         freed(*pair)
-
-
-# ------------------------------------------------------------------------------------------------ the calls
-def run_align(dev, d_iq, nbytes, case, d_taps, d_rot, n_out, records=True, out_offset=0):
-    """(uint8[2 n_out], ALIGN_DTYPE[blocks] or None) through gj_align_dev."""
-    out, rec = Guarded(dev, 2 * n_out, out_offset), Guarded(dev, 16 * ar.blocks(n_out))
-    try:
-        dev.align_dev(d_iq, nbytes, case, d_taps, d_rot, n_out, out.ptr, rec.ptr if records else None)
-        out.check_pads("output")
-        if records:
-            rec.check_pads("records")
-        else:
-            rec.check_untouched("no records were asked for")
-        return out.read(), rec.read(gpsjam.ALIGN_DTYPE) if records else None
-    finally:
-        freed(out, rec)
-
-
-def run_subtract(dev, capture, nbytes, first, n, B, d_rows, n_rows, channels, amps, flags, seed, records=True, out_offset=0):
-    """(uint8[2 n], SUB_DTYPE[blocks] or None) through gj_subtract_dev."""
-    table = np.array(channels, gpsjam.CORR_CHANNEL_DTYPE)
-    amps = np.ascontiguousarray(amps, np.int32)
-    assert amps.shape == (len(channels), cr.blocks(n, B), 2)
-    out, rec = Guarded(dev, 2 * n, out_offset), Guarded(dev, 24 * sr.blocks(n))
-    d_ch, d_amp = dev.alloc(table.nbytes).upload(table), dev.alloc(amps.nbytes).upload(amps)
-    try:
-        dev.subtract_dev(capture, nbytes, first, n, B, d_rows, n_rows, d_ch, len(channels), d_amp, flags, seed, out.ptr, rec.ptr if records else None)
-        out.check_pads("output")
-        if records:
-            rec.check_pads("records")
-        else:
-            rec.check_untouched("no records were asked for")
-        return out.read(), rec.read(gpsjam.SUB_DTYPE) if records else None
-    finally:
-        freed(out, rec, d_ch, d_amp)
-
-
-def run_corr(dev, capture, nbytes, first, n, B, d_rows, n_rows, channels, taps):
-    """int32[n_channels][blocks][n_taps][2] through gj_corr_bank_dev."""
-    table = np.array(channels, gpsjam.CORR_CHANNEL_DTYPE)
-    out = Guarded(dev, 8 * len(channels) * gpsjam.corr_blocks(n, B) * len(taps))
-    d_ch = dev.alloc(table.nbytes).upload(table)
-    try:
-        dev.corr_bank_dev(capture, nbytes, first, n, B, d_rows, n_rows, d_ch, len(channels), taps, out.ptr)
-        out.check_pads("records")
-        return out.read(np.int32).reshape(len(channels), -1, len(taps), 2)
-    finally:
-        freed(out, d_ch)
-
-
-def run_fine(dev, a, nbytes_a, first_a, b, nbytes_b, first_b, n, centre, half, records=True):
-    """(total int64[2R+1][2], blocks int32[nb][2R+1][2] or None) through gj_xcorr_fine_dev."""
-    nl, nb = 2 * half + 1, gpsjam.fine_blocks(n)
-    tot, rec = Guarded(dev, 16 * nl), Guarded(dev, 8 * nl * nb)
-    try:
-        dev.xcorr_fine_dev(a, nbytes_a, first_a, b, nbytes_b, first_b, n, centre, half, tot.ptr, rec.ptr if records else None)
-        tot.check_pads("totals")
-        if records:
-            rec.check_pads("records")
-        else:
-            rec.check_untouched("no records were asked for")
-        return tot.read(np.int64).reshape(nl, 2), rec.read(np.int32).reshape(nb, nl, 2) if records else None
-    finally:
-        freed(tot, rec)
 
 
 def same_bytes(got, want, what):
@@ -239,10 +133,10 @@ def test_subtract_where_every_workgroup_takes_a_second_tile(dev, cus, raws, caps
     amps = sr.random_amps(3, cr.blocks(n, B), 2 ** 14, seed=B)
     what = f"subtract n {n} B {B} flags {flags} seed {seed}"
     want, wrec = sr.subtract(raws[0], FIRST, n, B, codes, channels, amps, flags, seed)
-    got, rec = run_subtract(dev, caps[0], caps[0].nbytes, FIRST, n, B, d_codes, len(codes), channels, amps, flags, seed)
+    got, rec = run_subtract(dev, caps[0], FIRST, n, B, d_codes, len(codes), channels, amps, flags, seed)
     same_bytes(got, want, what)
     same_records(rec, wrec, what)
-    bare, none = run_subtract(dev, caps[0], caps[0].nbytes, FIRST, n, B, d_codes, len(codes), channels, amps, flags, seed, records=False, out_offset=2)
+    bare, none = run_subtract(dev, caps[0], FIRST, n, B, d_codes, len(codes), channels, amps, flags, seed, records=False, out_offset=2)
     assert none is None
     same_bytes(bare, want, what + " records off, output 2 bytes off alignment")
 
@@ -256,10 +150,10 @@ def test_fine_where_every_workgroup_takes_a_second_tile(dev, cus, raws, caps, ce
     a, b = caps
     what = f"fine n {n} centre {centre} half {half}"
     want = fr.fine(raws[0], raws[1], centre, half, FINE_FIRST_A, FINE_FIRST_B, n)
-    total, blocks = run_fine(dev, a, a.nbytes, FINE_FIRST_A, b, b.nbytes, FINE_FIRST_B, n, centre, half)
+    total, blocks = run_fine(dev, a, b, FINE_FIRST_A, FINE_FIRST_B, n, centre, half)
     same_records(blocks.astype(np.int64), want.blocks, what)
     np.testing.assert_array_equal(total, want.total, err_msg=what + ": the 64-bit sums over a workgroup's tiles")
-    bare, none = run_fine(dev, a, a.nbytes, FINE_FIRST_A, b, b.nbytes, FINE_FIRST_B, n, centre, half, records=False)
+    bare, none = run_fine(dev, a, b, FINE_FIRST_A, FINE_FIRST_B, n, centre, half, want_blocks=False)
     assert none is None
     np.testing.assert_array_equal(bare, want.total, err_msg=what + " without records")
 
@@ -274,7 +168,7 @@ def test_corr_where_every_workgroup_takes_a_second_tile(dev, cus, raws, caps, d_
     print(f"{cus} CUs: {-(-cr.blocks(n, B) // tile_blocks)} tiles of {tl.corr_tile(B)} on {CORR_PER_CU * cus} workgroups")
     codes, channels = cr.parity_codes(), cr.parity_channels(4)
     want = cr.bank(raws[0], 1, n, B, codes, channels, TAPS)
-    got = run_corr(dev, caps[0], caps[0].nbytes, 1, n, B, d_codes, len(codes), channels, TAPS)
+    got = run_corr(dev, caps[0], 1, n, B, d_codes, len(codes), channels, TAPS)
     for ch in range(4):
         same_records(got[ch].astype(np.int64), want[ch], f"corr n {n} B {B} channel {ch} (records of {tile_blocks} to a tile)")
 
@@ -345,7 +239,7 @@ class TestPastByte2To32:
         near, _ = sr.subtract(np.concatenate((np.zeros(2, np.uint8), window[:2 * FAR_SAMPLES])), 1, FAR_SAMPLES, 256, codes, channels, amps,
                               sr.DITHER, seed)
         assert near.tobytes() != want.tobytes(), "the same bytes from sample 1: the upper word of the key is seen"
-        got, rec = run_subtract(dev, buf, BIG, S0, FAR_SAMPLES, 256, d_codes, len(codes), channels, amps, sr.DITHER, seed)
+        got, rec = run_subtract(dev, buf, S0, FAR_SAMPLES, 256, d_codes, len(codes), channels, amps, sr.DITHER, seed)
         same_bytes(got, want, "subtract past sample 2^31")
         same_records(rec, wrec, "subtract past sample 2^31")
 
@@ -354,11 +248,11 @@ class TestPastByte2To32:
         codes, channels = cr.parity_codes(), cr.parity_channels(4)
         for B in (48, 4096):
             want = cr.bank(window, 0, FAR_SAMPLES, B, codes, channels, TAPS)
-            got = run_corr(dev, buf, BIG, S0, FAR_SAMPLES, B, d_codes, len(codes), channels, TAPS)
+            got = run_corr(dev, buf, S0, FAR_SAMPLES, B, d_codes, len(codes), channels, TAPS)
             same_records(got.astype(np.int64).reshape(-1, 2 * len(TAPS)), want.reshape(-1, 2 * len(TAPS)), f"corr past sample 2^31, B {B}")
         for centre, half in ((3, 2), (-4099, 16)):
             want = fr.fine(window, window, centre, half, 0, FAR_B - S0, FAR_SAMPLES)
-            total, blocks = run_fine(dev, buf, BIG, S0, buf, BIG, FAR_B, FAR_SAMPLES, centre, half)
+            total, blocks = run_fine(dev, buf, buf, S0, FAR_B, FAR_SAMPLES, centre, half)
             same_records(blocks.astype(np.int64), want.blocks, f"fine past sample 2^31, centre {centre}")
             np.testing.assert_array_equal(total, want.total)
 
@@ -377,13 +271,7 @@ class TestPastByte2To32:
                     "fine, range a": lambda: dev.xcorr_fine_dev(buf, BIG, first, buf, BIG, S0, FAR_SAMPLES, 0, 2, out.ptr, rec.ptr),
                     "fine, range b": lambda: dev.xcorr_fine_dev(buf, BIG, S0, buf, BIG, first, FAR_SAMPLES, 0, 2, out.ptr, rec.ptr),
                 }
-                for name, call in calls.items():
-                    with pytest.raises(gpsjam.GpsJamError) as e:
-                        call()
-                    assert e.value.status == GJ_ERR_INVALID, (name, first, e.value)
-            dev.synchronize()
-            out.check_untouched("refused calls")
-            rec.check_untouched("refused calls")
+                refused(dev, lambda name: calls[name](), [((name,), GJ_ERR_INVALID) for name in calls], out, rec)
             # the last range that fits is taken
             dev.corr_bank_dev(buf, BIG, BIG // 2 - FAR_SAMPLES, FAR_SAMPLES, 256, d_codes, len(codes), d_ch, 3, TAPS, rec.ptr)
             dev.synchronize()

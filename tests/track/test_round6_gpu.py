@@ -16,12 +16,12 @@ import corr_restatement as cr
 import gpsjam
 import track_restatement as tr
 from gpsjam import gnss, postcorr, track
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, SENTINEL, Guarded, freed, refused
+from gpu_lib import run_track as run
+from gpu_lib import track_state_records as to_records
 
 pytestmark = pytest.mark.gpu
 
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5     # include/gpsjam.h gj_status
-SENTINEL = 0xA5
-PAD = 256                                       # sentinel bytes behind the records and behind the states
 EPOCH, STATE = gpsjam.TRACK_EPOCH_DTYPE, gpsjam.TRACK_STATE_DTYPE
 G = tr.MAX_GAIN
 WIDE = tr.gains(*tr.WIDE, 2048, cr.FS)          # (1, 1540, ...)
@@ -40,33 +40,6 @@ def d_codes(dev):
     b = dev.alloc(cr.parity_codes().nbytes).upload(cr.parity_codes())
     yield b
     b.free()
-
-
-def to_records(states):
-    rec = np.zeros(len(states), STATE)
-    for k, s in enumerate(states):
-        rec[k] = (tuple(s[:6]), s[6], s[7], s[8], s[9], s[10], tuple(s[11:13]))
-    return rec
-
-
-def run(dev, capture, first, n, B, n_epochs, d_rows, n_rows, states, params):
-    """(record bytes uint8[n_channels][n_epochs * 56], states after as tuples) through gj_track_dev; both buffers are
-    sentinel-filled and their pads checked."""
-    rec = to_records(states)
-    size = EPOCH.itemsize * len(states) * n_epochs
-    out, d_st = dev.alloc(size + PAD), dev.alloc(rec.nbytes + PAD)
-    try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
-        d_st.upload(np.full(d_st.nbytes, SENTINEL, np.uint8))
-        d_st.upload(rec)
-        dev.track_dev(capture, capture.nbytes, first, n, B, n_epochs, d_rows, n_rows, d_st, len(states), params, out)
-        got, st = out.download(np.uint8), d_st.download(np.uint8)
-    finally:
-        out.free()
-        d_st.free()
-    assert np.all(got[size:] == SENTINEL), "bytes were written behind the call's records"
-    assert np.all(st[rec.nbytes:] == SENTINEL), "bytes were written behind the call's states"
-    return got[:size].reshape(len(states), -1), tr.states_as_tuples(st[:rec.nbytes].view(STATE))
 
 
 def compare(dev, capture, raw, first, n, B, n_epochs, d_rows, codes, states, params):
@@ -194,14 +167,13 @@ def test_refusals_enqueue_nothing(dev, cap, d_codes):
     states = spread_states(3, n, E, B)
     rec = to_records(states)
     size = EPOCH.itemsize * 3 * E
-    out, d_st = dev.alloc(size + PAD), dev.alloc(rec.nbytes + 8)
+    out, d_st = Guarded(dev, size), dev.alloc(rec.nbytes + 8)
     P = WIDE
 
     def with_(at, v):
         return P[:at] + (v,) + P[at + 1:]
 
     try:
-        out.upload(np.full(out.nbytes, SENTINEL, np.uint8))
         d_st.upload(np.concatenate([rec.view(np.uint8), np.zeros(8, np.uint8)]))
         I, U = GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED
         reserved = gpsjam.TrackParams(*P, 1)
@@ -240,23 +212,17 @@ def test_refusals_enqueue_nothing(dev, cap, d_codes):
         for at in range(2, 7):                                                                     # a gain beyond +-2^30
             cases.append((cap, cap.nbytes, 0, n, B, E, d_codes, 4, d_st, 3, with_(at, G + 1), out, U))
             cases.append((cap, cap.nbytes, 0, n, B, E, d_codes, 4, d_st, 3, with_(at, -G - 1), out, U))
-        for d_iq, nbytes, first, ns, bs, ne, d_rows, rows, d_s, n_ch, params, d_o, status in cases:
-            with pytest.raises(gpsjam.GpsJamError) as e:
-                dev.track_dev(d_iq, nbytes, first, ns, bs, ne, d_rows, rows, d_s, n_ch, params, d_o)
-            what = (first, ns, bs, ne, rows, n_ch, params if isinstance(params, tuple) else "reserved")
-            assert e.value.status == status, (what, e.value)
-            dev.synchronize()
-            assert np.all(out.download(np.uint8) == SENTINEL), what
-            assert d_st.download(np.uint8, rec.nbytes).tobytes() == rec.tobytes(), what
+        for c in cases:                                      # nothing written behind each one of them, the states as they were
+            refused(dev, dev.track_dev, [(c[:-1], c[-1])], out)
+            assert d_st.download(np.uint8, rec.nbytes).tobytes() == rec.tobytes(), c[2:8]
         # accepted: the limits themselves
         dev.track_dev(cap, cap.nbytes, cap.nsamples - 16, 16, 16, 1, d_codes, 4, d_st, 1, (64, 0, G, -G, G, -G, G), out)
         d_st.upload(rec)
         dev.track_dev(cap, cap.nbytes, 0, 4096, 4096, 1, d_codes, 4, d_st, 1, (1, 2 ** 31 - 1, -G, G, -G, G, -G), out)
         dev.synchronize()
-        assert np.all(out.download(np.uint8, PAD, size) == SENTINEL)
+        out.check_pads("records")
     finally:
-        out.free()
-        d_st.free()
+        freed(out, d_st)
     # the next valid call gives the parity bits, and a library refusal through the wrapper raises and leaves the capture alone
     compare(dev, cap, raw, 7, n + 5, B, E, d_codes, codes, states, P)
     with pytest.raises(gpsjam.GpsJamError) as e:

@@ -18,6 +18,9 @@ import pytest
 import caf_restatement as caf
 import gpsjam
 from gpsjam import _ffi
+from gpu_lib import CAF_REC as REC
+from gpu_lib import GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED, LAG_INVALID as INVALID, ResidentSlices as Resident, as_k5, make_slots
+from gpu_lib import caf_records as records
 
 pytestmark = pytest.mark.gpu
 
@@ -26,68 +29,8 @@ SKRYPTY = os.path.join(os.path.dirname(os.path.dirname(HERE)), "gps-jamming_amd"
 if SKRYPTY not in sys.path:
     sys.path.insert(0, SKRYPTY)
 
-REC = C.sizeof(_ffi.CafResult)
-GJ_ERR_INVALID, GJ_ERR_UNSUPPORTED = -1, -5    # include/gpsjam.h gj_status
-INVALID = _ffi.GJ_LAG_INVALID
-P3 = [(0, 1), (0, 2), (1, 2)]
-P7 = P3 + [(1, 0), (2, 0), (0, 0), (2, 2)]     # more than 2 x antennas: K5's many-pair path
+P3, P7 = caf.P3, caf.P7
 FIRST, NBINS = caf.BINS_REF
-
-
-def records(raw: bytes):
-    return [_ffi.CafResult.from_buffer_copy(raw[k:k + REC]) for k in range(0, len(raw), REC)]
-
-
-class Resident:
-    """Slices resident in HBM with their start words and output buffers for one shape of call."""
-
-    def __init__(self, dev, raws, n, n_pairs, n_bins, starts=None):
-        self.dev, self.n, self.n_pairs, self.n_bins = dev, n, n_pairs, n_bins
-        self.caps = [dev.capture(r) for r in raws]
-        st = np.zeros(len(raws), np.int64) if starts is None else np.asarray(starts, np.int64)
-        self.d_starts = dev.alloc(8 * len(raws)).upload(st)
-        self.sizes = [(REC * n_pairs, np.uint8), (4 * n_pairs * n_bins, np.uint8), (4 * n_pairs * n_bins, np.uint8)]
-        self.bufs = [dev.alloc(s) for s, _ in self.sizes]
-        self.k5 = [dev.alloc(4 * n_pairs) for _ in range(3)]
-
-    def fill(self, byte=0xA5):
-        for b in self.bufs:
-            b.upload(np.full(b.nbytes, byte, np.uint8))
-
-    def read(self):
-        self.dev.synchronize()
-        return tuple(b.download(np.uint8).tobytes() for b in self.bufs)
-
-    def caf(self, pairs, bin_first, n_bins, bpl=0, bufs=None):
-        d_out, d_bl, d_bp = bufs or self.bufs
-        self.dev.xcorr_caf_dev(self.caps, [c.nbytes for c in self.caps], self.d_starts, self.n, pairs, bin_first, n_bins, d_out,
-                               d_bl, d_bp, bins_per_launch=bpl)
-
-    def lags(self, pairs):
-        self.dev.xcorr_lags_dev(self.caps, [c.nbytes for c in self.caps], self.d_starts, self.n, pairs, *self.k5)
-        self.dev.synchronize()
-        return tuple(b.download(np.uint8, 4 * len(pairs)).tobytes() for b in self.k5)
-
-    def close(self):
-        for x in self.caps + self.bufs + self.k5 + [self.d_starts]:
-            x.free()
-
-
-def make_slots(dev, raws, n, flags=None):
-    sb = dev.tdoa_slot_bytes(n)
-    host = np.zeros(len(raws) * sb, np.uint8)
-    for a, r in enumerate(raws):
-        head = np.array([0 if flags is None else flags[a], 0], np.int64)
-        host[a * sb:a * sb + 16] = head.view(np.uint8)
-        host[a * sb + 16:a * sb + 16 + 2 * n] = r[:2 * n]
-    return dev.alloc(host.nbytes).upload(host), sb
-
-
-def as_k5(raw_out: bytes):
-    """lag | peak | margin_lag of the records, as the three byte strings K5 writes."""
-    rs = records(raw_out)
-    return (np.array([r.lag for r in rs], np.int32).tobytes(), np.array([r.peak for r in rs], np.float32).tobytes(),
-            np.array([r.margin_lag for r in rs], np.float32).tobytes())
 
 
 # ------------------------------------------------------------------ 4: bin 0 is K5
