@@ -1,7 +1,8 @@
-// The replica layer under the correlator bank (k_corr.hip), the counterfeit-signal subtraction (k_subtract.hip) and the
-// tracking loops (k_track.hip): those three include this, nothing else does.  All walk the same local replica -- a code
-// row resampled by a code NCO, times a 16-entry carrier table indexed by a carrier NCO -- the bank and the loops to
-// multiply the capture with it, the subtraction to take it off.  What defines the replica stands here once; the
+// The replica layer under the correlator bank (k_corr.hip), the counterfeit-signal subtraction (k_subtract.hip), the
+// tracking loops (k_track.hip) and the subtraction of tracked signals (k_subtract_track.hip): those four include this,
+// nothing else does.  All walk the same local replica -- a code row resampled by a code NCO, times a 16-entry carrier
+// table indexed by a carrier NCO -- the bank and the loops to multiply the capture with it, the subtractions to take it
+// off.  What defines the replica stands here once; the
 // kernels, their inner loops and their occupancy stay apart.
 //
 // A CHANNEL is a gj_corr_channel of include/gpsjam.h, good when reserved == 0, 0 <= code_row < n_code_rows,

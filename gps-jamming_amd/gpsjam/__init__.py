@@ -33,7 +33,7 @@ __all__ = ["Device", "DevBuf", "Capture", "GpsJamError", "GpsJamLibraryError", "
            "CrossSpectrum", "csd_rows", "CANCEL_DTYPE", "CORR_MAX_BLOCK", "CORR_CHANNEL_DTYPE", "corr_blocks", "CorrBank",
            "ACQ_MAX_PEAKS", "ACQ_PEAK_DTYPE", "ACQ_FLOOR_DTYPE", "SUB_BLOCK", "SUB_DTYPE", "SUB_FRAC", "SUB_MAX_AMP",
            "subtract_blocks", "ALIGN_BLOCK", "ALIGN_DTYPE", "ALIGN_PHASES", "ALIGN_TAPS", "ALIGN_ROT_LEN", "AlignParams",
-           "align_blocks", "TRACK_MAX_CHANNELS", "TRACK_MAX_EPOCHS", "TRACK_MAX_GAIN", "TRACK_STATE_DTYPE", "TRACK_EPOCH_DTYPE",
+           "align_blocks", "TRACK_MAX_CHANNELS", "TRACK_MAX_EPOCHS", "TRACK_MAX_GAIN", "TRACK_STATE_DTYPE", "TRACK_EPOCH_DTYPE", "SUB_TRACK_CHANNEL_DTYPE",
            "TrackParams"]
 
 _default = None
@@ -327,6 +327,29 @@ def _track_states(states) -> np.ndarray:
         if len(r) != 13 or any(not a <= v < b for v, a, b in zip(r, lo, hi)):
             raise GpsJamError(-1, f"invalid argument: a state is thirteen integers in the order of gj_track_state, not {r}")
         rec[k] = (r[:6], r[6], r[7], r[8], r[9], r[10], r[11:13])
+    return rec
+
+
+SUB_TRACK_CHANNEL_DTYPE = np.dtype([("start", np.uint32), ("code_row", np.int32)])          # gj_subtract_track_channel
+
+
+def _subtract_track_channels(channels, n_code_rows: int, n_epochs: int, block_samples: int, n_samples: int) -> np.ndarray:
+    """The channel table of ``Device.subtract_tracked`` as SUB_TRACK_CHANNEL_DTYPE records, checked on the host: it lives
+    in device memory once uploaded, where gj_subtract_track_dev cannot answer for it with a status."""
+    if isinstance(channels, np.ndarray) and channels.dtype == SUB_TRACK_CHANNEL_DTYPE:
+        rec = np.ascontiguousarray(channels).reshape(-1)
+    else:
+        rows = [tuple(int(v) for v in c) for c in channels]
+        for r in rows:
+            if len(r) != 2 or not (0 <= r[0] < 2 ** 32 and -2 ** 31 <= r[1] < 2 ** 31):
+                raise GpsJamError(-1, f"invalid argument: a channel is (start, code_row), not {r}")
+        rec = np.array(rows, SUB_TRACK_CHANNEL_DTYPE).reshape(-1)
+    for k, c in enumerate(rec):
+        if not 0 <= int(c["code_row"]) < n_code_rows:
+            raise GpsJamError(-1, f"invalid argument: channel {k}: code_row {int(c['code_row'])} outside the {n_code_rows} rows")
+        if int(c["start"]) + n_epochs * block_samples > n_samples:
+            raise GpsJamError(-1, f"invalid argument: channel {k}: {n_epochs} epochs of {block_samples} samples from start "
+                                  f"{int(c['start'])} run past the range's {n_samples}")
     return rec
 
 
@@ -1485,6 +1508,46 @@ class Device:
             out = d_out.download(TRACK_EPOCH_DTYPE, rec.size * n_epochs).reshape(rec.size, n_epochs)
             return out, d_st.download(TRACK_STATE_DTYPE, rec.size)
 
+    def subtract_tracked(self, capture, channels, codes, records, amplitudes, first_sample: int = 0,
+                         n_samples: Optional[int] = None, block_samples: int = 2048, dither: bool = True, seed: int = 0,
+                         n_epochs: Optional[int] = None):
+        """Subtraction of tracked signals (gj_subtract_track_dev): ``subtract`` with the replica's NCOs taken per epoch
+        from the records ``track`` returned.  ``channels``: SUB_TRACK_CHANNEL_DTYPE records or (start, code_row) rows, one
+        per tracked channel, ``start`` being its state's; ``records``: TRACK_EPOCH_DTYPE[n_channels][n_epochs], on the
+        host or in a device buffer (the one gj_track_dev wrote, as it is); ``amplitudes``: int32[n_channels][n_epochs][2]
+        in units of 2^-SUB_FRAC, what ``gpsjam.track.amplitudes`` makes of the records' prompts, on the host or in a
+        device buffer; ``n_epochs``: needed only where neither of the two is on the host.  ``capture``, ``codes``,
+        ``dither`` and ``seed`` as in ``subtract``.  The channel table is checked HERE, on the host (GJ_ERR_INVALID); a
+        record whose code NCO is out of bounds is not an error: by the definition its epoch is left alone.  Samples in
+        front of a channel's ``start`` and behind its last whole epoch keep that channel's signal.  Returns
+        ``(cleaned, records)`` as ``subtract`` does."""
+        first_sample, block_samples = int(first_sample), int(block_samples)
+        with contextlib.ExitStack() as temps:
+            cap, n_samples, d_codes, n_rows, _, _ = self._replica_inputs(temps, capture, (), codes, first_sample, n_samples,
+                                                                         block_samples)
+            n_ch = len(channels)
+            on_device = lambda v: isinstance(v, (DevBuf, int)) or hasattr(v, "data_ptr")
+            if n_epochs is None:
+                host = next((np.asarray(v) for v in (records, amplitudes) if not on_device(v)), None)
+                if host is None:
+                    raise ValueError("records and amplitudes are both on the device: n_epochs must be given")
+                per = 1 if host.dtype == TRACK_EPOCH_DTYPE else 2
+                n_epochs = host.size // (per * n_ch) if n_ch else 0
+            n_epochs = int(n_epochs)
+            rec = _subtract_track_channels(channels, n_rows, n_epochs, block_samples, n_samples)
+            if not on_device(records):
+                host = np.ascontiguousarray(records)
+                if host.dtype != TRACK_EPOCH_DTYPE or host.size != rec.size * n_epochs:
+                    raise ValueError(f"records must be TRACK_EPOCH_DTYPE[{rec.size}][{n_epochs}]")
+                records = temps.enter_context(DevBuf(self, max(host.nbytes, 8))).upload(host.reshape(-1))
+            d_amp = self._on_device(temps, amplitudes, np.int32, 2 * rec.size * n_epochs, "amplitudes",
+                                    f"{rec.size} channels of {n_epochs} epochs take {2 * rec.size * n_epochs}")
+            d_ch = temps.enter_context(DevBuf(self, max(rec.nbytes, 8))).upload(rec)
+            self._count("subtract_tracked")
+            return self._cleaned(n_samples, subtract_blocks(n_samples), SUB_DTYPE, lambda d_out, d_rec: self.subtract_track_dev(
+                cap, cap.nbytes, first_sample, n_samples, block_samples, n_epochs, d_codes, n_rows, d_ch, rec.size, records, d_amp,
+                _ffi.GJ_SUB_DITHER if dither else 0, seed, d_out, d_rec))
+
     def align(self, capture, params, taps, rot, n_out: Optional[int] = None):
         """Pair alignment (gj_align_dev): ``n_out`` samples (default: as many as ``capture`` holds) read from ``capture``
         along the time base and the phase of ``params`` -- an ``AlignParams`` or ``(pos0, pos_step, rot_phase, rot_step)``,
@@ -1573,6 +1636,18 @@ class Device:
                                               int(block_samples), _ptr(d_codes), int(n_code_rows), _ptr(d_channels),
                                               int(n_channels), _ptr(d_amp), int(flags), int(seed) & 0xFFFFFFFF, _ptr(d_out),
                                               _ptr(d_blocks) or None))
+
+    def subtract_track_dev(self, d_iq, nbytes, first_sample, n_samples, block_samples, n_epochs, d_codes, n_code_rows, d_channels,
+                           n_channels, d_epochs, d_amp, flags, seed, d_out, d_blocks=None):
+        """gj_subtract_track_dev: 2 * n_samples cleaned bytes into d_out and, if asked for, one 24-byte record (SUB_DTYPE)
+        per SUB_BLOCK samples into d_blocks, on the context's stream; ``d_epochs``: the 56-byte records gj_track_dev wrote;
+        ``seed`` is taken modulo 2^32."""
+        args = [int(v) for v in (block_samples, n_epochs, n_code_rows, n_channels, flags)]
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in args):
+            raise GpsJamError(-5, "unsupported: an argument outside int32")
+        self._check(self._lib.gj_subtract_track_dev(self._ctx, _ptr(d_iq), int(nbytes), int(first_sample), int(n_samples), args[0],
+                                                    args[1], _ptr(d_codes), args[2], _ptr(d_channels), args[3], _ptr(d_epochs),
+                                                    _ptr(d_amp), args[4], int(seed) & 0xFFFFFFFF, _ptr(d_out), _ptr(d_blocks) or None))
 
     def align_dev(self, d_iq, nbytes, params, d_taps, d_rot, n_out, d_out, d_blocks=None):
         """gj_align_dev: 2 * n_out aligned bytes into d_out and, if asked for, one 16-byte record (ALIGN_DTYPE) per

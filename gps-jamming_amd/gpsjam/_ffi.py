@@ -191,6 +191,11 @@ class TrackEpoch(C.Structure):
                 ("carr_step", C.c_uint32), ("code_phase", C.c_uint64), ("code_step", C.c_uint64), ("e", C.c_int32), ("c", C.c_int32)]
 
 
+class SubtractTrackChannel(C.Structure):
+    """gj_subtract_track_channel: one entry of gj_subtract_track_dev's channel table (include/gpsjam.h)."""
+    _fields_ = [("start", C.c_uint32), ("code_row", C.c_int32)]
+
+
 class AlignBlock(C.Structure):
     """gj_align_block: one GJ_ALIGN_BLOCK-sample record of the pair alignment (include/gpsjam.h)."""
     _fields_ = [("power_out", C.c_uint64), ("n_clipped", C.c_int32), ("n_edge", C.c_int32)]
@@ -358,6 +363,7 @@ SIGNATURES = {
     "gj_subtract_blocks": (_sz, [_sz]),
     "gj_subtract_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _vp, _i, _vp, _i, _vp, _i, C.c_uint32, _vp, _vp]),
     "gj_track_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _i, _vp, _i, TrackParams, _vp]),
+    "gj_subtract_track_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, C.c_uint32, _vp, _vp]),
     "gj_align_blocks": (_sz, [_sz]),
     "gj_align_dev": (_i, [_vp, _vp, _sz, AlignParams, _vp, _vp, _sz, _vp, _vp]),
     "gj_pack_result_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

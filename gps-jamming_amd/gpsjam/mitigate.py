@@ -9,7 +9,7 @@ measures its spectrum, the excisor cleans the whole capture.
     python -m gpsjam.mitigate IN.bin OUT.bin --pulsed [--window W] [--guard G] [--rise-db D]
     python -m gpsjam.mitigate A.bin OUT.bin --spatial B.bin [--nfft N] [--frames-per-row M] [--p-fa P] [--lag L|k5]
     python -m gpsjam.mitigate A.bin OUT.bin --spatial B.bin --spatial2 C.bin [--lag L|k5] [--lag2 L|k5]
-    python -m gpsjam.mitigate A.bin OUT.bin --spoofed B.bin [--peaks K] [--out-b OUT_B.bin]
+    python -m gpsjam.mitigate A.bin OUT.bin --spoofed B.bin [--peaks K] [--out-b OUT_B.bin] [--tracked]
 
 writes the cleaned file, byte for byte as long as the input (``--spoofed``: as long as the range it cleans), for gnssdec.
 
@@ -39,7 +39,9 @@ A spoofer is no interference in any of these senses: its signals have the satell
 ``spoof.scan_peaks`` tells them by their common direction, and ``clean_spoofed`` (``--spoofed``) takes them out of both
 captures by successive interference cancellation: each counterfeit signal rebuilt from its correlator outputs
 (``Device.corr_bank``, ``postcorr.amplitudes``) and subtracted (``Device.subtract``, gj_subtract_dev).  A plain
-acquisition on the result locks onto the authentic signals.
+acquisition on the result locks onto the authentic signals.  That is open loop and covers a tenth of a second;
+``--tracked`` follows each counterfeit signal with the tracking loops and cleans to the end of the capture
+(``spoof.remove_tracked``, gj_subtract_track_dev).
 
 Nothing here computes on the CPU but the threshold's arithmetic on one PSD row or one floor value, the weights'
 on the rows x nfft sums, and the amplitudes' on a hundred prompts per signal.
@@ -403,14 +405,19 @@ class CleanedSpoofed(NamedTuple):
 
 
 def clean_spoofed(dev, a, b, k: int = 2, search=None, tol: float = 0.15, min_common: int = 4, pfa: float = 1e-3,
-                  first_sample: int = 0, duration_s: float = 0.1, dither: bool = True) -> CleanedSpoofed:
+                  first_sample: int = 0, duration_s: float = 0.1, dither: bool = True, tracked: bool = False) -> CleanedSpoofed:
     """Two antennas on one clock with the counterfeit signals taken out.  ``spoof.scan_peaks`` (``k`` peaks per PRN) names
     the counterfeit candidates: the ones that share one inter-antenna phase.  When it says ``spoofed``, ``spoof.remove``
     takes them out of ``a`` -- re-observed, one amplitude per code period from the correlator bank, replicas subtracted
     by gj_subtract_dev -- and out of ``b`` with the SAME channels and b's own amplitudes.  What is left holds the
     authentic signals: a plain acquisition on it finds them, and ``spoof.scan`` on the cleaned pair measures their
     phases.  ``a`` and ``b``: resident ``Capture``s or host bytes (uploaded once each); ``search``: as in
-    ``spoof.scan``.  The result covers samples first_sample .. + duration_s (``spoof.remove`` states why no more)."""
+    ``spoof.scan``.  The result covers samples first_sample .. + duration_s (``spoof.remove`` states why no more).
+    ``tracked``: the candidates are found on those ``duration_s`` as before and then taken out from ``first_sample`` to
+    the END of each capture by ``spoof.remove_tracked``: each antenna follows them through tracking loops of its own and
+    subtracts with the NCOs those loops had (gj_subtract_track_dev).  ``spoof.remove_tracked`` states the limits: samples
+    in front of a signal's first epoch and behind its last whole one keep it, an epoch with a bit flip inside it is
+    under-subtracted, and one complex dimension of noise per epoch and signal goes out with the signal."""
     from . import gnss, spoof
     own = search is None
     if own:
@@ -419,9 +426,15 @@ def clean_spoofed(dev, a, b, k: int = 2, search=None, tol: float = 0.15, min_com
         with dev._resident(a) as cap_a, dev._resident(b) as cap_b:
             report = spoof.scan_peaks(dev, cap_a, cap_b, search, k, tol, min_common, pfa, first_sample, duration_s)
             fakes = report.counterfeit if report.spoofed else []
-            out_a = spoof.remove(dev, cap_a, fakes, search, first_sample, duration_s, dither)
+            if tracked:
+                out_a = spoof.remove_tracked(dev, cap_a, fakes, search, first_sample, dither=dither)
+            else:
+                out_a = spoof.remove(dev, cap_a, fakes, search, first_sample, duration_s, dither)
             try:
-                out_b = spoof.remove(dev, cap_b, fakes, search, first_sample, duration_s, dither, observations=out_a.observations)
+                if tracked:
+                    out_b = spoof.remove_tracked(dev, cap_b, fakes, search, first_sample, dither=dither)
+                else:
+                    out_b = spoof.remove(dev, cap_b, fakes, search, first_sample, duration_s, dither, observations=out_a.observations)
             except BaseException:
                 out_a.capture.free()
                 raise
@@ -475,6 +488,9 @@ def main(argv=None) -> int:
     ap.add_argument("--out-b", metavar="OUT_B.bin", default=None, help="--spoofed: also write the second antenna's cleaned range")
     ap.add_argument("--first-sample", type=int, default=0, help="--spoofed: where the cleaned range starts")
     ap.add_argument("--duration", type=float, default=0.1, help="--spoofed: seconds of the cleaned range")
+    ap.add_argument("--tracked", action="store_true",
+                    help="--spoofed: follow the counterfeit signals with tracking loops and clean from --first-sample to the end of the "
+                         "input (spoof.remove_tracked); --duration is then the part the signals are found on")
     args = ap.parse_args(argv)
     if sum(map(bool, (args.pulsed, args.swept, args.spatial, args.spoofed))) > 1:
         ap.error("--pulsed, --swept, --spatial and --spoofed exclude each other")
@@ -487,7 +503,7 @@ def main(argv=None) -> int:
             try:
                 with dev.capture(args.input) as cap, dev.capture(args.spoofed) as aux:
                     res = clean_spoofed(dev, cap, aux, k=args.peaks, search=search, first_sample=args.first_sample,
-                                        duration_s=args.duration)
+                                        duration_s=args.duration, tracked=args.tracked)
                     try:
                         res.capture_a.download().tofile(args.output)
                         if args.out_b:

@@ -19,7 +19,9 @@ signals of one PRN closer than the guard (2 samples per chip either side) are on
 
 ``remove`` takes the counterfeit candidates out of a capture -- replicas rebuilt from the bank's prompts and subtracted
 (``Device.subtract``, gj_subtract_dev) -- so that a receiver can go back to the authentic ones;
-``gpsjam.mitigate.clean_spoofed`` does it for both antennas.
+``gpsjam.mitigate.clean_spoofed`` does it for both antennas.  ``remove`` is open loop and good for a tenth of a second;
+``remove_tracked`` follows every candidate with the tracking loops (``gpsjam.track``) and takes it out of the whole
+capture with the NCOs the loops had, epoch by epoch (``Device.subtract_tracked``, gj_subtract_track_dev).
 
     python -m gpsjam.spoof A.bin B.bin [--peaks K]
 """
@@ -246,7 +248,8 @@ def remove(dev, capture, candidates, search, first_sample: int = 0, duration_s: 
     an earlier ``remove`` on another antenna of the same clock -- the candidates are then not observed again, the SAME
     channels are used, and the amplitudes are this capture's own.  No candidate: the range comes back byte for byte.
 
-    Limits.  One set of channels serves the whole range: 0.1 s is fine, ten seconds of a moving receiver are not.  The
+    Limits.  One set of channels serves the whole range: 0.1 s is fine, ten seconds of a moving receiver are not
+    (``remove_tracked`` is for those).  The
     replica has the mixer's 16-step carrier: what the bank sees is nulled, about 1 % of the signal's power stays behind
     as the staircase's harmonics, far from its Doppler.  Per code period one complex dimension of the noise goes out
     with the signal.  Two copies closer than the K-peak guard are one peak and are removed as one."""
@@ -287,6 +290,89 @@ def remove(dev, capture, candidates, search, first_sample: int = 0, duration_s: 
                     db = float(10.0 * np.log10(mb / ma)) if mb > 0.0 and ma > 0.0 else (float("inf") if mb > 0.0 else 0.0)
                     removals.append(Removal(o.prn, int(c.code_index), o.doppler_hz, postcorr.cn0(pb, period_s), postcorr.cn0(pa, period_s), db))
                 seen.extend(obs)
+        except BaseException:
+            if held is not None:
+                held.free()
+            raise
+    return Removed(held, removals, records, seen)
+
+
+TRACKED_WINDOW = 100                     # epochs of one measuring window of ``remove_tracked``
+
+
+def _window_prompts(dev, cap, origin: int, tracks, rows, B: int, windows):
+    """Per track the prompts of one-tap banks over ``windows`` (first epochs) of TRACKED_WINDOW epochs each: a window
+    starts on that track's epoch boundary, ``origin`` + start + m B of ``cap``, and holds the channel of that epoch's
+    record for its length."""
+    out = []
+    for k, t in enumerate(tracks):
+        parts = []
+        for m in windows:
+            r = t.records[m]
+            ch = postcorr.Channel(int(r["code_phase"]), int(r["code_step"]), int(r["carr_phase"]), int(r["carr_step"]), k)
+            count = min(TRACKED_WINDOW, t.records.size - m)
+            parts.append(dev.corr_bank(cap, [ch], rows, origin + t.start + m * B, count * B, B, (0,)).tap(0)[0])
+        out.append(np.concatenate(parts))
+    return out
+
+
+def remove_tracked(dev, capture, candidates, search, first_sample: int = 0, pull_in: int = 200, dither: bool = True) -> Removed:
+    """``remove`` over a whole capture, closed loop: ``track.follow(results=...)`` runs its DLL / FLL / PLL on every
+    candidate from ``first_sample`` to the end of ``capture`` (``pull_in`` epochs with the wide loops),
+    ``track.amplitudes`` makes one amplitude per epoch from each epoch's own prompt, and ``Device.subtract_tracked``
+    (gj_subtract_track_dev) rebuilds every replica with the NCOs its loop had in that epoch and takes it off the bytes.
+    At most BANK_CHANNELS candidates go out per pass, as in ``remove``.  A ``Removal`` per candidate: C/N0 and
+    suppression from one-tap banks before and after, on windows of TRACKED_WINDOW epochs, one per second of capture,
+    each at the channel of its first epoch's record; ``doppler_hz`` is the loop's mean.  ``Removed.observations`` holds
+    the ``track.Track`` of every candidate.  No candidate: the range comes back byte for byte.
+
+    Limits.  Samples in front of a channel's ``start`` (the candidate's code index) and behind its last whole epoch keep
+    that channel's signal.  An epoch with a navigation bit flip inside it has a small prompt and is under-subtracted.
+    One amplitude per epoch takes one complex dimension of the noise per epoch out with the signal.  While the loops
+    pull in, the replica is as good as the loops are.  The staircase carrier and the K-peak guard: as in ``remove``."""
+    from . import track
+    candidates = list(candidates)
+    with dev._resident(capture) as cap:
+        first = int(first_sample)
+        n = cap.nsamples - first
+        if not candidates:
+            cleaned, records = _copy_range(dev, cap, first, n)
+            return Removed(cleaned, [], records, [])
+        removals, seen, held, records = [], [], None, None
+        try:
+            for at in range(0, len(candidates), BANK_CHANNELS):
+                part = candidates[at:at + BANK_CHANNELS]
+                src = cap if held is None else held
+                results = [gnss.AcqResult(c.prn, True, c.ratio, c.cn0_dbhz, c.code_index,
+                                          int(np.argmin(np.abs(np.asarray(search.freqs) - c.doppler_hz))), c.doppler_hz, 0, 0.0, 0.0, 0.0)
+                           for c in part]
+                tracks = track.follow(dev, src, search, first, pull_in, results=results)
+                if len(tracks) != len(part):
+                    raise ValueError("the capture holds no whole epoch behind the candidates' code indices")
+                B = int(round(tracks[0].block_s * search.fs))
+                rows = postcorr.codes([t.prn for t in tracks])
+                rec_in = np.stack([t.records for t in tracks])
+                E = rec_in.shape[1]
+                stride = max(TRACKED_WINDOW, int(round(search.fs / B)))
+                windows = [m for m in range(0, E, stride) if m + TRACKED_WINDOW <= E] or [0]
+                before = _window_prompts(dev, src, first, tracks, rows, B, windows)
+                cleaned, rec = dev.subtract_tracked(src, [(t.start, k) for k, t in enumerate(tracks)], rows, rec_in,
+                                                    track.amplitudes(rec_in, B), first, n, B, dither=dither)
+                if records is None:
+                    records = rec                            # ``total`` is the input's: the first pass reads it
+                else:
+                    records["removed"] += rec["removed"]
+                    records["n_clipped"] += rec["n_clipped"]
+                if held is not None:
+                    held.free()
+                held, first = cleaned, 0                     # the cleaned range is a capture of its own, from its sample 0
+                after = _window_prompts(dev, held, 0, tracks, rows, B, windows)
+                for c, t, pb, pa in zip(part, tracks, before, after):
+                    mb, ma = float(np.mean(np.abs(pb) ** 2)), float(np.mean(np.abs(pa) ** 2))
+                    db = float(10.0 * np.log10(mb / ma)) if mb > 0.0 and ma > 0.0 else (float("inf") if mb > 0.0 else 0.0)
+                    removals.append(Removal(t.prn, int(c.code_index), float(t.doppler_hz.mean()), postcorr.cn0(pb, t.block_s),
+                                            postcorr.cn0(pa, t.block_s), db))
+                seen.extend(tracks)
         except BaseException:
             if held is not None:
                 held.free()

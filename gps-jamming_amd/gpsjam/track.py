@@ -5,7 +5,9 @@ rate per channel for the whole range, which is fine for 0.1 s and not for 10 s o
 receiver spends its life in closed loops instead (sdrtracking -> correlator -> pll / dll, sdrtrk.c): each millisecond
 the early, prompt and late sums steer a carrier and a code NCO.  ``Device.track`` (gj_track_dev, k_track.hip) runs that
 loop for every channel in one launch, in exact integers; what is left for the host is the loop gains, the hand-over from
-the acquisition and float arithmetic on the records, and lives here.
+the acquisition and float arithmetic on the records, and lives here.  ``amplitudes`` makes of the records what
+``Device.subtract_tracked`` (gj_subtract_track_dev) needs to take a followed signal out of the capture again
+(``gpsjam.spoof.remove_tracked``).
 
 Nothing here is a CPU fallback for the kernel: the records come from the library.
 """
@@ -123,6 +125,24 @@ def follow(dev, capture, search, first_sample: int = 0, pull_in: int = 200, bloc
         return []
     rec = np.concatenate(pieces, axis=1)
     return [_series(prn, int(starts[k]), rec[k], st[k], block_s, float(search.fs), window) for k, prn in enumerate(prns)]
+
+
+def amplitudes(records, block_samples: int) -> np.ndarray:
+    """int32[n_channels][n_epochs][2]: the amplitudes (aI, aQ) with which ``Device.subtract_tracked`` takes out what the
+    loops followed, from TRACK_EPOCH_DTYPE[n_channels][n_epochs] records (one channel's row alone counts as one channel).
+    Per epoch the least-squares amplitude of the loop's own template, as ``postcorr.amplitudes`` makes it per code period:
+
+        a = round(P / (block_samples * MIXER_GAIN) * 2^SUB_FRAC),    P the epoch's prompt
+
+    The prompt was made with exactly the NCO the replica will be made with, so the replica's own prompt is P again and
+    the epoch's prompt is nulled.  Limits: an epoch with a navigation bit flip inside it has a small prompt and is
+    under-subtracted (``states`` starts every channel on its code period, so a flip falls between epochs unless the code
+    has slipped); and one amplitude per epoch takes one complex dimension of the noise per epoch out with the signal."""
+    rec = np.asarray(records)
+    if rec.ndim == 1:
+        rec = rec[None, :]
+    alpha = rec["prompt"].astype(np.float64) / (float(block_samples) * postcorr.MIXER_GAIN) * 2.0 ** postcorr.SUB_FRAC
+    return np.floor(alpha + 0.5).astype(np.int32)
 
 
 def main(argv=None) -> int:

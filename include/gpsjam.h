@@ -1062,6 +1062,61 @@ int gj_track_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_s
                  gj_track_state* d_states /* [n_channels], in/out */, int n_channels, gj_track_params params,
                  gj_track_epoch* d_out /* [n_channels][n_epochs] */);
 
+/* ------------------------------------------------- subtraction of tracked signals ---- */
+/* gj_subtract_dev with the replica's NCOs taken per EPOCH from the records gj_track_dev wrote, not from one channel per
+ * call: a counterfeit signal followed by the loops is taken out over a whole capture, not over the tenth of a second
+ * one Doppler and one code rate hold for.  The terms are the subtraction's and the bank's (GJ_CORR_COS_TABLE with
+ * S[i] = C[(i - 4) & 15], the chip rule at tap 0, I, Q = byte - 128 WHATEVER gj_set_unpack says, GJ_SUB_*,
+ * gj_subtract_block, gj_subtract_blocks).  gpsjam/track.py (amplitudes) makes the amplitudes from the records' own
+ * prompts; gpsjam/spoof.py (remove_tracked) joins the pieces.
+ *
+ * For sample t = 0 .. n_samples-1 of the range and channel ch = d_channels[.], with B = block_samples, E = n_epochs:
+ *
+ *   r       = t - start                       the channel is SILENT at t if r < 0 or r >= E*B; otherwise
+ *   m, u    = r div B, r mod B;   rec = d_epochs[ch][m]
+ *             the channel is also silent at t if rec.code_phase >= 1023 * 2^32 or rec.code_step >= GJ_CORR_MAX_CODE_STEP
+ *   chip    = ((rec.code_phase + u*rec.code_step) mod 1023 * 2^32) >> 32,   c = d_codes[code_row][chip] as +-1
+ *   i       = ((rec.carr_phase + u*rec.carr_step) mod 2^32) >> 28
+ *   a       = clamp(d_amp[ch][m][0..1], -GJ_SUB_MAX_AMP, +GJ_SUB_MAX_AMP)
+ *   R_I, R_Q  gj_subtract_dev's sums, over the channels that are not silent at t
+ *   d, q, the output byte and the gj_subtract_block records: gj_subtract_dev's, word for word; the dither is keyed on
+ *   the ABSOLUTE sample first_sample + t.
+ *
+ * Only carr_phase, carr_step, code_phase and code_step of a record are read.  The records are device memory and far
+ * too many for every workgroup to check, so a record out of bounds adds nothing: that is part of the definition, not
+ * an error.  d_amp: int32[n_channels][n_epochs][2], not checked (the clamp is part of the definition).
+ *
+ * Consequences.  With records that are one constant channel advanced by m*B samples per epoch, start 0 and
+ * n_samples = E*B, the call writes the bytes and the records of gj_subtract_dev with that channel and the same
+ * amplitudes.  All amplitudes 0, or every channel silent everywhere, gives back the input bytes.  Every value is an
+ * exact integer: the bytes do not depend on tiling or order, two calls give identical bits.  Widths: u < 4096 and
+ * code_step < 2^34 give u*code_step < 2^46; R's bound is gj_subtract_dev's (64 channels at the most add up).  Samples
+ * in front of a channel's start and behind its last whole epoch keep that channel's signal.
+ *
+ * Limits (GJ_ERR_UNSUPPORTED): gj_subtract_dev's (block_samples a multiple of 16 in 16 .. GJ_CORR_MAX_BLOCK, n_channels
+ * 1 .. GJ_CORR_MAX_CHANNELS, n_samples 1 .. GJ_CORR_MAX_SAMPLES); n_epochs < 1.
+ * GJ_ERR_INVALID: gj_subtract_dev's (a null ctx or buffer, d_epochs among them; an odd d_iq or d_codes; a d_amp that is
+ * not 4-byte aligned, a d_blocks that is not 8-byte aligned; n_code_rows < 1; a flag bit other than GJ_SUB_DITHER; a
+ * range that runs past the capture; a d_out that overlaps the capture); a d_channels or d_epochs that is not 8-byte
+ * aligned; n_epochs*B > n_samples.  A refused call enqueues nothing.
+ * The channel table is in DEVICE memory: Device.subtract_tracked (gpsjam/__init__.py) checks it on the host before it
+ * uploads it and raises GJ_ERR_INVALID, and every workgroup checks all of it before it reads a chip: if ANY code_row
+ * lies outside 0 .. n_code_rows-1 or ANY start + n_epochs*B > n_samples, the launch writes NOTHING, neither a byte nor
+ * a record.
+ * One launch on the context's stream; no workspace, no memset, no atomics: 0 bytes to gj_reserve, the call never
+ * allocates.  Every byte and every record is written by exactly one workgroup. */
+typedef struct gj_subtract_track_channel {   /* 8 bytes */
+    uint32_t start;        /* this channel's epoch 0 begins `start` samples after first_sample (gj_track_state.start) */
+    int32_t  code_row;     /* row of d_codes */
+} gj_subtract_track_channel;
+int gj_subtract_track_dev(gj_ctx* ctx, const uint8_t* d_iq, size_t nbytes, size_t first_sample, size_t n_samples,
+                          int block_samples, int n_epochs, const int16_t* d_codes /* [n_code_rows][1023], +-1 */,
+                          int n_code_rows, const gj_subtract_track_channel* d_channels /* at most 64 */, int n_channels,
+                          const gj_track_epoch* d_epochs /* [n_channels][n_epochs], as gj_track_dev wrote them */,
+                          const int32_t* d_amp /* [n_channels][n_epochs][2]  aI, aQ */,
+                          int flags, uint32_t seed, uint8_t* d_out /* [2*n_samples] */,
+                          gj_subtract_block* d_blocks /* [gj_subtract_blocks(n_samples)] or NULL */);
+
 /* ------------------------------------------------- pair alignment --------------------- */
 /* One uint8 I/Q capture written from another along a linear time base and a linear phase: antenna b brought onto
  * antenna a's clock, for receivers that each run on a crystal of their own (the crystal sets the sample clock AND the
