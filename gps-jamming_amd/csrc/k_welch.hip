@@ -44,6 +44,18 @@ __device__ __forceinline__ c2 one_minus_hi(c2 a, c2 p) {
     return r;
 }
 
+// a * p.x + q  /  a * p.y + q : a pair scaled by one half of a packed pair of scalars and added to a pair
+__device__ __forceinline__ c2 add_scaled_lo(c2 a, c2 p, c2 q) {
+    c2 r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(a), "v"(p), "v"(q));
+    return r;
+}
+__device__ __forceinline__ c2 add_scaled_hi(c2 a, c2 p, c2 q) {
+    c2 r;
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(p), "v"(q));
+    return r;
+}
+
 // N = 32 .. 4096 run in the "three workgroups per CU" shape (<= 168 VGPRs, one LDS buffer with two barriers per
 // exchange, window kept as 16 floats, scalar |X|^2 accumulators: +32 VALU instructions per step, but a third wave per
 // SIMD to fill the issue slots -- a wave issues at most one instruction every ~5 cycles, whatever its kind).  Measured
@@ -297,6 +309,18 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
     unsigned rawh[CARRY ? 8 : 1];      // CARRY: only the new half segment is ever loaded
     c2 carry[CARRY ? 8 : 1];           // CARRY: 2u - off2 of the previous step's second half = this step's first half
     [[maybe_unused]] unsigned ws_cur = 0, ws_prv = 2;   // HS: slot of this step's half-sum / of the previous step's
+    // Detrend: bins 0 and 1 end up in slot 0 of the threads jl = 0 and 1, bin N-1 in slot 15 of thread jl = TF-1
+    // (WelchBins).  Per lane, what the segment's sum is multiplied by before it is added to slot 0 / slot 15:
+    // (2048 points keep the predicated form: that kernel spills already, and two more live registers make it spill more)
+    constexpr bool FIX_FMA = TF >= 2 && N != 2048;
+    static_assert(!FIX_FMA || (WelchBins<N>::slot(0) == 0 && WelchBins<N>::slot(1) == 0 && WelchBins<N>::slot(N - 1) == 15 &&
+                             WelchBins<N>::jl(0) == 0 && WelchBins<N>::jl(1) == 1 && WelchBins<N>::jl(N - 1) == TF - 1), "detrend slots");
+    [[maybe_unused]] const c2 fix_c = make_c2(jl == 0 ? -0.5f : (jl == 1 ? 0.25f : 0.f), jl == TF - 1 ? 0.25f : 0.f);
+    [[maybe_unused]] const c2 ksum = make_c2(-g.off2 * N, -g.off2 * N);
+    // A transform of several waves adds its waves' half-segment sums in the lanes that detrend; where the half is carried
+    // anyway, so is its total (4096 points; at 1024 one wave's sum is the total, and 2048 has no register to spare)
+    constexpr bool CARRY_SUM = CARRY && WPF > 1;
+    [[maybe_unused]] c2 half_prev = make_c2(0.f, 0.f);   // CARRY_SUM, in the lanes that detrend: (sum I, sum Q) of the previous half segment
     if constexpr (CARRY) {
         // first step of the group's run: the first half has no predecessor -- unpack it here, once.  Both halves are
         // asked for before the first is waited for: one exposed round trip per workgroup, not two.
@@ -315,6 +339,13 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
         if ((tid & 63) == 0) {
             wsum[ws_prv][b][(tid >> 6) % WPF][0] = li;
             wsum[ws_prv][b][(tid >> 6) % WPF][1] = lq;
+        }
+        if constexpr (CARRY_SUM) {
+            __syncthreads();
+            if (jl <= 1 || jl == TF - 1) {
+#pragma unroll
+                for (int k = 0; k < WPF; ++k) { half_prev.x += wsum[ws_prv][b][k][0]; half_prev.y += wsum[ws_prv][b][k][1]; }
+            }
         }
     } else {
         load_step(raw, RUNS ? seg_idle : ((seg_lo + b < seg_hi) ? seg_lo + b : seg_lo));
@@ -400,24 +431,39 @@ __global__ __launch_bounds__(kBlockThreads, WelchCfg<N>::min_waves) void welch_k
                 si = 0.f; sq = 0.f;
 #pragma unroll
                 for (int k = 0; k < WPF; ++k) { si += wsum[cur][b][k][0]; sq += wsum[cur][b][k][1]; }
-                if constexpr (HS) {
+                if constexpr (CARRY_SUM) {
+                    // the previous half segment's total is CARRIED, not added up again from its per-wave sums: sums
+                    // of bytes, exact in float whatever the order
+                    const float hi = si, hq = sq;
+                    si += half_prev.x; sq += half_prev.y;
+                    half_prev = make_c2(hi, hq);
+                } else if constexpr (HS) {
 #pragma unroll
                     for (int k = 0; k < WPF; ++k) { si += wsum[prv][b][k][0]; sq += wsum[prv][b][k][1]; }
                 }
             }
         }
-        const float Sx = fmaf(2.0f, si, -g.off2 * N), Sy = fmaf(2.0f, sq, -g.off2 * N);   // sum of (2u - off2)
-        if (jl == WelchBins<N>::jl(0)) {
-            v[WelchBins<N>::slot(0)].x -= 0.5f * Sx;
-            v[WelchBins<N>::slot(0)].y -= 0.5f * Sy;
-        }
-        if (jl == WelchBins<N>::jl(1)) {
-            v[WelchBins<N>::slot(1)].x += 0.25f * Sx;
-            v[WelchBins<N>::slot(1)].y += 0.25f * Sy;
-        }
-        if (jl == WelchBins<N>::jl(N - 1)) {
-            v[WelchBins<N>::slot(N - 1)].x += 0.25f * Sx;
-            v[WelchBins<N>::slot(N - 1)].y += 0.25f * Sy;
+        if constexpr (FIX_FMA) {
+            // v[0] += c0 S and v[15] += c15 S in EVERY lane (fix_c), one packed FMA each: in the lanes that hold the three
+            // bins the same single rounding as the predicated v -= 0.5 S / v += 0.25 S
+            // below, and v + 0 S = v in all others (S is finite; a -0 would become +0, which |X|^2 does not see)
+            const c2 S = twice_plus_k(make_c2(si, sq), ksum);   // sum of (2u - off2), both components
+            v[0] = add_scaled_lo(S, fix_c, v[0]);
+            v[15] = add_scaled_hi(S, fix_c, v[15]);
+        } else {
+            const float Sx = fmaf(2.0f, si, -g.off2 * N), Sy = fmaf(2.0f, sq, -g.off2 * N);   // sum of (2u - off2)
+            if (jl == WelchBins<N>::jl(0)) {
+                v[WelchBins<N>::slot(0)].x -= 0.5f * Sx;
+                v[WelchBins<N>::slot(0)].y -= 0.5f * Sy;
+            }
+            if (jl == WelchBins<N>::jl(1)) {
+                v[WelchBins<N>::slot(1)].x += 0.25f * Sx;
+                v[WelchBins<N>::slot(1)].y += 0.25f * Sy;
+            }
+            if (jl == WelchBins<N>::jl(N - 1)) {
+                v[WelchBins<N>::slot(N - 1)].x += 0.25f * Sx;
+                v[WelchBins<N>::slot(N - 1)].y += 0.25f * Sy;
+            }
         }
         if (active) {
 #pragma unroll

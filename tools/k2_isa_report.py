@@ -8,11 +8,13 @@ that file (asked of `make -n`, not copied) and prints, for every welch_kernel in
     sample loads -- stand relative to the LDS exchanges' barriers / wave fences;
   * how many vector (VALU) instructions lie between the last sample load and the s_waitcnt vmcnt that covers it,
     followed along the loop's fall-through path and across its back edge.
-It reads loads, waits, barriers, LDS instructions and the register summary, nothing else.
+  * for every block of that loop together: instructions, vector instructions, s_nop and branches.
+It reads loads, waits, barriers, LDS instructions, mnemonics and the register summary, nothing else.
 
     python tools/k2_isa_report.py                 # the table
     python tools/k2_isa_report.py --json          # the same as JSON (tests/test_k2_prefetch_isa.py reads this)
     python tools/k2_isa_report.py --source k_ridge.hip --kernels ridge   # another file's kernels, e.g. the short-time front end
+    python tools/k2_isa_report.py --source k_scan.hip --kernels stream_scan_kernel   # the fused scan (its loop: one full tile)
     python tools/k2_isa_report.py --asm FILE      # report on an assembly file made earlier (e.g. of another commit)
 """
 import argparse
@@ -169,9 +171,12 @@ def report_kernel(f):
     syncs = [i for i in path if is_sync(ins[i][0])]
     lds_w = [i for i in path if ins[i][0].startswith("ds_write")]
     lds_r = [i for i in path if ins[i][0].startswith("ds_read")]
+    body = [op for op, _, _ in ins[head:end + 1]]    # every block of the loop, whichever way its branches go
     rep["loop"] = {
         "instructions": len(path),
         "valu": sum(is_valu(ins[i][0]) for i in path),
+        "all_blocks": {"instructions": len(body), "valu": sum(is_valu(op) for op in body), "s_nop": body.count("s_nop"),
+                       "branches": sum(op.startswith(("s_cbranch", "s_branch")) for op in body)},
         "blocks_on_path": 1 + sum(bool(ins[i][2]) for i in path[1:]),
         "sync_kind": ("s_barrier" if any(ins[i][0] == "s_barrier" for i in syncs) else "wave fence") if syncs else None,
         "sync_at": [pos[i] for i in syncs],
@@ -224,6 +229,9 @@ def kernel_key(name):
     m = re.search(r"welch_kernelILi(\d+)ELb([01])E", name)
     if m:
         return f"welch_kernel<{m.group(1)},{'true' if m.group(2) == '1' else 'false'}>"
+    m = re.search(r"stream_scan_kernelILb([01])E", name)
+    if m:
+        return f"stream_scan_kernel<{'true' if m.group(1) == '1' else 'false'}>"
     return name
 
 
@@ -241,6 +249,8 @@ def print_table(rep):
             continue
         print(f"    steady-state loop: {lp['instructions']} instructions on the main path ({lp['valu']} VALU), "
               f"{lp['blocks_on_path']} block(s); exchanges ordered by {lp['sync_kind']} at {lp['sync_at']}")
+        ab = lp["all_blocks"]
+        print(f"    all blocks of the loop: {ab['instructions']} instructions, {ab['valu']} VALU, {ab['s_nop']} s_nop, {ab['branches']} branches")
         print(f"    first LDS write at {lp['first_lds_write_at']}, first LDS read at {lp['first_lds_read_at']}; "
               f"loads ({', '.join(lp['load_kinds']) or 'none'}) at {lp['load_at']}")
         if "loads_before_first_sync" in lp:
